@@ -6,7 +6,12 @@ convolution (2 x 5453 = 10906) plus the PriorPose2 row in ONE kernel launch, wit
 already resident in HBM.  One convolution = what IIF `approxConvBelief` does for one factor
 and target: N=100 getSample + inflateCycles(3) x {entropy inflation, 100 per-particle root-finds}.
 
-    python bench.py [--gpus N --steps K --warmup W] [--solver newton|nelder_mead|closed_form]
+    python bench.py [--gpus N --steps K --warmup W] [--solver newton|nelder_mead|closed_form] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the line.  --full adds everything else the line has carried:
+the per-solver throughputs and rooflines, the solve-level wall-clocks, the CPU baseline, the stored counter passes and, for
+K < 1000, more blocks of K steps for their spread.  --dump-outputs DIR writes the proposals of the last timed step to
+DIR/*.npy (float64; a fixed, seeded sample of rows above 64 MB).
 
 N>1 (launched by torch.distributed.run, one rank per GPU): weak scaling -- every rank owns one
 Manhattan-sized segment of a chain of segments; after each sweep the ranks all-gather their
@@ -32,6 +37,7 @@ import numpy as np  # noqa: E402
 #   gauss_newton / nelder_mead (start from the belief point): fixed 3 + start point u0 3 + solution 3 = 72
 BYTES_PER_PARTICLE_P2P2 = {"closed_form": 48, "newton": 48, "gauss_newton": 72, "nelder_mead": 72}
 HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_BYTES_MAX = 64 << 20     # --dump-outputs: all files of one run together
 
 
 def parse():
@@ -54,8 +60,11 @@ def parse():
                          "convolutions sharded by target ownership + all-gather of the owned beliefs (rome_jl_amd.distributed.TargetShardedSweep)")
     ap.add_argument("--dry-run", action="store_true", help="no device, no process group: build every rank's tables / arena / exchange plan on "
                                                           "CPU tensors and check them against each other (what an N-GPU run relies on)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-modes", action="store_true", help="skip the extra per-solver throughput runs")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: per-solver runs, solve legs, CPU baseline, "
+                                                        "stored counter passes, extra timed blocks of short runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the extra per-solver throughput runs")
     ap.add_argument("--cpu-seconds", type=float, default=40.0)
     ap.add_argument("--settle-launches", type=int, default=4000,
                     help="untimed launches BEFORE the --warmup steps so that the device reaches its steady clocks whatever W is "
@@ -113,6 +122,19 @@ def separator_rows(pk, args, last):
     f_first = int(np.nonzero((vf == pk.index["x0"]) & (vt == pk.index["x1"]))[0][0])
     f_last = int(np.nonzero((vf == pk.index["x%d" % (args.poses - 2)]) & (vt == pk.index[last]))[0][0])
     return 2 * f_first + 1, 2 * f_last + 0      # odometry x0->x1, dir 1 -> target x0 ; odometry x_{P-2}->x_{P-1}, dir 0 -> target x_{P-1}
+
+
+def dump_output(path, name, a, budget):
+    """--dump-outputs: the array `a` (rows along axis 0) as path/name.npy in float64.  Above `budget` bytes: a fixed, seeded sample of
+    rows in ascending order, their indices in path/name_rows.npy (float64 as well)"""
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.nbytes > budget:
+        k = max(1, budget // (a[0].nbytes + 8))
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=min(k, a.shape[0]), replace=False))
+        np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(path, name + ".npy"), a)
 
 
 def dry_run(args):
@@ -407,24 +429,36 @@ def main():
         km = 1e3 * (t1 - t0) / args.steps if (multi or not with_events) else float(ev[0].elapsed_time(ev[len(marks)])) / args.steps
         return el, km
 
-    # short runs (the driver's --steps 20: a 0.17 ms region in which every host call between the two synchronizes counts --
+    # `value` and `ms_per_step` come from ONE block of exactly K = --steps steps between barrier + synchronize.  Short runs (K = 20
+    # is a 0.17 ms region in which every host call between the two synchronizes counts --
     # scripts/short_region_cost.py / profiles/r04_short_region_cost.txt: an event record is 4 us of host time and a barrier packet in the
-    # queue): the block of K steps is repeated and the MEDIAN block is reported (every block is exactly K steps between barrier +
-    # synchronize; all block times are listed).  The blocks behind `value` carry no event records; the launch period of the dominant
-    # kernel for the roofline comes from one more block of the same K steps WITH the two HIP events around it.
+    # queue) run two UNTIMED blocks of the same K steps first (the first blocks after the barrier are cold: 14.5 us per step against
+    # 9.5-11 measured; at K = 20 the second block still reads 0.5-3 us above the later ones), and their timed block carries no
+    # event records.  --full adds, for K < 1000, one block of the same K steps
+    # WITH the two HIP events around it (the launch period of the dominant kernel as a cross-check) and n_blocks - 1 more blocks of
+    # K steps for the spread of a short run (all block times are listed, the headline block first).
     n_blocks = 1 if args.steps >= 1000 else (5 if args.steps >= 100 else 9)
     if n_blocks > 1:
-        timed_block()   # one UNTIMED block first: the first block after the barrier is cold (14.5 us per step against 9.5-11 in round 3)
-        ev_block = timed_block(True)
-        blocks = [timed_block(False) for _ in range(n_blocks)]
-    else:
-        blocks = [timed_block(True)]
-        ev_block = blocks[0]
-    order = sorted(range(n_blocks), key=lambda i: blocks[i][0])
-    elapsed, _ = blocks[order[n_blocks // 2]]
-    # ONE period for `value` and for the roofline: the median block (N=1: a step IS one launch of the dominant kernel; the event-bracketed
-    # block is kept beside it as a cross-check -- round 4 quoted the roofline on that block alone, 7.8 us against a reproducible 8.6)
-    kern_ms_events = ev_block[1]
+        timed_block()
+        timed_block()
+    blocks = [timed_block(n_blocks == 1)]
+    elapsed = blocks[0][0]
+    kern_ms_events = blocks[0][1] if n_blocks == 1 else None
+    if args.dump_outputs:
+        # what the timed path hands its caller after the last step: the proposals of every (factor, direction) row (the per-rank
+        # segment table at N>1 weak scaling), the replicated belief store after a strong-scaled step
+        if strong:
+            if rank == 0:
+                dump_output(args.dump_outputs, "beliefs", pipe.store[:dg.bel[R.Pose2].shape[0]].cpu().numpy(), DUMP_BYTES_MAX)
+        else:
+            dump_output(args.dump_outputs, "proposals" if world == 1 else "proposals_rank%d" % rank,
+                        (pipe.prop if multi else prop).cpu().numpy(), DUMP_BYTES_MAX // world)
+    if args.full and n_blocks > 1:
+        kern_ms_events = timed_block(True)[1]
+        blocks += [timed_block(False) for _ in range(n_blocks - 1)]
+    # ONE period for `value` and for the roofline: the headline block (N=1: a step IS one launch of the dominant kernel; the
+    # event-bracketed block is kept beside it as a cross-check -- round 4 quoted the roofline on that block alone, 7.8 us against a
+    # reproducible 8.6)
     kern_ms = 1e3 * elapsed / args.steps
 
     data_kind = "synthetic" if (not args.g2o or args.g2o == "synthetic") else \
@@ -440,7 +474,10 @@ def main():
         "metric": "factor convolutions/sec (N=100) on Manhattan-3500; solveTree! wall-clock",
         "value": value, "unit": "convolutions/s", "n_gpus": (dist.get_world_size() if multi else 1), "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": 1e3 * elapsed / args.steps, "timed_blocks_ms_per_step": [1e3 * b[0] / args.steps for b in blocks],
-        "timed_block": "median of %d blocks of exactly %d steps, each between barrier + synchronize%s" % (n_blocks, args.steps, ", after one untimed block; kernel_ms_per_launch from one more such block bracketed by two HIP events" if n_blocks > 1 else ""), "higher_is_better": True, "scaling": "strong" if strong else "weak",
+        "timed_block": "one block of exactly %d steps between barrier + synchronize%s" % (args.steps, ", after two untimed blocks" if n_blocks > 1 else "") +
+                       ("; --full: kernel_ms_event_bracketed_block from one more such block bracketed by two HIP events, then %d more blocks "
+                        "(timed_blocks_ms_per_step, the headline block first)" % (n_blocks - 1) if args.full and n_blocks > 1 else ""),
+        "higher_is_better": True, "scaling": "strong" if strong else "weak",
         "vs_baseline": None, "dtype": "f64", "data": data_kind if not shared else
         data_kind + " [ROME_BENCH_SHARED_DEVICE=1: %d ranks on ONE device, host-staged exchange -- a flow test, NOT a measurement]" % world,
         "config": {"workload": workload, "poses_per_gpu": len(pk.labels[R.Pose2]), "pose2pose2_factors_per_gpu": tb["F"],
@@ -461,13 +498,13 @@ def main():
                      "bytes_per_particle": BYTES_PER_PARTICLE_P2P2[args.solver],
                      "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                      "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms_per_launch": kern_ms,
-                     "period": "ms_per_step of the median timed block (the period behind `value`)", "kernel_ms_event_bracketed_block": kern_ms_events,
+                     "period": "ms_per_step of the headline block (the period behind `value`)", "kernel_ms_event_bracketed_block": kern_ms_events,
                      "traffic": None},
     }
     # counter-measured HBM traffic of the same kernel on the same table (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes,
-    # scripts/profile_round.sh; PMC counters need rocprofv3 around the process, so this run quotes the stored pass)
+    # scripts/profile_round.sh; PMC counters need rocprofv3 around the process, so a --full run quotes the stored pass)
     tfile = os.path.join(ROOT, "profiles", "r06_hbm_traffic_%s.json" % args.solver)
-    if os.path.exists(tfile) and world == 1:
+    if args.full and os.path.exists(tfile) and world == 1:
         try:
             with open(tfile) as f:
                 tj = json.load(f)
@@ -483,7 +520,7 @@ def main():
             pass
 
     sfile = os.path.join(ROOT, "profiles", "r06_sq_counters_%s.json" % args.solver)
-    if os.path.exists(sfile) and world == 1:
+    if args.full and os.path.exists(sfile) and world == 1:
         try:
             with open(sfile) as f:
                 sj = json.load(f)
@@ -499,7 +536,7 @@ def main():
         except Exception:
             pass
 
-    if rank == 0 and world == 1 and not args.no_modes:
+    if args.full and rank == 0 and world == 1 and not args.no_modes:
         modes, by_solver = {}, {}
         for name, sv in (("closed_form", R.SOLVER_CLOSED_FORM), ("newton", R.SOLVER_NEWTON), ("gauss_newton", R.SOLVER_GAUSS_NEWTON),
                          ("nelder_mead", R.SOLVER_NELDER_MEAD)):
@@ -780,7 +817,7 @@ def main():
         except Exception as e:   # noqa: BLE001
             out["parametric_helix10k"] = {"error": repr(e)}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(R, pk, fg, N, args.cpu_seconds)
         # the other half of the metric next to a CPU number: one Bayes-tree pass (up + down, relative messages) on a bounded SAMPLE -- the
         # first 200 poses of the same g2o file with their loop closures -- by the oracle's restatement on the host (oracle/cpu_tree_bench.py,

@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 (timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -15) > $O/pytest.log
 (timeout 200 python __graft_entry__.py smoke 2>&1 | tail -3) > $O/smoke.log
-(timeout 400 python bench.py 2>&1 | tail -2) > $O/bench.log
+(timeout 600 python bench.py --full 2>&1 | tail -2) > $O/bench.log
 cd /tmp && export TMPDIR=/tmp
 for s in newton closed_form nelder_mead; do
   st=2000; wu=2000; [ $s = nelder_mead ] && st=20 && wu=10

@@ -321,7 +321,7 @@ def test_bench_under_torchrun_ranks_share_one_device(scaling, world):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "20", "--warmup", "5",
-           "--settle-launches", "50", "--scaling", scaling]
+           "--settle-launches", "50", "--scaling", scaling, "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1100, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

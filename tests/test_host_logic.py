@@ -417,6 +417,27 @@ def test_bench_dry_run_builds_and_checks_every_rank_of_an_8_gpu_run():
     assert sum(out["strong"]["rows_per_rank"]) == 10907 and out["frontier"]["cliques"] > 900
 
 
+def test_bench_dump_output_writes_float64_and_a_fixed_sample_above_the_budget(tmp_path):
+    """bench.py --dump-outputs: the whole array within the budget; above it a seeded sample of rows (ascending, indices beside them)
+    that fits the budget and is the same in every run"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    a = np.random.default_rng(5).standard_normal((1000, 3, 10)).astype(np.float32)
+    bench.dump_output(str(tmp_path / "whole"), "p", a, a.nbytes * 2)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["p.npy"]
+    w = np.load(tmp_path / "whole" / "p.npy")
+    assert w.dtype == np.float64 and np.array_equal(w, a.astype(np.float64))
+    budget = 60 * 1024
+    for run in ("s1", "s2"):
+        bench.dump_output(str(tmp_path / run), "p", a, budget)
+    s, rows = np.load(tmp_path / "s1" / "p.npy"), np.load(tmp_path / "s1" / "p_rows.npy")
+    assert s.dtype == np.float64 and rows.dtype == np.float64 and s.nbytes + rows.nbytes <= budget and len(s) == len(rows) > 100
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s, a[rows.astype(np.int64)].astype(np.float64))
+    assert np.array_equal(s, np.load(tmp_path / "s2" / "p.npy")) and np.array_equal(rows, np.load(tmp_path / "s2" / "p_rows.npy"))
+
+
 def test_init_rounds_multihypo_candidates_need_the_certain_variable_only():
     """two candidate landmarks reachable only through [x, l1, l2] multihypo sightings, no priors of their own, must not block
     each other (IIF initialises a fractional variable from the certain one)."""
