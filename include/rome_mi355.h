@@ -7,6 +7,8 @@
  *     PriorPose2                 src/factors/PriorPose2.jl:13-47
  *     Pose2Point2BearingRange    src/factors/BearingRange2D.jl:10-64
  *     Pose3Pose3                 src/factors/Pose3Pose3.jl:9-29      (+ PriorPose3, src/factors/Pose3D.jl:15-19)
+ *     Point2Point2Range          src/factors/Range2D.jl:8-17
+ *     Pose2Point2Range           src/factors/Range2D.jl:40-54        (partial = (1, 2) on the pose)
  * (paths relative to the RoME.jl v0.24.6 checkout).  Each entry point names the reference
  * interface it replaces.  Plain pointers and sizes only; no exceptions cross the ABI; the library
  * never retains caller pointers past a call.  There is NO CPU fallback: without a HIP device
@@ -163,6 +165,11 @@ int rome_residual_pose2point2br_pt(rome_ctx*, int32_t n, const double* z /*n*2*/
 int rome_residual_pose3pose3(rome_ctx*, int32_t n, const double* z /*n*6*/, const double* p /*n*6*/, const double* q /*n*6*/, double* r /*n*6*/);
 int rome_residual_pose3pose3_pt(rome_ctx*, int32_t n, const double* z /*n*6*/, const double* p_pt /*n*12*/, const double* q_pt /*n*12*/, double* r /*n*6*/);
 int rome_residual_priorpose3(rome_ctx*, int32_t n, const double* m /*n*6*/, const double* p /*n*6*/, double* r /*n*6*/);
+/* Range-only residuals r = ρ − ‖lm − x‖ (one row per particle):
+ *   rome_residual_point2point2range  (cf::CalcFactor{<:Point2Point2Range})(rho, xi, lm)  Range2D.jl:14-17
+ *   rome_residual_pose2point2range   (cf::CalcFactor{<:Pose2Point2Range})(rho, p, lm)    Range2D.jl:51-54  (p's heading is not read) */
+int rome_residual_point2point2range(rome_ctx*, int32_t n, const double* z /*n*/, const double* xi /*n*2*/, const double* lm /*n*2*/, double* r /*n*/);
+int rome_residual_pose2point2range(rome_ctx*, int32_t n, const double* z /*n*/, const double* p /*n*3*/, const double* lm /*n*2*/, double* r /*n*/);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched factor convolutions, HOST pointers: C independent convolutions x N particles.
@@ -208,6 +215,31 @@ int rome_conv_pose3pose3(rome_ctx*, const rome_opts*, int32_t C, const int32_t* 
                          const double* mu /*C*6*/, const double* cov /*C*36*/,
                          const double* fixed /*C*N*6*/, const double* noise /*C*N*6 or NULL*/,
                          double* target_inout /*C*N*6*/, int32_t* status);
+/* Range-only factors (src/factors/Range2D.jl; IIF approxConvBelief through the factor's residual functor, as above):
+ *   Point2Point2Range(Z) over [xi::Point2, lm::Point2], r = ρ − ‖lm − xi‖ (:14-17).  dir [C] or NULL (all 0):
+ *     0 solves lm from xi, 1 solves xi from lm.  fixed / target_inout: C blocks of Point2 (2).
+ *   Pose2Point2Range(Z) over [x::Pose2, lm::Point2], r = ρ − ‖lm − x.t‖ (:51-54), partial = (1, 2) (:44).  dir (scalar): 0 solves
+ *     lm (2) from the fixed poses (3); 1 solves the poses (3) from the fixed landmarks (2): only (x, y) move, every particle's
+ *     heading is returned bit for bit (neither the solve nor the entropy touches it).
+ *   mu [C], sigma [C]: ρ = μ + σξ, one standard normal ξ per particle (the particle's own Philox call, first Box-Muller output);
+ *   sigma < 0 encodes Uniform(μ − |σ|, μ + |σ|) through the normal CDF of ξ, as the bearing-range entries.  noise [C][N][1]:
+ *   standard normals, or (ROME_NOISE_MEASUREMENTS) caller-sampled ρ for any other SamplableBelief.
+ *   Every (factor, direction) has a ring of roots around the anchor a (the fixed point / the fixed pose's translation): every solver
+ *   runs inflate_cycles x {entropy, solve} from the start points (the spread over the WHOLE target variable, IIF's "no std yet -> 1";
+ *   on a Pose2 target the entropy is the compose form with a zero heading component).  CLOSED_FORM / NEWTON: the radial projection
+ *   t <- a + ρ (t − a)/‖t − a‖ (t == a leaves along +x; ρ <= 0 returns a, NEWTON status 1); NEWTON with status evaluates the functor
+ *   there.  GAUSS_NEWTON: that step iterated until |r| <= tol.  NELDER_MEAD: on r² over (x, y).
+ *   Partial-factor rule: IIF's source is not vendored; "spread over the whole variable, entropy and solve on the partial coordinates
+ *   only" is the reading this library pins.  nullhypo (opts->nullhypo) is honoured; multihypo is not supported (ROME_ERR_INVALID_ARG
+ *   from the _dev entries when alt_var / hypo_w is set).  N <= ROME_MAX_PARTICLES.                                                  */
+int rome_conv_point2point2range(rome_ctx*, const rome_opts*, int32_t C, const int32_t* dir /*[C] or NULL*/,
+                                const double* mu /*C*/, const double* sigma /*C*/,
+                                const double* fixed /*C*N*2*/, const double* noise /*C*N*1 or NULL*/,
+                                double* target_inout /*C*N*2*/, int32_t* status);
+int rome_conv_pose2point2range(rome_ctx*, const rome_opts*, int32_t C, int32_t dir,
+                               const double* mu /*C*/, const double* sigma /*C*/,
+                               const double* fixed, const double* noise /*C*N*1 or NULL*/,
+                               double* target_inout, int32_t* status);
 /* Prior "convolution" = N samples of the prior as points: IIF samplePoint on PriorPose2.Z / PriorPose3.Z
  * (src/factors/PriorPose2.jl:13-17, src/factors/Pose3D.jl:8-12).                                 */
 int rome_sample_priorpose2(rome_ctx*, const rome_opts*, int32_t C, const double* mu /*C*3*/, const double* cov /*C*9*/,
@@ -468,6 +500,10 @@ typedef struct rome_conv_dev {
 int rome_conv_pose2pose2_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 int rome_conv_pose2point2br_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 int rome_conv_pose3pose3_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
+/* range-only factors on device tables: L = [F][1] sigma (negative: Uniform, as above); no multihypo (alt_var / hypo_w -> INVALID_ARG).
+ * point2point2range: the row direction from rows4 / dir / dir_all; pose2point2range: dir_all (0 landmark, 1 pose), dir must be NULL */
+int rome_conv_point2point2range_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
+int rome_conv_pose2point2range_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 /* The whole convolution sweep of a Pose2 / Point2 graph (odometry + bearing-range sightings: MIT.g2o with landmarks, the beehive) in ONE
  * call: the Pose2Pose2 (+ PriorPose2 rows) table, the bearing-range -> pose table (dir_all = 1) and the bearing-range -> landmark table
  * (dir_all = 0); any of them may be NULL.  Philox stream of row r of family k = opts->stream_offset + family_stream_offset[k] + r

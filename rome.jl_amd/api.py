@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3,
-                      PriorPose3, getCoordinates)
+                      PriorPose3, Point2Point2Range, Pose2Point2Range, getCoordinates)
 
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
@@ -81,6 +81,18 @@ def residual_priorpose3(m, p, ctx=None):
     return _rows(_lib.load().rome_residual_priorpose3, ctx, (m, p), (6, 6), 6)
 
 
+def residual_point2point2range(z, xi, lm, ctx=None):
+    """r = ρ − ‖lm − xi‖ per row (Range2D.jl:14-17): z (n,) ranges, xi / lm (n, 2) -> (n,)"""
+    z = np.atleast_1d(_d(z)).reshape(-1, 1)
+    return _rows(_lib.load().rome_residual_point2point2range, ctx, (z, xi, lm), (1, 2, 2), 1)[:, 0]
+
+
+def residual_pose2point2range(z, p, lm, ctx=None):
+    """r = ρ − ‖lm − p.t‖ per row (Range2D.jl:51-54): z (n,), p (n, 3) pose coordinates (heading not read), lm (n, 2) -> (n,)"""
+    z = np.atleast_1d(_d(z)).reshape(-1, 1)
+    return _rows(_lib.load().rome_residual_pose2point2range, ctx, (z, p, lm), (1, 3, 2), 1)[:, 0]
+
+
 def _meas_coords(factor, meas):
     """Accepts the reference's tangent containers (hat form) or plain coordinates."""
     m = np.asarray(meas, dtype=np.float64).ravel()
@@ -94,6 +106,9 @@ def _meas_coords(factor, meas):
             return m
         if m.size == 5:  # ([0 -b; b 0], [ρ])
             return np.array([m[1], m[4]])
+    elif isinstance(factor, (Point2Point2Range, Pose2Point2Range)):
+        if m.size == 1:   # the range sample ρ
+            return m
     elif isinstance(factor, (Pose3Pose3, PriorPose3)):
         if m.size == 6:
             return m
@@ -118,6 +133,11 @@ def calcFactorResidualTemporary(factor, vartypes, meas, points, ctx=None):
         if pts[0].size == 6:
             return residual_pose2point2br_pt([z], [pts[0]], [pts[1]], ctx)[0]
         return residual_pose2point2br([z], [pts[0]], [pts[1]], ctx)[0]
+    if isinstance(factor, Point2Point2Range):
+        return residual_point2point2range(z, [pts[0]], [pts[1]], ctx)[0]
+    if isinstance(factor, Pose2Point2Range):
+        c = pts[0] if pts[0].size == 3 else getCoordinates(Pose2, pts[0])
+        return residual_pose2point2range(z, [c], [pts[1]], ctx)[0]
     if isinstance(factor, Pose3Pose3):
         if pts[0].size == 12:
             return residual_pose3pose3_pt([z], [pts[0]], [pts[1]], ctx)[0]
@@ -314,6 +334,53 @@ def conv_pose2point2br(opts, direction, mu, sigma, fixed, target, noise=None, wa
         alt = _blocks(alt, C_, N, 2, opts.layout); hypo_w = _d(hypo_w, (C_,))
         _lib.check(_lib.load().rome_conv_pose2point2br_mh(ctx.handle, C.byref(opts), C_, int(direction), _p(mu), _p(sigma),
                                                          _p(fixed), _p(alt), _p(hypo_w), _p(noise), _p(out), _pi(st)), ctx.handle)
+    return (out, st) if want_status else out
+
+
+def _with_layout(opts, layout):
+    if layout is None:
+        return opts
+    o = _lib.Opts.from_buffer_copy(opts)
+    o.layout = int(layout)
+    return o
+
+
+def conv_point2point2range(opts, mu, sigma, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None):
+    """C Point2Point2Range convolutions (Range2D.jl:8-17): mu / sigma (C,) range means and sigmas (sigma < 0: Uniform(mu ± |sigma|)),
+    dirs (C,) or None (0: solve lm from xi, 1: solve xi from lm), fixed / target C Point2 blocks, noise C blocks of one standard
+    normal per particle (or the range samples themselves under presampled=NOISE_MEASUREMENTS)."""
+    ctx = ctx or default_context()
+    opts = _with_layout(opts, layout)
+    mu = np.atleast_1d(_d(mu)).ravel(); C_ = mu.shape[0]; N = opts.n_particles
+    sigma = np.atleast_1d(_d(sigma)).ravel()
+    if sigma.shape != (C_,):
+        raise ValueError("sigma: expected %d values, got %s" % (C_, sigma.shape))
+    fixed = _blocks(fixed, C_, N, 2, opts.layout)
+    out = _blocks(target, C_, N, 2, opts.layout).copy()
+    noise = None if noise is None else _blocks(noise, C_, N, 1, opts.layout, points_ok=False)
+    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
+    dirs = None if dirs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dirs, dtype=np.int32), (C_,)))
+    _lib.check(_lib.load().rome_conv_point2point2range(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(sigma), _p(fixed),
+                                                      _p(noise), _p(out), _pi(st)), ctx.handle)
+    return (out, st) if want_status else out
+
+
+def conv_pose2point2range(opts, direction, mu, sigma, fixed, target, noise=None, want_status=False, ctx=None, layout=None):
+    """C Pose2Point2Range convolutions (Range2D.jl:40-54), one direction per call: 0 solves the landmarks from the fixed poses, 1 the
+    poses from the fixed landmarks -- (x, y) only, every particle's heading is returned unchanged."""
+    ctx = ctx or default_context()
+    opts = _with_layout(opts, layout)
+    mu = np.atleast_1d(_d(mu)).ravel(); C_ = mu.shape[0]; N = opts.n_particles
+    sigma = np.atleast_1d(_d(sigma)).ravel()
+    if sigma.shape != (C_,):
+        raise ValueError("sigma: expected %d values, got %s" % (C_, sigma.shape))
+    df, dt = (3, 2) if direction == 0 else (2, 3)
+    fixed = _blocks(fixed, C_, N, df, opts.layout)
+    out = _blocks(target, C_, N, dt, opts.layout).copy()
+    noise = None if noise is None else _blocks(noise, C_, N, 1, opts.layout, points_ok=False)
+    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
+    _lib.check(_lib.load().rome_conv_pose2point2range(ctx.handle, C.byref(opts), C_, int(direction), _p(mu), _p(sigma),
+                                                     _p(fixed), _p(noise), _p(out), _pi(st)), ctx.handle)
     return (out, st) if want_status else out
 
 

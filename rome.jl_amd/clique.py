@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, api
-from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2)
+from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2,
+                      refuse_range)
 
 FAMILY_STREAM = {"p2p2": 0, "br1": 1 << 28, "br0": 2 << 28, "p3p3": 5 << 28, "prpt2": 7 << 28}   # = DeviceGraph.STREAM_* / rome_clique_proposals
 
@@ -69,6 +70,7 @@ class CliqueBatch:
                table draws what the whole table draws (partition-independent results); default: the row's index."""
 
     def __init__(self, fg, pairs, var_index=None, stream_ids=None):
+        refuse_range([fg.getFactor(fl)[2] for fl, _ in pairs], "CliqueBatch")
         self.fg, self.N = fg, fg.N
         self.vars = {Pose2: [], Point2: [], Pose3: []}
         self.vidx = {}
@@ -303,6 +305,7 @@ class DeviceStore:
     TYPES = (Pose2, Point2, Pose3)
 
     def __init__(self, fg, ctx=None, wrap=None, upload=True):
+        refuse_range([f for _, _, f in fg.factors], "DeviceStore")
         self.ctx = ctx or api.default_context()
         self._lib = _lib.load()
         self.fg, self.N = fg, fg.N

@@ -162,7 +162,7 @@ void from_soa(const double* src, int C, int N, int d, int layout, double* dst) {
   }
 }
 
-enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2 };
+enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2, kP2R, kPPR };
 
 inline int point_len(int dim) { return dim == 3 ? 6 : (dim == 6 ? 12 : dim); }
 
@@ -284,6 +284,8 @@ int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const i
     case kPrior2: e = rome::launch_sample_priorpose2(a, s); break;
     case kPrior3: e = rome::launch_sample_priorpose3(a, s); break;
     case kPriorPt2: e = rome::launch_sample_priorpoint2(a, s); break;
+    case kP2R: e = rome::launch_conv_point2point2range(a, o->solver, s); break;
+    case kPPR: e = rome::launch_conv_pose2point2range(a, o->solver, s); break;
   }
   ROME_HIP(ctx, e);
   ROME_HIP(ctx, hipMemcpyAsync(h_out, d_out, sizeof(double) * blk_t, hipMemcpyDeviceToHost, s));
@@ -464,6 +466,16 @@ int rome_residual_priorpose3(rome_ctx* c, int32_t n, const double* m, const doub
   return host_rows(c, n, in, 2, r, 6, [&](const double* a, const double* b, const double*, double* o, hipStream_t s) {
     return rome::launch_residual_priorpose3(n, a, b, o, s); });
 }
+int rome_residual_point2point2range(rome_ctx* c, int32_t n, const double* z, const double* xi, const double* lm, double* r) {
+  RowBuf in[3] = {{z, 1}, {xi, 2}, {lm, 2}};
+  return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
+    return rome::launch_residual_range(n, a, b, 2, d, o, s); });
+}
+int rome_residual_pose2point2range(rome_ctx* c, int32_t n, const double* z, const double* p, const double* lm, double* r) {
+  RowBuf in[3] = {{z, 1}, {p, 3}, {lm, 2}};
+  return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
+    return rome::launch_residual_range(n, a, b, 3, d, o, s); });
+}
 
 /* ---- host-pointer convolutions ---- */
 int rome_conv_pose2pose2(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* cov,
@@ -512,6 +524,25 @@ int rome_conv_pose3pose3(rome_ctx* c, const rome_opts* o, int32_t C, const int32
   std::vector<double> L((size_t)C * 21);
   if ((rc = rome_cholesky_lower(6, C, cov, L.data()))) return rc;
   return host_conv(c, o, kP3P3, C, dir, 0, 6, 6, 6, mu, L.data(), 21, fixed, noise, target_inout, status);
+}
+int rome_conv_point2point2range(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* sigma,
+                                const double* fixed, const double* noise, double* target_inout, int32_t* status) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || C < 0 || (C > 0 && (!mu || !sigma || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
+  if (C == 0) return ROME_OK;
+  if (dir) for (int i = 0; i < C; ++i) if (dir[i] != 0 && dir[i] != 1) return ROME_ERR_INVALID_ARG;
+  for (int i = 0; i < C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;  /* sigma < 0 encodes Uniform(mu ± |sigma|) */
+  rome_opts oc = *o;
+  if (oc.layout == ROME_LAYOUT_AOS_POINTS) oc.layout = ROME_LAYOUT_AOS;   // a Point2 point IS its coordinates
+  return host_conv(c, &oc, kP2R, C, dir, 0, 1, 2, 2, mu, sigma, 1, fixed, noise, target_inout, status);
+}
+int rome_conv_pose2point2range(rome_ctx* c, const rome_opts* o, int32_t C, int32_t dir, const double* mu, const double* sigma,
+                               const double* fixed, const double* noise, double* target_inout, int32_t* status) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || C < 0 || (dir != 0 && dir != 1) || (C > 0 && (!mu || !sigma || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
+  if (C == 0) return ROME_OK;
+  for (int i = 0; i < C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;
+  return host_conv(c, o, kPPR, C, nullptr, dir, 1, dir == 0 ? 3 : 2, dir == 0 ? 2 : 3, mu, sigma, 1, fixed, noise, target_inout, status);
 }
 int rome_sample_priorpose2(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* cov, const double* noise, double* out) {
   int rc = check_opts(o); if (rc) return rc;
@@ -562,6 +593,22 @@ int rome_conv_pose2point2br_dev(rome_ctx* c, const rome_opts* o, const rome_conv
   if (t->dir != nullptr || (t->dir_all != 0 && t->dir_all != 1)) return ROME_ERR_INVALID_ARG;
   rome::ConvArgs a; args_from_dev(a, o, t);
   ROME_HIP(c, rome::launch_conv_bearingrange(a, o->solver, c->stream));
+  return ROME_OK;
+}
+int rome_conv_point2point2range_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
+  int rc = dev_common(c, o, t, true); if (rc) return rc;
+  if (t->alt_var || t->hypo_w) return ROME_ERR_INVALID_ARG;   // no multihypo on range factors
+  if (!t->dir && !t->rows4 && t->dir_all != 0 && t->dir_all != 1) return ROME_ERR_INVALID_ARG;
+  rome::ConvArgs a; args_from_dev(a, o, t);
+  ROME_HIP(c, rome::launch_conv_point2point2range(a, o->solver, c->stream));
+  return ROME_OK;
+}
+int rome_conv_pose2point2range_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
+  int rc = dev_common(c, o, t, true); if (rc) return rc;
+  if (t->alt_var || t->hypo_w) return ROME_ERR_INVALID_ARG;
+  if (t->dir != nullptr || (t->dir_all != 0 && t->dir_all != 1)) return ROME_ERR_INVALID_ARG;
+  rome::ConvArgs a; args_from_dev(a, o, t);
+  ROME_HIP(c, rome::launch_conv_pose2point2range(a, o->solver, c->stream));
   return ROME_OK;
 }
 int rome_sweep_pose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* p2p2, const rome_conv_dev* br1, const rome_conv_dev* br0,

@@ -232,6 +232,8 @@ __device__ __forceinline__ u32x4 noise_words(uint64_t seed, uint64_t stream, uin
 //        a field f enters box_muller as the word (f << 11) | 0x400, i.e. the centre of its bin: the radius is
 //        sqrt(-2 ln((f + 0.5) / 2^21)) <= 5.52, the angle has 19 bits below the two quadrant bits.  The draws differ from N(0,1)
 //        by < 2e-6 in Kolmogorov distance (tests/test_host_logic.py); a Pose2 convolution of N = 100 particles costs 50 Philox calls.
+//   D = 1 (range measurements):       the oracle's rule for any other d -- the particle's OWN call (counter = the particle id itself,
+//                                     not the even neighbour), words 0 / 1 -> one Box-Muller pair, its first output
 template <int D>
 __device__ __forceinline__ void normals3_fields(const u32x4& w, uint32_t (&r)[3], uint32_t (&a)[3]) {
   r[0] = (w.x & 0xFFFFF800u) | 0x400u; a[0] = (w.y & 0xFFFFF800u) | 0x400u;
@@ -242,8 +244,13 @@ __device__ __forceinline__ void normals3_fields(const u32x4& w, uint32_t (&r)[3]
 // the normals of particles p_even (even) and p_even + 1 together
 template <int D>
 __device__ __forceinline__ void rng_normals_pair(uint64_t seed, uint64_t stream, uint32_t p_even, double (&oe)[D], double (&oo)[D]) {
-  static_assert(D == 2 || D == 3 || D == 6, "measurement dimensions of the supported factors");
-  if constexpr (D == 3) {
+  static_assert(D == 1 || D == 2 || D == 3 || D == 6, "measurement dimensions of the supported factors");
+  if constexpr (D == 1) {
+    const u32x4 we = noise_words(seed, stream, p_even, 0u), wo = noise_words(seed, stream, p_even + 1u, 0u);
+    double unused;
+    box_muller(we.x, we.y, &oe[0], &unused);
+    box_muller(wo.x, wo.y, &oo[0], &unused);
+  } else if constexpr (D == 3) {
     const u32x4 w = noise_words(seed, stream, p_even, 0u);
     uint32_t r[3], a[3];
     normals3_fields<3>(w, r, a);
@@ -267,10 +274,14 @@ __device__ __forceinline__ void rng_normals_pair(uint64_t seed, uint64_t stream,
 // one particle on its own (prior sampling, one-particle-per-lane launches): only the calls / pairs it needs
 template <int D>
 __device__ __forceinline__ void rng_normals(uint64_t seed, uint64_t stream, uint32_t particle, double (&out)[D]) {
-  static_assert(D == 2 || D == 3 || D == 6, "measurement dimensions of the supported factors");
+  static_assert(D == 1 || D == 2 || D == 3 || D == 6, "measurement dimensions of the supported factors");
   const uint32_t pe = particle & ~1u;
   const bool odd = (particle & 1u) != 0u;
-  if constexpr (D == 3) {
+  if constexpr (D == 1) {
+    const u32x4 w = noise_words(seed, stream, particle, 0u);
+    double unused;
+    box_muller(w.x, w.y, &out[0], &unused);
+  } else if constexpr (D == 3) {
     const u32x4 w = noise_words(seed, stream, pe, 0u);
     uint32_t r[3], a[3];
     normals3_fields<3>(w, r, a);

@@ -437,6 +437,121 @@ struct BR {
   }
 };
 
+// ---- range-only factors (src/factors/Range2D.jl): Point2Point2Range over [xi::Point2, lm::Point2], r = ρ − ‖lm − xi‖ (:14-17);
+// Pose2Point2Range over [x::Pose2, lm::Point2], r = ρ − ‖lm − x.t‖ (:51-54), partial = (1, 2) on the pose (:44).
+// Every (factor, direction) has a RING of roots around the anchor a -- the fixed point, or the fixed pose's translation: the start
+// point selects the member, so every solver runs the inflation cycles {entropy, solve} as BR<1> does.  The solve moves the target's
+// translation t only; a Pose2 target's heading passes through unchanged (neither the solve nor the entropy touches it).
+//   CLOSED_FORM / NEWTON: the radial projection  t ← a + ρ (t − a)/‖t − a‖  (also the exact minimum-norm Gauss-Newton step);
+//                         t == a leaves along +x, ρ ≤ 0 returns a (the minimiser of (ρ − n)² over n ≥ 0 is n = 0).
+//   GAUSS_NEWTON:         that step iterated, the functor evaluated at every iterate until |r| ≤ tol.
+//   NELDER_MEAD:          nelder_mead<2> on r² over (x, y) (at fixed θ on a Pose2 target).
+// The measurement ρ = μ + σξ (σ < 0: Uniform(μ − |σ|, μ + |σ|) through the normal CDF of ξ, as BR::measurement); one standard normal
+// per particle from the particle's own Philox call (rng_normals<1>).
+struct RangeCost {
+  double rho, ax, ay;
+  __device__ __forceinline__ double operator()(const double (&x)[2]) const {
+    const double dx = x[0] - ax, dy = x[1] - ay;
+    const double r = rho - fast_sqrt(dx * dx + dy * dy);
+    return r * r;
+  }
+};
+// ‖t − a‖ and the radial projection of t onto the ring of radius ρ about a, from one v_rsq_f64 + two Newton steps (fast_rsqrt);
+// the two degenerate rows as selects: t == a (n2 == 0) leaves along +x, ρ ≤ 0 returns a.
+__device__ __forceinline__ double range_norm(double dx, double dy) {
+  const double n2 = dx * dx + dy * dy;
+  return n2 > 0.0 ? n2 * fast_rsqrt(n2) : 0.0;
+}
+__device__ __forceinline__ void range_project(double rho, double ax, double ay, double& tx, double& ty) {
+  const double dx = tx - ax, dy = ty - ay;
+  const double n2 = dx * dx + dy * dy;
+  const double y = fast_rsqrt(n2);
+  const bool ok = n2 > 0.0, pos = rho > 0.0;
+  const double k = pos ? (ok ? rho * y : rho) : 0.0;      // t = a + k e
+  const double ex = ok ? dx : 1.0, ey = ok ? dy : 0.0;   // (t == a: e = +x)
+  tx = __builtin_fma(k, ex, ax);
+  ty = __builtin_fma(k, ey, ay);
+}
+// DF / DT: dimensions of the fixed and the target variable (2 = Point2, 3 = Pose2 coordinates); the anchor is (fx[0], fx[1])
+template <int DF_, int DT_>
+struct RangeBase {
+  static constexpr int DF = DF_, DT = DT_, DZ = 1, NL = 1, NK = 2;
+  static constexpr int kHypoDir = -1;           // no multihypo (refused by the entry points); the direction column is read from rows4
+  static constexpr bool kUniqueRoot = false;    // a ring of roots: k_conv / k_conv_big only, every solver cycles
+  struct Consts { double mu, sg; };
+  __device__ static __forceinline__ Consts load(const ConvArgs& a, int f, int) { Consts K; K.mu = a.mu[f]; K.sg = a.L[f]; return K; }
+  __device__ static __forceinline__ void measurement(const Consts& K, const double (&xi)[1], double (&z)[1]) {
+    if (K.sg >= 0.0) z[0] = K.mu + K.sg * xi[0];
+    else z[0] = K.mu - K.sg * (erfc(-xi[0] * 0.70710678118654752440) - 1.0);
+  }
+  __device__ static __forceinline__ void canonical(double (&)[DT]) {}   // (a Pose2 target's heading is passed through bit for bit)
+  __device__ static __forceinline__ bool needs_cycles(int, const Consts&) { return true; }
+  struct Aux {};
+  __device__ static __forceinline__ Aux init_aux(const double (&)[DT]) { return Aux{}; }
+  __device__ static __forceinline__ void finalize(double (&)[DT], const Aux&) {}
+  struct Ref { double c[DT]; };
+  __device__ static __forceinline__ Ref make_ref(const double (&t0)[DT], const Aux&) {
+    Ref r;
+#pragma unroll
+    for (int k = 0; k < DT; ++k) r.c[k] = t0[k];
+    return r;
+  }
+  __device__ static __forceinline__ void tangent(const Ref& r, const double (&t)[DT], const Aux&, double (&d)[DT]) {
+    d[0] = t[0] - r.c[0]; d[1] = t[1] - r.c[1];
+    if constexpr (DT == 3) d[2] = wrap_pi(t[2] - r.c[2]);
+  }
+  // the spread over the WHOLE target variable (Pose2: heading included), entropy and solve on the partial coordinates only
+  template <int PPL>
+  __device__ static __forceinline__ double spread(const double (&t)[PPL][DT], const Aux (&)[PPL], const bool (&act)[PPL], double inv, double den) {
+    if constexpr (DT == 3) return spread_se2<PPL>(t, act, inv, den);
+    else return spread_r2<PPL>(t, act, inv, den);
+  }
+  // Point2: t += spread (u − ½); Pose2: the compose form with a zero heading component, t += R(θ) spread (u_x − ½, u_y − ½)
+  __device__ static __forceinline__ void add_entropy(double (&t)[DT], Aux&, double spread, const double (&u)[DT]) {
+    const double ex = spread * (u[0] - 0.5), ey = spread * (u[1] - 0.5);
+    if constexpr (DT == 3) {
+      double s, c; fast_sincos(t[2], &s, &c);
+      t[0] += c * ex - s * ey; t[1] += s * ex + c * ey;
+    } else { t[0] += ex; t[1] += ey; }
+  }
+  struct Prep {};
+  __device__ static __forceinline__ Prep prepare(const Consts&, const double (&)[1], const double (&)[DF]) { return Prep{}; }
+  // the residual functor r = ρ − ‖t − a‖ at the target point
+  __device__ static __forceinline__ double functor(const double (&z)[1], const double (&fx)[DF], const double (&t)[DT]) {
+    return z[0] - range_norm(t[0] - fx[0], t[1] - fx[1]);
+  }
+  // status of a returned point: |r| <= tol (ρ ≤ 0 returns the anchor, which is no root: status 1)
+  __device__ static __forceinline__ int verify(const Consts&, const double (&z)[1], const double (&fx)[DF], const double (&t)[DT], const Aux&, double tol) {
+    return (z[0] > 0.0 && fabs(functor(z, fx, t)) <= tol) ? 0 : 1;
+  }
+  template <int SOLVER>
+  __device__ static __forceinline__ int solve(const Consts&, const Prep&, const double (&z)[1], const double (&fx)[DF],
+                                              double (&t)[DT], Aux&, int max_iters, double tol) {
+    if constexpr (SOLVER == kSolverClosedForm || SOLVER == kSolverNewton) {
+      range_project(z[0], fx[0], fx[1], t[0], t[1]);
+      return 0;
+    } else if constexpr (SOLVER == kSolverGaussNewton) {
+      for (int it = 0; it < max_iters; ++it) {
+        if (fabs(functor(z, fx, t)) <= tol) return 0;
+        range_project(z[0], fx[0], fx[1], t[0], t[1]);
+      }
+      return 1;
+    } else {
+      RangeCost cost{z[0], fx[0], fx[1]};
+      double x[2] = {t[0], t[1]};
+      const int st = nelder_mead<2>(cost, x, max_iters, tol);
+      t[0] = x[0]; t[1] = x[1];
+      return st;
+    }
+  }
+};
+// Point2Point2Range: both directions in one table (dir from rows4.y / the dir column): r is symmetric in (xi, lm), so the direction
+// only decides which block is fixed and which is the target -- the per-particle work is the same
+struct P2R : RangeBase<2, 2> {};
+// Pose2Point2Range  DIR 0: pose fixed (anchor = its translation) -> landmark target;  DIR 1: landmark fixed -> pose target (x, y)
+template <int DIR>
+struct PPR : RangeBase<DIR == 0 ? 3 : 2, DIR == 0 ? 2 : 3> {};
+
 // ---- Pose3Pose3.  Belief blocks hold coordinates (t, ω); inside the kernel the rotation of every particle lives as a
 // unit quaternion (Aux) from load to store, so the inflation cycles never go through Exp/Log round trips, and the root
 // (a, qa) of the residual  r = ( p.t + R_p z_t − q.t , Log(R_qᵀ R_p Exp(z_ω)) )  is prepared once per particle:
@@ -772,6 +887,12 @@ __device__ __forceinline__ int mirror_slot(const ConvArgs& a, int c_raw) {
 }
 
 template <class FP, int SOLVER, int PPL, bool LEAN> __device__ __forceinline__ void conv_wave_body(const ConvArgs& a, int blk);
+// minimum waves / SIMD asked of the Nelder-Mead instantiations of k_conv (the 2-D / 3-D factors: see below).  The range factors'
+// ring solve keeps its simplex in registers without that cap (capped at 128 VGPRs their PPL 4 / 8 kernels would spill)
+template <class FP> struct NmMinWaves { static constexpr int value = ROME_NM_MINWAVES; };
+template <> struct NmMinWaves<P2R> { static constexpr int value = ROME_MIN_WAVES; };
+template <> struct NmMinWaves<PPR<0>> { static constexpr int value = ROME_MIN_WAVES; };
+template <> struct NmMinWaves<PPR<1>> { static constexpr int value = ROME_MIN_WAVES; };
 
 // LEAN: the plain sweep -- in-kernel noise, all four table columns present, no multihypo / nullhypo rows.  The same code with
 // those features compiled out: the table row is one 16-byte scalar load, nothing stands between the belief loads and the
@@ -779,7 +900,7 @@ template <class FP, int SOLVER, int PPL, bool LEAN> __device__ __forceinline__ v
 template <class FP, int SOLVER, int PPL, bool LEAN>
 // Nelder-Mead on the 2-D/3-D factors is latency-bound (long dependent select/compare chains): asking for 4 waves/SIMD
 // (<= 128 VGPRs) is 5 % faster there; (the SE(3) kernels need their 256 VGPRs: capped at 3-4 waves/SIMD they spill and run 2.7x slower)
-__global__ void __launch_bounds__(64 * ROME_WPB, (SOLVER == kSolverNelderMead && FP::DT <= 3) ? ROME_NM_MINWAVES : ((SOLVER != kSolverNelderMead && FP::DT == 6) ? ROME_P3_MINBLK : ROME_MIN_WAVES))
+__global__ void __launch_bounds__(64 * ROME_WPB, (SOLVER == kSolverNelderMead && FP::DT <= 3) ? NmMinWaves<FP>::value : ((SOLVER != kSolverNelderMead && FP::DT == 6) ? ROME_P3_MINBLK : ROME_MIN_WAVES))
 k_conv(const ConvArgs a) {
   conv_wave_body<FP, SOLVER, PPL, LEAN>(a, xcd_contiguous_block(blockIdx.x, gridDim.x));
 }
@@ -1498,6 +1619,13 @@ __global__ void k_coords_to_points(int n, int dim, const double* __restrict__ c,
   }
 }
 
+// range residuals r = ρ − ‖lm − x‖: x rows are Point2 (dx = 2) or Pose2 coordinates (dx = 3, the heading is not read)
+__global__ void k_residual_range(int n, const double* z, const double* x, int dx, const double* l, double* r) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  r[i] = z[i] - range_norm(l[2 * i] - x[(size_t)dx * i], l[2 * i + 1] - x[(size_t)dx * i + 1]);
+}
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
@@ -1587,6 +1715,11 @@ hipError_t launch_conv_pose2pose2(const ConvArgs& a, int solver, hipStream_t s) 
 hipError_t launch_conv_pose3pose3(const ConvArgs& a, int solver, hipStream_t s) { return launch_solver<P3P3>(a, solver, s); }
 hipError_t launch_conv_bearingrange(const ConvArgs& a, int solver, hipStream_t s) {
   return a.dir_all == 0 ? launch_solver<BR<0>>(a, solver, s) : launch_solver<BR<1>>(a, solver, s);
+}
+// range factors: a ring of roots (kUniqueRoot = false) -> k_conv (N <= 512) / k_conv_big (N <= 4096) only
+hipError_t launch_conv_point2point2range(const ConvArgs& a, int solver, hipStream_t s) { return launch_solver<P2R>(a, solver, s); }
+hipError_t launch_conv_pose2point2range(const ConvArgs& a, int solver, hipStream_t s) {
+  return a.dir_all == 0 ? launch_solver<PPR<0>>(a, solver, s) : launch_solver<PPR<1>>(a, solver, s);
 }
 static bool plain_rows(const ConvArgs& a) { return a.rows4 && !a.noise && !a.alt_var && !a.nullhypo && !a.status && !a.row_stream && !a.meas_block; }
 static bool hypo_rows(const ConvArgs& a) { return a.rows4 && !a.noise && !a.status && !a.row_stream && !a.meas_block && (a.alt_var || a.nullhypo); }
@@ -1792,6 +1925,10 @@ hipError_t launch_residual_pose3pose3(int n, const double* z, const double* p, c
 }
 hipError_t launch_residual_priorpose3(int n, const double* m, const double* p, double* r, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_residual_priorpose3, rows_grid(n), dim3(256), 0, s, n, m, p, r);
+  return hipGetLastError();
+}
+hipError_t launch_residual_range(int n, const double* z, const double* x, int dx, const double* l, double* r, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_residual_range, rows_grid(n), dim3(256), 0, s, n, z, x, dx, l, r);
   return hipGetLastError();
 }
 

@@ -108,6 +108,22 @@ class DeviceGraph:
         for name, tab, d in (("prior2", pk.prior2, 3), ("prior3", pk.prior3, 6), ("priorpt2", pk.priorpt2, 2)):
             if tab["F"]:
                 self.tab[name] = dict(F=tab["F"], mu=t(tab["mu"], f64), L=t(cholesky_lower(tab["cov"]), f64), var=t(tab["var"], i32))
+        # range-only factors (Range2D.jl): their own tables, launched after every other family; L = the [F][1] sigmas
+        r2 = getattr(pk, "p2rng", None)
+        if r2 is not None and r2["F"]:
+            factor, dr, fixed, target = PackedGraph.range_conv_table(r2)
+            nh = np.repeat(r2["nh"], 2)
+            self.tab["p2rng"] = dict(F=r2["F"], C=2 * r2["F"], mu=t(r2["mu"], f64), L=t(r2["sigma"], f64),
+                                     nh=t(nh, f64) if np.any(nh > 0) else None, target_h=target,
+                                     rows4=t(np.stack([factor, dr, fixed, target], axis=1), i32))
+        rp = getattr(pk, "pprng", None)
+        if rp is not None and rp["F"]:
+            F = rp["F"]
+            fac = np.arange(F, dtype=np.int32)
+            self.tab["pprng"] = dict(F=F, mu=t(rp["mu"], f64), L=t(rp["sigma"], f64),
+                                     nh=t(rp["nh"], f64) if np.any(rp["nh"] > 0) else None,
+                                     rows4_0=t(np.stack([fac, np.zeros(F, np.int32), rp["pose"], rp["point"]], axis=1), i32),
+                                     rows4_1=t(np.stack([fac, np.ones(F, np.int32), rp["point"], rp["pose"]], axis=1), i32))
 
         self._build_solve_tables(t, i32)
 
@@ -120,18 +136,25 @@ class DeviceGraph:
         Fb0 = self.tab["br"]["F0"] if "br" in self.tab else 0
         C3 = self.tab["p3p3"]["C"] if "p3p3" in self.tab else 0
         Ppt = self.tab["priorpt2"]["F"] if "priorpt2" in self.tab else 0   # landmark priors: one proposal row each, behind the sightings
-        self.n_prop = {Pose2: C2 + Fb, Point2: Fb0 + Ppt, Pose3: C3}
+        # range factors behind everything else -- Point2: [br0 | priorpt2 | p2rng (2F, rows 2f+dir) | pprng dir 0], Pose2: [p2p2 | br1 | pprng dir 1]
+        Cr = self.tab["p2rng"]["C"] if "p2rng" in self.tab else 0
+        Fq = self.tab["pprng"]["F"] if "pprng" in self.tab else 0
+        self.n_prop = {Pose2: C2 + Fb + Fq, Point2: Fb0 + Ppt + Cr + Fq, Pose3: C3}
         self.prop_bw = {}
-        self.prop = {Pose2: torch.zeros((max(C2 + Fb, 1), 3, self.N), dtype=f64, device=self.device),
-                     Point2: torch.zeros((max(Fb0 + Ppt, 1), 2, self.N), dtype=f64, device=self.device),
+        self.prop = {Pose2: torch.zeros((max(C2 + Fb + Fq, 1), 3, self.N), dtype=f64, device=self.device),
+                     Point2: torch.zeros((max(Fb0 + Ppt + Cr + Fq, 1), 2, self.N), dtype=f64, device=self.device),
                      Pose3: torch.zeros((max(C3, 1), 6, self.N), dtype=f64, device=self.device)}
         self.bel_next = {vt: torch.zeros_like(self.bel[vt]) for vt in (Pose2, Point2, Pose3)}
         tgt2 = [self.tab["p2p2"]["target"].cpu().numpy()] if C2 else []
         if Fb:
             tgt2.append(pk.br["pose"])
+        if Fq:
+            tgt2.append(pk.pprng["pose"])
         self._prop_targets = {Pose2: np.concatenate(tgt2) if tgt2 else np.zeros(0, np.int32),
                               Point2: np.concatenate([pk.br["rows0"]["point"] if Fb else np.zeros(0, np.int32),
-                                                      pk.priorpt2["var"] if Ppt else np.zeros(0, np.int32)]),
+                                                      pk.priorpt2["var"] if Ppt else np.zeros(0, np.int32),
+                                                      self.tab["p2rng"]["target_h"] if Cr else np.zeros(0, np.int32),
+                                                      pk.pprng["point"] if Fq else np.zeros(0, np.int32)]).astype(np.int32),
                               Pose3: self.tab["p3p3"]["target"].cpu().numpy() if C3 else np.zeros(0, np.int32)}
         self.frozen = set()
         self._build_csr()
@@ -272,6 +295,11 @@ class DeviceGraph:
     # ---- solve loop pieces ----
     STREAM_P2P2, STREAM_BR1, STREAM_BR0, STREAM_PROD2, STREAM_PRODL, STREAM_P3P3, STREAM_PROD3, STREAM_PRIORPT2 = \
         0, 1 << 28, 2 << 28, 3 << 28, 4 << 28, 5 << 28, 6 << 28, 7 << 28
+    STREAM_P2RNG, STREAM_PPRNG1, STREAM_PPRNG0 = 8 << 28, 9 << 28, 10 << 28   # range factors (Point2Point2Range, Pose2Point2Range dir 1 / 0)
+
+    def has_range(self):
+        """does the graph hold range-only factors (served by conv_step / solve only: not by the multi-rank drivers)"""
+        return "p2rng" in self.tab or "pprng" in self.tab
 
     def _opts_at(self, opts, offset):
         o = _lib.Opts.from_buffer_copy(opts)
@@ -301,6 +329,17 @@ class DeviceGraph:
                          mu=tp["mu"], L=tp["L"], out=self.prop[Point2][Fb0:Fb0 + tp["F"]])
         if "p3p3" in self.tab and self.tab["p3p3"]["C"]:
             self.sweep_pose3pose3(self._opts_at(opts, base + self.STREAM_P3P3), out=self.prop[Pose3][:self.tab["p3p3"]["C"]])
+        if self.has_range():   # range-only factors: after every other family, their proposal rows behind the other rows
+            C2 = self.tab["p2p2"]["C"] if "p2p2" in self.tab else 0
+            Fb = self.tab["br"]["F"] if "br" in self.tab else 0
+            pt0 = (self.tab["br"]["F0"] if "br" in self.tab else 0) + (self.tab["priorpt2"]["F"] if "priorpt2" in self.tab else 0)
+            Cr = self.tab["p2rng"]["C"] if "p2rng" in self.tab else 0
+            if Cr:
+                self.sweep_point2point2range(self._opts_at(opts, base + self.STREAM_P2RNG), out=self.prop[Point2][pt0:pt0 + Cr])
+            if "pprng" in self.tab:
+                Fq = self.tab["pprng"]["F"]
+                self.sweep_pose2point2range(self._opts_at(opts, base + self.STREAM_PPRNG1), 1, out=self.prop[Pose2][C2 + Fb:C2 + Fb + Fq])
+                self.sweep_pose2point2range(self._opts_at(opts, base + self.STREAM_PPRNG0), 0, out=self.prop[Point2][pt0 + Cr:pt0 + Cr + Fq])
 
     def product_step(self, opts, sweep=0, bandwidth="silverman", product="importance", gibbs_iters=1):
         """bel <- product of the proposals targeting each variable (Jacobi update: computed into bel_next, copied back in place
@@ -501,6 +540,28 @@ class DeviceGraph:
                 kw.update(nullhypo=tb["nh"])
         self._launch(self._lib.rome_conv_pose2point2br_dev, opts, n_conv=nrow, dir_all=int(direction), dir=None,
                      mu=tb["mu"], L=tb["sigma"], noise=noise, out=out, status=status, **kw)
+        return out
+
+    def sweep_point2point2range(self, opts, out=None, noise=None, status=None):
+        """Every Point2Point2Range factor in both directions (row 2f + dir: 0 solves lm from xi, 1 xi from lm) -> [2F, 2, N], one launch."""
+        tb = self.tab["p2rng"]
+        if out is None:
+            out = self.torch.empty((tb["C"], 2, self.N), dtype=self.torch.float64, device=self.device)
+        self._launch(self._lib.rome_conv_point2point2range_dev, opts, n_conv=tb["C"], dir_all=0, rows4=tb["rows4"], mu=tb["mu"], L=tb["L"],
+                     bel_fixed=self.bel[Point2], bel_target=self.bel[Point2], noise=noise, out=out, status=status,
+                     **({"nullhypo": tb["nh"]} if tb["nh"] is not None else {}))
+        return out
+
+    def sweep_pose2point2range(self, opts, direction, out=None, noise=None, status=None):
+        """direction 0: poses -> landmark proposals [F, 2, N]; 1: landmarks -> pose proposals [F, 3, N] ((x, y) only, headings kept)."""
+        tb = self.tab["pprng"]
+        dt = 2 if direction == 0 else 3
+        if out is None:
+            out = self.torch.empty((tb["F"], dt, self.N), dtype=self.torch.float64, device=self.device)
+        bf, bt = (self.bel[Pose2], self.bel[Point2]) if direction == 0 else (self.bel[Point2], self.bel[Pose2])
+        self._launch(self._lib.rome_conv_pose2point2range_dev, opts, n_conv=tb["F"], dir_all=int(direction),
+                     rows4=tb["rows4_0"] if direction == 0 else tb["rows4_1"], mu=tb["mu"], L=tb["L"], bel_fixed=bf, bel_target=bt,
+                     noise=noise, out=out, status=status, **({"nullhypo": tb["nh"]} if tb["nh"] is not None else {}))
         return out
 
     def _conv_dev(self, keep, **kw):

@@ -14,6 +14,13 @@ read separator beliefs that are one sweep old -- the same asynchrony IIF's cliqu
 import numpy as np
 
 
+def _refuse_range_tables(dg, where):
+    """the multi-rank drivers plan the DeviceGraph.families() tables only: a graph with range-only factors is refused"""
+    if getattr(dg, "has_range", None) is not None and dg.has_range():
+        names = [n for n, k in (("Point2Point2Range", "p2rng"), ("Pose2Point2Range", "pprng")) if k in dg.tab]
+        raise TypeError("%s: %s factors are not supported by the multi-rank drivers" % (where, " / ".join(names)))
+
+
 def shard_range(n_items, world, rank):
     """Contiguous balanced partition of range(n_items): -> (lo, hi) of `rank`."""
     q, r = divmod(int(n_items), int(world))
@@ -114,6 +121,7 @@ class SeparatorPipeline:
     """
 
     def __init__(self, dg, opts, dist, world, rank, publish, ghosts, always_collective=False, depth=2, rccl_comms=None):
+        _refuse_range_tables(dg, type(self).__name__)
         torch = dg.torch
         self.dg, self.dist, self.world, self.rank = dg, dist, world, rank
         self.collective = world > 1 or always_collective
@@ -310,6 +318,7 @@ class TargetShardedSweep:
     (V/world x dim x N doubles per rank; Manhattan: 8.4 MB in total) restores the replicated store."""
 
     def __init__(self, dg, opts, dist, world, rank, family="p2p2", always_collective=False, rccl_comm=None):
+        _refuse_range_tables(dg, type(self).__name__)
         torch = dg.torch
         self.dg, self.dist, self.world, self.rank = dg, dist, world, rank
         self.collective = world > 1 or always_collective

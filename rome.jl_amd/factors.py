@@ -6,6 +6,7 @@ Same names and argument meaning as the reference (paths relative to the RoME.jl 
   PriorPose2(Z)                                              src/factors/PriorPose2.jl:13-15
   Pose2Point2BearingRange(bearing, range)                    src/factors/BearingRange2D.jl:10-13
   Pose3Pose3(Z), PriorPose3(Z)                               src/factors/Pose3Pose3.jl:9-11, Pose3D.jl:8-10
+  Point2Point2Range(Z), Pose2Point2Range(Z)                 src/factors/Range2D.jl:8-17, 40-54
   getMeasurementParametric(::Pose2Point2BearingRange)        src/factors/BearingRange2D.jl:30-37
   Packed* <-> factor converters                              src/factors/Pose2D.jl:76-84 etc.
 These objects only hold the measurement model; all arithmetic is done by the HIP library.
@@ -165,6 +166,41 @@ class Point2Point2(_RelativeFactor):
             raise ValueError("Point2Point2 needs a 2-dimensional belief")
 
 
+class Point2Point2Range(_RelativeFactor):
+    """Range between two `Point2` variables (src/factors/Range2D.jl:8-17): r = ρ − ‖lm − xi‖ over [xi, lm].  Z is a `Normal` or a
+    `Uniform` belief of the range.  One range constrains the other point to a ring: the convolution keeps the start point's member of
+    it (every solver runs the inflation cycles)."""
+    variable_types = (Point2, Point2)
+
+    def __init__(self, Z):
+        if not isinstance(Z, (Normal, Uniform)):
+            raise TypeError("Point2Point2Range: this build supports a Normal / Uniform range belief, got %s" % type(Z).__name__)
+        self.Z = Z
+
+
+class Pose2Point2Range(_RelativeFactor):
+    """Range from a `Pose2` to a `Point2` (src/factors/Range2D.jl:40-54): r = ρ − ‖lm − x.t‖ over [x, lm], partial = (1, 2) on the
+    pose (:44).  Solving the pose moves its (x, y) only; every particle's heading passes through unchanged."""
+    variable_types = (Pose2, Point2)
+    partial = (1, 2)
+
+    def __init__(self, Z):
+        if not isinstance(Z, (Normal, Uniform)):
+            raise TypeError("Pose2Point2Range: this build supports a Normal / Uniform range belief, got %s" % type(Z).__name__)
+        self.Z = Z
+
+
+RANGE_FACTORS = (Point2Point2Range, Pose2Point2Range)
+
+
+def refuse_range(factors, where):
+    """TypeError naming the first range-only factor in `factors` (paths that do not serve them yet)."""
+    for f in factors:
+        if isinstance(f, RANGE_FACTORS):
+            raise TypeError("%s: %s factors are not supported here (solveGraph / approxConv serve range factors)"
+                            % (where, type(f).__name__))
+
+
 def getMeasurementParametric(f):
     """(μ, iΣ) as IIF.getMeasurementParametric; BearingRange override at BearingRange2D.jl:30-37."""
     if isinstance(f, Pose2Point2BearingRange):
@@ -204,7 +240,7 @@ def unpack_factor(d):
     if t == "Pose2Point2BearingRange":
         return Pose2Point2BearingRange(_unpack_belief(d["bearstr"]), _unpack_belief(d["rangstr"]))
     cls = {"Pose2Pose2": Pose2Pose2, "PriorPose2": PriorPose2, "Pose3Pose3": Pose3Pose3, "PriorPose3": PriorPose3,
-           "PriorPoint2": PriorPoint2}[t]
+           "PriorPoint2": PriorPoint2, "Point2Point2Range": Point2Point2Range, "Pose2Point2Range": Pose2Point2Range}[t]
     return cls(_unpack_belief(d["Z"]))
 
 

@@ -13,7 +13,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .factors import (MvNormal, Normal, Uniform, Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange,
-                      Pose3Pose3, PriorPose3, PriorPoint2)
+                      Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range)
 
 
 @_contextlib.contextmanager
@@ -452,7 +452,7 @@ class PackedGraph:
         for l, t in fg.variables.items():
             self.index[l] = len(self.labels[t])
             self.labels[t].append(l)
-        p2, br, p3, pr2, pr3, prpt = [], [], [], [], [], []
+        p2, br, p3, pr2, pr3, prpt, p2r, ppr = [], [], [], [], [], [], [], []
         nullh = getattr(fg, "nullhypo", {})
         for flabel, labels, f in fg.factors:
             ids = [self.index[l] for l in labels]
@@ -462,6 +462,8 @@ class PackedGraph:
             elif isinstance(f, PriorPose2): pr2.append((ids, f, flabel))
             elif isinstance(f, PriorPose3): pr3.append((ids, f, flabel))
             elif isinstance(f, PriorPoint2): prpt.append((ids, f, flabel))
+            elif isinstance(f, Point2Point2Range): p2r.append((ids, f, flabel))
+            elif isinstance(f, Pose2Point2Range): ppr.append((ids, f, flabel))
             else: raise TypeError("factor type %s is outside the hot path" % type(f).__name__)
 
         def rel_tables(items, d):
@@ -507,6 +509,19 @@ class PackedGraph:
         self.prior3 = prior_tables(pr3, 6)
         self.priorpt2 = prior_tables(prpt, 2)   # landmark priors: parametric rows AND one proposal row each in the solve loop
 
+        # range-only factors (Range2D.jl): one range belief per factor (mu, sigma < 0: Uniform), nullhypo per factor
+        def range_tables(items, a, b):
+            F = len(items)
+            return {"F": F, "mu": np.array([f.Z.mu for _, f, _ in items], dtype=np.float64).reshape(F),
+                    "sigma": np.array([f.Z.sigma for _, f, _ in items], dtype=np.float64).reshape(F),
+                    a: np.array([ids[0] for ids, _, _ in items], dtype=np.int32).reshape(F),
+                    b: np.array([ids[1] for ids, _, _ in items], dtype=np.int32).reshape(F),
+                    "nh": np.array([nullh.get(fl, 0.0) for _, _, fl in items], dtype=np.float64).reshape(F),
+                    "labels": [it[2] for it in items]}
+
+        self.p2rng = range_tables(p2r, "from", "to")      # Point2Point2Range over [xi, lm]
+        self.pprng = range_tables(ppr, "pose", "point")   # Pose2Point2Range over [x, lm]
+
     @classmethod
     def from_pose2_tables(cls, N, n_poses, mu, cov, var_from, var_to, prior_mu=None, prior_cov=None, prior_var=None):
         """Packed graph of a Pose2 / Pose2Pose2 / PriorPose2 problem straight from arrays (no per-factor Python
@@ -529,6 +544,8 @@ class PackedGraph:
                            var=np.asarray(prior_var if P else np.zeros(0), dtype=np.int32), labels=[])
         self.prior3 = dict(F=0, mu=np.zeros((0, 6)), cov=np.zeros((0, 6, 6)), var=np.zeros(0, np.int32), labels=[])
         self.priorpt2 = dict(F=0, mu=np.zeros((0, 2)), cov=np.zeros((0, 2, 2)), var=np.zeros(0, np.int32), labels=[])
+        self.p2rng = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "from": z32, "to": z32, "nh": np.zeros(0), "labels": []}
+        self.pprng = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "pose": z32, "point": z32, "nh": np.zeros(0), "labels": []}
         return self
 
     @staticmethod
@@ -556,6 +573,15 @@ class PackedGraph:
         extra = dict(factor=mh, dir=np.zeros(mh.size, np.int32), fixed=tab["var_from"][mh], target=tab["alt"][mh],
                      alt=tab["var_to"][mh], w=tab["w2"][mh].astype(np.float64))
         return alt, w, extra
+
+    @staticmethod
+    def range_conv_table(tab):
+        """Point2Point2Range rows, both directions interleaved as conv_table: row 2f = (f, dir 0: fixed = xi, target = lm),
+        row 2f+1 = (f, dir 1: fixed = lm, target = xi)."""
+        return PackedGraph.conv_table({"F": tab["F"], "var_from": tab["from"], "var_to": tab["to"]})
+
+    def has_range(self):
+        return bool(getattr(self, "p2rng", {"F": 0})["F"] or getattr(self, "pprng", {"F": 0})["F"])
 
     def beliefs(self, fg, vartype):
         """(V, dim, N) SoA blocks from fg.vals (all variables of the type must be initialised)."""

@@ -125,6 +125,52 @@ function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:
   return manikde!(getManifold(getVariableType(dfg, target)), pts)
 end
 
+# ---- range-only factors (src/factors/Range2D.jl): Point2Point2Range over [xi, lm], Pose2Point2Range over [x, lm] (partial on the
+# pose: solving it moves (x, y) only, the headings come back unchanged) ----------------------------------------------------------------
+function conv_point2point2range(fg, f::Point2Point2Range{<:Normal}, fixedpts, u0pts, dir::Integer; solver=1)
+  o = default_opts(fg; solver)
+  μ = Float64[mean(f.Z)]; σ = Float64[std(f.Z)]
+  fixed = coords(Point2, fixedpts); target = coords(Point2, u0pts)
+  d = Int32[dir]
+  GC.@preserve μ σ fixed target d begin
+    check(ccall((:rome_conv_point2point2range, LIB), Cint,
+      (Ptr{Cvoid}, Ref{RomeOpts}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+      ctx().h, o, 1, d, μ, σ, fixed, C_NULL, target, C_NULL))
+  end
+  points(Point2, target)
+end
+
+function conv_pose2point2range(fg, f::Pose2Point2Range{<:Normal}, fixedpts, u0pts, dir::Integer; solver=1)
+  o = default_opts(fg; solver)
+  μ = Float64[mean(f.Z)]; σ = Float64[std(f.Z)]
+  Tf, Tt = dir == 0 ? (Pose2, Point2) : (Point2, Pose2)
+  fixed = coords(Tf, fixedpts); target = coords(Tt, u0pts)
+  GC.@preserve μ σ fixed target begin
+    check(ccall((:rome_conv_pose2point2range, LIB), Cint,
+      (Ptr{Cvoid}, Ref{RomeOpts}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+      ctx().h, o, 1, dir, μ, σ, fixed, C_NULL, target, C_NULL))
+  end
+  points(Tt, target)
+end
+
+function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:Point2Point2Range{<:Normal}}}, target::Symbol,
+                          measurement::AbstractVector=Tuple[]; solveKey::Symbol=:default, kw...)
+  vars = getVariableOrder(fc)
+  dir = vars[2] == target ? 0 : 1
+  other = dir == 0 ? vars[1] : vars[2]
+  pts = conv_point2point2range(dfg, getFactorType(fc), getVal(dfg, other; solveKey), getVal(dfg, target; solveKey), dir)
+  return manikde!(getManifold(Point2), pts)
+end
+
+function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:Pose2Point2Range{<:Normal}}}, target::Symbol,
+                          measurement::AbstractVector=Tuple[]; solveKey::Symbol=:default, kw...)
+  vars = getVariableOrder(fc)
+  dir = vars[2] == target ? 0 : 1
+  other = dir == 0 ? vars[1] : vars[2]
+  pts = conv_pose2point2range(dfg, getFactorType(fc), getVal(dfg, other; solveKey), getVal(dfg, target; solveKey), dir)
+  return manikde!(getManifold(getVariableType(dfg, target)), pts)
+end
+
 # ---- Pose3Pose3: coordinates (t, ω) = get_coordinates(M, ϵ, log(M, ϵ, p), DefaultOrthogonalBasis()) ----------
 const M3 = getManifold(Pose3)
 coords(::Type{Pose3}, pts) = reduce(hcat, [get_coordinates(M3, getPointIdentity(M3), log(M3, getPointIdentity(M3), p), DefaultOrthogonalBasis()) for p in pts])

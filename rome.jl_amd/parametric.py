@@ -365,6 +365,8 @@ def solveGraphParametric(fg, init=None, max_iters=100, tol=1e-4, ctx=None, retur
     The host arithmetic of the whole solve runs with the BLAS pools limited to one thread: every BLAS call
     of this loop is small -- SuperLU supernodes, 12 x 12 block products -- and the worker threads of a 64-thread OpenBLAS pool on a
     16-CPU quota spin after each of them while the sequential parts of the factorisation want the cores: 10k helix 6.1 -> 2.4 s"""
+    from .factors import refuse_range
+    refuse_range([f for _, _, f in fg.factors], "solveGraphParametric")
     with _blas_single_thread():
         return _solve_graph_parametric(fg, init, max_iters, tol, ctx, return_cov, verbose, shard, stats, polish)
 

@@ -30,6 +30,8 @@ import heapq
 
 import numpy as np
 
+from .factors import refuse_range
+
 
 class Clique:
     __slots__ = ("id", "frontals", "separators", "parent", "children", "factors", "level")
@@ -250,6 +252,7 @@ class TreeSolver:
                 shard: a factory `store -> distributed.FrontierShard` (the store exists only once the lifted universe is known): every level is
         then dealt to the ranks by clique -- share up-solve, ONE all-gather of the level's written blocks, one scatter; the block
         operations between levels run on every rank (each holds the whole store)."""
+        refuse_range([f for _, _, f in fg.factors], "TreeSolver")
         from .graph import FactorGraph
         if messages not in ("relative", "marginal"):
             raise ValueError("messages must be 'relative' or 'marginal'")
