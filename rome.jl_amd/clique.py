@@ -12,10 +12,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, api
+from .device import DeviceGraph
 from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2,
                       refuse_range)
 
-FAMILY_STREAM = {"p2p2": 0, "br1": 1 << 28, "br0": 2 << 28, "p3p3": 5 << 28, "prpt2": 7 << 28}   # = DeviceGraph.STREAM_* / rome_clique_proposals
+# Philox offsets of the families of rome_clique_proposals: DeviceGraph's ("prpt2" is this layer's name for its priorpt2)
+FAMILY_STREAM = {"p2p2": DeviceGraph.STREAM_P2P2, "br1": DeviceGraph.STREAM_BR1, "br0": DeviceGraph.STREAM_BR0, "p3p3": DeviceGraph.STREAM_P3P3,
+                 "prpt2": DeviceGraph.STREAM_PRIORPT2}
 
 
 class CliqueHost(C.Structure):

@@ -56,14 +56,33 @@ class DeviceGraph:
         self.bel = {Pose2: torch.zeros((len(pk.labels[Pose2]), 3, self.N), dtype=f64, device=self.device),
                     Point2: torch.zeros((len(pk.labels[Point2]), 2, self.N), dtype=f64, device=self.device),
                     Pose3: torch.zeros((len(pk.labels[Pose3]), 6, self.N), dtype=f64, device=self.device)}
+        # ---- the family list: one record per (factor family, direction) that is launched on its own, in LAUNCH order.  The proposal
+        # rows (prop_lo: rows of prop[vt_target] in list order per target type), the Philox offsets, the CSR, conv_step, the sweep
+        # methods and family_table() are all derived from it; `tab` is a view of its counts and tensors for outside readers.
+        self.fams = {}
         self.tab = {}
+        self.n_prop = {Pose2: 0, Point2: 0, Pose3: 0}
+        dev = lambda a, dt: a if a is None or torch.is_tensor(a) else t(a, dt)
+
+        def add(name, entry, vt_fixed, vt_target, dir_all, stream, targets, mu, L, rows4=None, alt=None, w=None, nh=None, in_step=True):
+            """alt / w / nh stay None unless the graph has them: the library picks its kernel from which pointers are null"""
+            rec = dict(name=name, entry=entry, fn=entry if plan_only else getattr(self._lib, entry), vt_fixed=vt_fixed, vt_target=vt_target,
+                       dir_all=dir_all, stream=stream, n=len(targets), targets_h=np.asarray(targets, dtype=np.int32), mu=mu, L=L,
+                       rows4=dev(rows4, i32), alt=dev(alt, i32), w=dev(w, f64), nh=dev(nh, f64), prop_lo=None)
+            if in_step:   # (the PriorPose2 / PriorPose3 samplers are launchable but own no rows: their factors are rows of p2p2 / p3p3)
+                rec["prop_lo"] = self.n_prop[vt_target]
+                self.n_prop[vt_target] += rec["n"]
+            self.fams[name] = rec
+            return rec
+
         # relative factors: both directions interleaved, then one ROME_DIR_PRIOR row per prior factor, so a
         # whole-graph sweep of one variable family is a single launch
-        for name, tab, ptab, d in (("p2p2", pk.p2p2, pk.prior2, 3), ("p3p3", pk.p3p3, pk.prior3, 6)):
-            if tab["F"] == 0 and ptab["F"] == 0:
-                continue
-            factor, dr, fixed, target = PackedGraph.conv_table(tab)
+        def relative(name, entry, vt, stream, tab, ptab):
+            d = vt.dim
             F, P = tab["F"], ptab["F"]
+            if F == 0 and P == 0:
+                return
+            factor, dr, fixed, target = PackedGraph.conv_table(tab)
             mu = np.concatenate([tab["mu"].reshape(F, d), ptab["mu"].reshape(P, d)])
             cov = np.concatenate([tab["cov"].reshape(F, d, d), ptab["cov"].reshape(P, d, d)])
             factor = np.concatenate([factor, F + np.arange(P, dtype=np.int32)])
@@ -87,75 +106,71 @@ class DeviceGraph:
             if nhf is not None and np.any(nhf > 0):
                 nh = np.concatenate([np.repeat(nhf, 2), np.zeros(P)] + ([nhf[ex["factor"]]] if E else []))
             # rows4: the four table columns interleaved (one 16-byte scalar load per convolution; selects the lean kernel)
-            self.tab[name] = dict(F=F, P=P, E=E, C_rel=2 * F, C=2 * F + P + E, mu=t(mu, f64), L=t(cholesky_lower(cov), f64),
-                                  nh=t(nh, f64) if nh is not None else None,
-                                  factor=t(factor, i32), dir=t(dr, i32), fixed=t(fixed, i32), target=t(target, i32),
-                                  rows4=t(np.stack([factor, dr, fixed, target], axis=1), i32), mh=hyp is not None,
-                                  alt=t(alt, i32) if alt is not None else None, w=t(w, f64) if w is not None else None)
+            rec = add(name, entry, vt, vt, 0, stream, target, t(mu, f64), t(cholesky_lower(cov), f64),
+                      rows4=np.stack([factor, dr, fixed, target], axis=1), alt=alt, w=w, nh=nh)
+            self.tab[name] = dict(F=F, P=P, E=E, C_rel=2 * F, C=rec["n"], mh=hyp is not None,
+                                  **{k: rec[k] for k in ("rows4", "alt", "w", "nh")})
+
+        def sampler(name, entry, vt, stream, tab, in_step=False):
+            if tab["F"]:
+                add(name, entry, None, vt, 0, stream, tab["var"], t(tab["mu"], f64), t(cholesky_lower(tab["cov"]), f64), in_step=in_step)
+
+        col = lambda v, n: np.full(n, v, np.int32)
+        relative("p2p2", "rome_conv_pose2pose2_dev", Pose2, self.STREAM_P2P2, pk.p2p2, pk.prior2)
         if pk.br["F"]:
-            b = pk.br
-            r0 = b["rows0"]
+            b, r0 = pk.br, pk.br["rows0"]
+            F, F0 = b["F"], len(r0["factor"])
             mh = bool((b["alt"] >= 0).any())
             nhb = b.get("nh")
-            has_nh = nhb is not None and bool(np.any(nhb > 0))
-            self.tab["br"] = dict(F=b["F"], F0=len(r0["factor"]), mh=mh, mu=t(b["mu"], f64), sigma=t(b["sigma"], f64),
-                                  nh=t(nhb, f64) if has_nh else None, nh0=t(nhb[r0["factor"]], f64) if has_nh else None,
-                                  pose=t(b["pose"], i32), point=t(b["point"], i32), alt=t(b["alt"], i32), w=t(b["w"], f64),
-                                  factor0=t(r0["factor"], i32), pose0=t(r0["pose"], i32), point0=t(r0["point"], i32),
-                                  alt0=t(r0["alt"], i32), w0=t(r0["w"], f64),
-                                  rows4_0=t(np.stack([r0["factor"], np.zeros(len(r0["factor"]), np.int32), r0["pose"], r0["point"]], axis=1), i32),
-                                  rows4_1=t(np.stack([np.arange(b["F"], dtype=np.int32), np.ones(b["F"], np.int32), b["point"], b["pose"]], axis=1), i32))
-        for name, tab, d in (("prior2", pk.prior2, 3), ("prior3", pk.prior3, 6), ("priorpt2", pk.priorpt2, 2)):
-            if tab["F"]:
-                self.tab[name] = dict(F=tab["F"], mu=t(tab["mu"], f64), L=t(cholesky_lower(tab["cov"]), f64), var=t(tab["var"], i32))
+            if nhb is None or not np.any(nhb > 0):
+                nhb = None
+            mu, sigma = t(b["mu"], f64), t(b["sigma"], f64)
+            br1 = add("br1", "rome_conv_pose2point2br_dev", Point2, Pose2, 1, self.STREAM_BR1, b["pose"], mu, sigma,
+                      rows4=np.stack([np.arange(F, dtype=np.int32), col(1, F), b["point"], b["pose"]], axis=1),
+                      alt=b["alt"] if mh else None, w=b["w"] if mh else None, nh=nhb)
+            add("br0", "rome_conv_pose2point2br_dev", Pose2, Point2, 0, self.STREAM_BR0, r0["point"], mu, sigma,
+                rows4=np.stack([r0["factor"], col(0, F0), r0["pose"], r0["point"]], axis=1),
+                alt=r0["alt"] if mh else None, w=r0["w"] if mh else None, nh=None if nhb is None else nhb[r0["factor"]])
+            self.tab["br"] = dict(F=F, F0=F0, mh=mh, nh=br1["nh"])
+        sampler("priorpt2", "rome_sample_priorpoint2_dev", Point2, self.STREAM_PRIORPT2, pk.priorpt2, in_step=True)   # rows behind the sightings
+        if "priorpt2" in self.fams:
+            self.tab["priorpt2"] = dict(F=pk.priorpt2["F"])
+        relative("p3p3", "rome_conv_pose3pose3_dev", Pose3, self.STREAM_P3P3, pk.p3p3, pk.prior3)
         # range-only factors (Range2D.jl): their own tables, launched after every other family; L = the [F][1] sigmas
+        nh_or_none = lambda nh: nh if np.any(nh > 0) else None
         r2 = getattr(pk, "p2rng", None)
         if r2 is not None and r2["F"]:
             factor, dr, fixed, target = PackedGraph.range_conv_table(r2)
-            nh = np.repeat(r2["nh"], 2)
-            self.tab["p2rng"] = dict(F=r2["F"], C=2 * r2["F"], mu=t(r2["mu"], f64), L=t(r2["sigma"], f64),
-                                     nh=t(nh, f64) if np.any(nh > 0) else None, target_h=target,
-                                     rows4=t(np.stack([factor, dr, fixed, target], axis=1), i32))
+            add("p2rng", "rome_conv_point2point2range_dev", Point2, Point2, 0, self.STREAM_P2RNG, target, t(r2["mu"], f64), t(r2["sigma"], f64),
+                rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(r2["nh"], 2)))
+            self.tab["p2rng"] = dict(C=2 * r2["F"])
         rp = getattr(pk, "pprng", None)
         if rp is not None and rp["F"]:
             F = rp["F"]
             fac = np.arange(F, dtype=np.int32)
-            self.tab["pprng"] = dict(F=F, mu=t(rp["mu"], f64), L=t(rp["sigma"], f64),
-                                     nh=t(rp["nh"], f64) if np.any(rp["nh"] > 0) else None,
-                                     rows4_0=t(np.stack([fac, np.zeros(F, np.int32), rp["pose"], rp["point"]], axis=1), i32),
-                                     rows4_1=t(np.stack([fac, np.ones(F, np.int32), rp["point"], rp["pose"]], axis=1), i32))
+            mu, sigma, nh = t(rp["mu"], f64), t(rp["sigma"], f64), dev(nh_or_none(rp["nh"]), f64)
+            for name, d, stream, vf, vt, fx, tg in (("pprng1", 1, self.STREAM_PPRNG1, Point2, Pose2, rp["point"], rp["pose"]),
+                                                    ("pprng0", 0, self.STREAM_PPRNG0, Pose2, Point2, rp["pose"], rp["point"])):
+                add(name, "rome_conv_pose2point2range_dev", vf, vt, d, stream, tg, mu, sigma, rows4=np.stack([fac, col(d, F), fx, tg], axis=1), nh=nh)
+            self.tab["pprng"] = dict(F=F)
+        sampler("prior2", "rome_sample_priorpose2_dev", Pose2, None, pk.prior2)
+        sampler("prior3", "rome_sample_priorpose3_dev", Pose3, None, pk.prior3)
 
-        self._build_solve_tables(t, i32)
+        # one conv_step: the fused Pose2 / Point2 call for its three records when all three have rows, then every other record that
+        # owns proposal rows, in list order
+        step = [r for r in self.fams.values() if r["prop_lo"] is not None]
+        fused = [self.fams[f] for f in ("p2p2", "br1", "br0") if f in self.fams and self.fams[f]["n"]]
+        self._fused = fused if len(fused) == 3 else []
+        self._unfused = [r for r in step if not any(r is f for f in self._fused)]
 
-    # ---- proposal buffers + CSR (variable -> proposal rows) for the product / solve loop ----
-    def _build_solve_tables(self, t, i32):
-        torch, pk = self.torch, self.packed
-        f64 = torch.float64
-        C2 = self.tab["p2p2"]["C"] if "p2p2" in self.tab else 0
-        Fb = self.tab["br"]["F"] if "br" in self.tab else 0
-        Fb0 = self.tab["br"]["F0"] if "br" in self.tab else 0
-        C3 = self.tab["p3p3"]["C"] if "p3p3" in self.tab else 0
-        Ppt = self.tab["priorpt2"]["F"] if "priorpt2" in self.tab else 0   # landmark priors: one proposal row each, behind the sightings
-        # range factors behind everything else -- Point2: [br0 | priorpt2 | p2rng (2F, rows 2f+dir) | pprng dir 0], Pose2: [p2p2 | br1 | pprng dir 1]
-        Cr = self.tab["p2rng"]["C"] if "p2rng" in self.tab else 0
-        Fq = self.tab["pprng"]["F"] if "pprng" in self.tab else 0
-        self.n_prop = {Pose2: C2 + Fb + Fq, Point2: Fb0 + Ppt + Cr + Fq, Pose3: C3}
+        # ---- proposal buffers + CSR (variable -> proposal rows) for the product / solve loop ----
         self.prop_bw = {}
-        self.prop = {Pose2: torch.zeros((max(C2 + Fb + Fq, 1), 3, self.N), dtype=f64, device=self.device),
-                     Point2: torch.zeros((max(Fb0 + Ppt + Cr + Fq, 1), 2, self.N), dtype=f64, device=self.device),
-                     Pose3: torch.zeros((max(C3, 1), 6, self.N), dtype=f64, device=self.device)}
+        self.prop = {vt: torch.zeros((max(self.n_prop[vt], 1), vt.dim, self.N), dtype=f64, device=self.device) for vt in (Pose2, Point2, Pose3)}
+        for r in step:   # the record's rows of prop[vt_target]: a view, made once (conv_step writes there)
+            r["prop"] = self.prop[r["vt_target"]][r["prop_lo"]:r["prop_lo"] + r["n"]]
         self.bel_next = {vt: torch.zeros_like(self.bel[vt]) for vt in (Pose2, Point2, Pose3)}
-        tgt2 = [self.tab["p2p2"]["target"].cpu().numpy()] if C2 else []
-        if Fb:
-            tgt2.append(pk.br["pose"])
-        if Fq:
-            tgt2.append(pk.pprng["pose"])
-        self._prop_targets = {Pose2: np.concatenate(tgt2) if tgt2 else np.zeros(0, np.int32),
-                              Point2: np.concatenate([pk.br["rows0"]["point"] if Fb else np.zeros(0, np.int32),
-                                                      pk.priorpt2["var"] if Ppt else np.zeros(0, np.int32),
-                                                      self.tab["p2rng"]["target_h"] if Cr else np.zeros(0, np.int32),
-                                                      pk.pprng["point"] if Fq else np.zeros(0, np.int32)]).astype(np.int32),
-                              Pose3: self.tab["p3p3"]["target"].cpu().numpy() if C3 else np.zeros(0, np.int32)}
+        self._prop_targets = {vt: np.concatenate([np.zeros(0, np.int32)] + [r["targets_h"] for r in step if r["vt_target"] is vt])
+                              for vt in (Pose2, Point2, Pose3)}
         self.frozen = set()
         self._build_csr()
 
@@ -192,30 +207,17 @@ class DeviceGraph:
         self._build_csr()
 
     # ---- one uniform view of the convolution tables (what the multi-GPU drivers plan launches from) ----
-    FAMILIES = {"p2p2": ("rome_conv_pose2pose2_dev", Pose2, Pose2, 0), "p3p3": ("rome_conv_pose3pose3_dev", Pose3, Pose3, 0),
-                "br1": ("rome_conv_pose2point2br_dev", Point2, Pose2, 1), "br0": ("rome_conv_pose2point2br_dev", Pose2, Point2, 0)}
+    RANK_FAMILIES = ("p2p2", "p3p3", "br1", "br0")
 
-    def families(self):
-        """Convolution families present in this graph, in launch order."""
-        out = [f for f in ("p2p2", "p3p3") if f in self.tab and self.tab[f]["C"]]
-        if "br" in self.tab:
-            out += ["br1", "br0"]
-        return out
+    def families(self, every=False):
+        """Convolution families present in this graph: the ones the multi-rank drivers serve, or (every=True) the whole family
+        list in launch order."""
+        return list(self.fams) if every else [f for f in self.RANK_FAMILIES if f in self.fams]
 
     def family_table(self, fam):
-        """-> dict(n, fn, vt_fixed, vt_target, dir_all, rows4 [n,4] int32 (factor, dir, fixed, target), mu, L, alt, w)."""
-        name, vf, vt, d = self.FAMILIES[fam]
-        fn = name if self.plan_only else getattr(self._lib, name)
-        if fam in ("p2p2", "p3p3"):
-            tb = self.tab[fam]
-            return dict(n=tb["C"], fn=fn, vt_fixed=vf, vt_target=vt, dir_all=0, rows4=tb["rows4"], mu=tb["mu"], L=tb["L"],
-                        alt=tb["alt"] if tb["mh"] else None, w=tb["w"] if tb["mh"] else None, nh=tb["nh"])
-        tb = self.tab["br"]
-        if fam == "br1":
-            return dict(n=tb["F"], fn=fn, vt_fixed=vf, vt_target=vt, dir_all=1, rows4=tb["rows4_1"], mu=tb["mu"], L=tb["sigma"],
-                        alt=tb["alt"] if tb["mh"] else None, w=tb["w"] if tb["mh"] else None, nh=tb["nh"])
-        return dict(n=tb["F0"], fn=fn, vt_fixed=vf, vt_target=vt, dir_all=0, rows4=tb["rows4_0"], mu=tb["mu"], L=tb["sigma"],
-                    alt=tb["alt0"] if tb["mh"] else None, w=tb["w0"] if tb["mh"] else None, nh=tb["nh0"])
+        """-> the family's record: n, fn, vt_fixed, vt_target, dir_all, rows4 [n,4] int32 (factor, dir, fixed, target; None for the prior
+        samplers), mu, L, alt, w, nh (None unless the graph has them), stream, targets_h, prop_lo, prop (its rows of self.prop)."""
+        return self.fams[fam]
 
     # ---- belief store ----
     def upload_beliefs(self, fg):
@@ -227,20 +229,9 @@ class DeviceGraph:
         self.ctx.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
 
     @staticmethod
-    def _ptr(x):
-        return None if x is None else C.c_void_p(x.data_ptr())
-
-    def _launch(self, fn, opts, **kw):
-        self._plan(fn, opts, **kw)()
-
-    def _plan(self, fn, opts, _ctx=None, **kw):
-        """Pre-builds the rome_conv_dev descriptor once; the returned callable only binds the current
-        torch stream and issues the launch (what a captured / replayed step calls).  `_ctx`: a Context whose stream the
-        caller has fixed (one per pipeline slot) -- the launch then is a single C call with no stream lookup."""
-        if self.plan_only:
-            return _PlanStub(fn, opts, kw)
+    def _conv_dev(keep, **kw):
+        """a rome_conv_dev descriptor from keywords (ints by value, tensors by address and appended to `keep`, None = null)"""
         cd = _lib.ConvDev()
-        keep = []
         for k, v in kw.items():
             if k == "mirror_row":
                 for m, r in enumerate(v):
@@ -250,6 +241,16 @@ class DeviceGraph:
             elif v is not None:
                 keep.append(v)
                 setattr(cd, k, v.data_ptr())
+        return cd
+
+    def _plan(self, fn, opts, _ctx=None, **kw):
+        """Pre-builds the rome_conv_dev descriptor once; the returned callable only binds the current
+        torch stream and issues the launch (what a captured / replayed step calls).  `_ctx`: a Context whose stream the
+        caller has fixed (one per pipeline slot) -- the launch then is a single C call with no stream lookup."""
+        if self.plan_only:
+            return _PlanStub(fn, opts, kw)
+        keep = []
+        cd = self._conv_dev(keep, **kw)
         o = _lib.Opts.from_buffer_copy(opts)
         ctx, check, cur = self.ctx, _lib.check, self.torch.cuda.current_stream
         h = ctx.handle
@@ -273,24 +274,35 @@ class DeviceGraph:
         launch._keep = (keep, o, cd)
         return launch
 
+    def _conv_kw(self, rec, out, noise=None, status=None, rows=None):
+        """the rome_conv_dev keywords of one family record (rows: a (lo, hi) slice of its table)"""
+        cut = (lambda x: x) if rows is None else (lambda x: None if x is None else x[rows[0]:rows[1]])
+        sampler = rec["vt_fixed"] is None
+        return dict(n_conv=rec["n"] if rows is None else rows[1] - rows[0], dir_all=rec["dir_all"], rows4=cut(rec["rows4"]), mu=rec["mu"], L=rec["L"],
+                    bel_fixed=None if sampler else self.bel[rec["vt_fixed"]], bel_target=None if sampler else self.bel[rec["vt_target"]],
+                    alt_var=cut(rec["alt"]), hypo_w=cut(rec["w"]), nullhypo=cut(rec["nh"]), noise=noise, out=out, status=status)
+
+    def _sweep(self, rec, opts, out=None, noise=None, status=None, rows=None, fixed_ctx=None, plan=False):
+        """One launch of one family record -> its proposals [n, dim, N].  rows=(lo, hi): that slice of the table, row ids (Philox
+        streams) kept.  plan=True: the pre-built launch (a callable) instead of launching."""
+        if out is None:
+            n = rec["n"] if rows is None else rows[1] - rows[0]
+            out = self.torch.empty((n, rec["vt_target"].dim, self.N), dtype=self.torch.float64, device=self.device)
+        if rows is not None:
+            opts = self._opts_at(opts, rows[0])
+        launch = self._plan(rec["fn"], opts, _ctx=fixed_ctx, **self._conv_kw(rec, out, noise, status, rows))
+        if plan:
+            return launch
+        launch()
+        return out
+
     def plan_sweep_pose2pose2(self, opts, out, noise=None, status=None, fixed_ctx=None):
         """fixed_ctx: a Context whose stream the caller has set once (Context.set_stream): the launch is then ONE C call, without the
         per-launch lookup of torch's current stream (5.4 -> ~2 us of host time per launch)"""
-        tb = self.tab["p2p2"]
-        mh = dict(alt_var=tb["alt"], hypo_w=tb["w"]) if tb["mh"] else {}
-        if tb["nh"] is not None:
-            mh["nullhypo"] = tb["nh"]
-        if fixed_ctx is not None:
-            mh["_ctx"] = fixed_ctx
-        return self._plan(self._lib.rome_conv_pose2pose2_dev, opts, n_conv=tb["C"], dir_all=0,
-                          factor=tb["factor"], dir=tb["dir"], fixed_var=tb["fixed"], target_var=tb["target"], rows4=tb["rows4"],
-                          mu=tb["mu"], L=tb["L"], bel_fixed=self.bel[Pose2], bel_target=self.bel[Pose2],
-                          noise=noise, out=out, status=status, **mh)
+        return self._sweep(self.fams["p2p2"], opts, out, noise, status, fixed_ctx=fixed_ctx, plan=True)
 
     def plan_sample_priors(self, opts, out, kind="prior2", noise=None):
-        tb = self.tab[kind]
-        fn = self._lib.rome_sample_priorpose2_dev if kind == "prior2" else self._lib.rome_sample_priorpose3_dev
-        return self._plan(fn, opts, n_conv=tb["F"], dir_all=0, mu=tb["mu"], L=tb["L"], noise=noise, out=out)
+        return self._sweep(self.fams[kind], opts, out, noise, plan=True)
 
     # ---- solve loop pieces (SURVEY §8(f) rows 1, 4) ----
     STREAM_P2P2, STREAM_BR1, STREAM_BR0, STREAM_PROD2, STREAM_PRODL, STREAM_P3P3, STREAM_PROD3, STREAM_PRIORPT2 = \
@@ -308,38 +320,22 @@ class DeviceGraph:
 
     def conv_step(self, opts, sweep=0):
         """All factor convolutions of the graph with the current beliefs -> self.prop (one launch per factor
-        family/direction).  Philox streams: base + sweep·2³² + family offset + row."""
+        family/direction, in the order of the family list).  Philox streams: base + sweep·2³² + family offset + row."""
         base = sweep << 32
-        C2 = self.tab["p2p2"]["C"] if "p2p2" in self.tab else 0
-        if C2 and "br" in self.tab and self.tab["br"]["F"] and self.tab["br"]["F0"]:
-            # a Pose2 / Point2 graph: ONE library call for the three families (one fused launch when the tables are plain)
-            Fb, Fb0 = self.tab["br"]["F"], self.tab["br"]["F0"]
-            self.sweep_graph_pose2(self._opts_at(opts, base), self.prop[Pose2][:C2], self.prop[Pose2][C2:C2 + Fb], self.prop[Point2][:Fb0])
-        else:
-            if C2:
-                self.sweep_pose2pose2(self._opts_at(opts, base + self.STREAM_P2P2), out=self.prop[Pose2][:C2])
-            if "br" in self.tab:
-                Fb, Fb0 = self.tab["br"]["F"], self.tab["br"]["F0"]
-                self.sweep_bearingrange(self._opts_at(opts, base + self.STREAM_BR1), 1, out=self.prop[Pose2][C2:C2 + Fb])
-                self.sweep_bearingrange(self._opts_at(opts, base + self.STREAM_BR0), 0, out=self.prop[Point2][:Fb0])
-        if "priorpt2" in self.tab:   # PriorPoint2 (src/factors/Point2D.jl:8-18): the landmark priors' samples, rows behind the sightings
-            tp = self.tab["priorpt2"]
-            Fb0 = self.tab["br"]["F0"] if "br" in self.tab else 0
-            self._launch(self._lib.rome_sample_priorpoint2_dev, self._opts_at(opts, base + self.STREAM_PRIORPT2), n_conv=tp["F"], dir_all=0,
-                         mu=tp["mu"], L=tp["L"], out=self.prop[Point2][Fb0:Fb0 + tp["F"]])
-        if "p3p3" in self.tab and self.tab["p3p3"]["C"]:
-            self.sweep_pose3pose3(self._opts_at(opts, base + self.STREAM_P3P3), out=self.prop[Pose3][:self.tab["p3p3"]["C"]])
-        if self.has_range():   # range-only factors: after every other family, their proposal rows behind the other rows
-            C2 = self.tab["p2p2"]["C"] if "p2p2" in self.tab else 0
-            Fb = self.tab["br"]["F"] if "br" in self.tab else 0
-            pt0 = (self.tab["br"]["F0"] if "br" in self.tab else 0) + (self.tab["priorpt2"]["F"] if "priorpt2" in self.tab else 0)
-            Cr = self.tab["p2rng"]["C"] if "p2rng" in self.tab else 0
-            if Cr:
-                self.sweep_point2point2range(self._opts_at(opts, base + self.STREAM_P2RNG), out=self.prop[Point2][pt0:pt0 + Cr])
-            if "pprng" in self.tab:
-                Fq = self.tab["pprng"]["F"]
-                self.sweep_pose2point2range(self._opts_at(opts, base + self.STREAM_PPRNG1), 1, out=self.prop[Pose2][C2 + Fb:C2 + Fb + Fq])
-                self.sweep_pose2point2range(self._opts_at(opts, base + self.STREAM_PPRNG0), 0, out=self.prop[Point2][pt0 + Cr:pt0 + Cr + Fq])
+        if self._fused:   # a Pose2 / Point2 graph: ONE library call for the three families (one fused launch when the tables are plain)
+            self.sweep_graph_pose2(self._opts_at(opts, base), *[r["prop"] for r in self._fused])
+        for rec in self._unfused:
+            self._sweep(rec, self._opts_at(opts, base + rec["stream"]), out=rec["prop"])
+
+    def conv_plan(self, opts, sweep=0):
+        """What conv_step(opts, sweep) launches, without launching (works on a plan-only graph): per launch the entry point, n_conv,
+        dir_all, the absolute Philox stream_offset, where its rows go in prop[vt_target], which optional columns are non-null, and
+        whether it is part of the fused Pose2 / Point2 call."""
+        base = opts.stream_offset + (sweep << 32)
+        return [dict(name=r["name"], entry=r["entry"], n_conv=r["n"], dir_all=r["dir_all"], stream_offset=base + r["stream"],
+                     vt_target=r["vt_target"].name, prop_lo=r["prop_lo"], cols=[k for k in ("alt", "w", "nh") if r[k] is not None],
+                     fused=k < len(self._fused))
+                for k, r in enumerate(self._fused + self._unfused)]
 
     def product_step(self, opts, sweep=0, bandwidth="silverman", product="importance", gibbs_iters=1):
         """bel <- product of the proposals targeting each variable (Jacobi update: computed into bel_next, copied back in place
@@ -487,126 +483,39 @@ class DeviceGraph:
             fn()
         return g
 
-    # ---- sweeps ----
+    # ---- sweeps: one launch over one family's whole table ----
     def sweep_pose2pose2(self, opts, out=None, noise=None, status=None, conv_slice=None):
         """All (factor, direction) Pose2Pose2 convolutions (row 2f+dir) followed by the PriorPose2 rows (and one row per multihypo
         factor for its second candidate) -> proposals [2F+P+E, 3, N], one launch."""
-        tb = self.tab["p2p2"]
-        lo, hi = (0, tb["C"]) if conv_slice is None else conv_slice
-        n = hi - lo
-        if out is None:
-            out = self.torch.empty((n, 3, self.N), dtype=self.torch.float64, device=self.device)
-        o = _lib.Opts.from_buffer_copy(opts); o.stream_offset = opts.stream_offset + lo
-        mh = dict(alt_var=tb["alt"][lo:hi], hypo_w=tb["w"][lo:hi]) if tb["mh"] else {}
-        if tb["nh"] is not None:
-            mh["nullhypo"] = tb["nh"][lo:hi]
-        self._launch(self._lib.rome_conv_pose2pose2_dev, o, n_conv=n, dir_all=0,
-                     factor=tb["factor"][lo:hi], dir=tb["dir"][lo:hi], fixed_var=tb["fixed"][lo:hi], target_var=tb["target"][lo:hi],
-                     rows4=tb["rows4"][lo:hi], mu=tb["mu"], L=tb["L"], bel_fixed=self.bel[Pose2], bel_target=self.bel[Pose2],
-                     noise=noise, out=out, status=status, **mh)
-        return out
+        return self._sweep(self.fams["p2p2"], opts, out, noise, status, rows=conv_slice)
 
     def sweep_pose3pose3(self, opts, out=None, noise=None, status=None):
-        tb = self.tab["p3p3"]
-        if out is None:
-            out = self.torch.empty((tb["C"], 6, self.N), dtype=self.torch.float64, device=self.device)
-        self._launch(self._lib.rome_conv_pose3pose3_dev, opts, n_conv=tb["C"], dir_all=0,
-                     factor=tb["factor"], dir=tb["dir"], fixed_var=tb["fixed"], target_var=tb["target"], rows4=tb["rows4"],
-                     mu=tb["mu"], L=tb["L"], bel_fixed=self.bel[Pose3], bel_target=self.bel[Pose3],
-                     noise=noise, out=out, status=status, **({"nullhypo": tb["nh"]} if tb["nh"] is not None else {}))
-        return out
+        return self._sweep(self.fams["p3p3"], opts, out, noise, status)
 
     def sweep_bearingrange(self, opts, direction, out=None, noise=None, status=None):
         """direction 0: poses -> landmark proposals [F0,2,N] (one row per (factor, candidate landmark));
         1: landmarks -> pose proposals [F,3,N].  Multihypo factors draw the landmark per particle."""
-        tb = self.tab["br"]
-        dt = 2 if direction == 0 else 3
-        nrow = tb["F0"] if direction == 0 else tb["F"]
-        if out is None:
-            out = self.torch.empty((nrow, dt, self.N), dtype=self.torch.float64, device=self.device)
-        if direction == 0:
-            kw = dict(factor=tb["factor0"], fixed_var=tb["pose0"], target_var=tb["point0"], rows4=tb["rows4_0"],
-                      bel_fixed=self.bel[Pose2], bel_target=self.bel[Point2])
-            if tb["mh"]:
-                kw.update(alt_var=tb["alt0"], hypo_w=tb["w0"])
-            if tb["nh0"] is not None:
-                kw.update(nullhypo=tb["nh0"])
-        else:
-            kw = dict(factor=None, fixed_var=tb["point"], target_var=tb["pose"], rows4=tb["rows4_1"],
-                      bel_fixed=self.bel[Point2], bel_target=self.bel[Pose2])
-            if tb["mh"]:
-                kw.update(alt_var=tb["alt"], hypo_w=tb["w"])
-            if tb["nh"] is not None:
-                kw.update(nullhypo=tb["nh"])
-        self._launch(self._lib.rome_conv_pose2point2br_dev, opts, n_conv=nrow, dir_all=int(direction), dir=None,
-                     mu=tb["mu"], L=tb["sigma"], noise=noise, out=out, status=status, **kw)
-        return out
+        return self._sweep(self.fams["br0" if direction == 0 else "br1"], opts, out, noise, status)
 
     def sweep_point2point2range(self, opts, out=None, noise=None, status=None):
         """Every Point2Point2Range factor in both directions (row 2f + dir: 0 solves lm from xi, 1 xi from lm) -> [2F, 2, N], one launch."""
-        tb = self.tab["p2rng"]
-        if out is None:
-            out = self.torch.empty((tb["C"], 2, self.N), dtype=self.torch.float64, device=self.device)
-        self._launch(self._lib.rome_conv_point2point2range_dev, opts, n_conv=tb["C"], dir_all=0, rows4=tb["rows4"], mu=tb["mu"], L=tb["L"],
-                     bel_fixed=self.bel[Point2], bel_target=self.bel[Point2], noise=noise, out=out, status=status,
-                     **({"nullhypo": tb["nh"]} if tb["nh"] is not None else {}))
-        return out
+        return self._sweep(self.fams["p2rng"], opts, out, noise, status)
 
     def sweep_pose2point2range(self, opts, direction, out=None, noise=None, status=None):
         """direction 0: poses -> landmark proposals [F, 2, N]; 1: landmarks -> pose proposals [F, 3, N] ((x, y) only, headings kept)."""
-        tb = self.tab["pprng"]
-        dt = 2 if direction == 0 else 3
-        if out is None:
-            out = self.torch.empty((tb["F"], dt, self.N), dtype=self.torch.float64, device=self.device)
-        bf, bt = (self.bel[Pose2], self.bel[Point2]) if direction == 0 else (self.bel[Point2], self.bel[Pose2])
-        self._launch(self._lib.rome_conv_pose2point2range_dev, opts, n_conv=tb["F"], dir_all=int(direction),
-                     rows4=tb["rows4_0"] if direction == 0 else tb["rows4_1"], mu=tb["mu"], L=tb["L"], bel_fixed=bf, bel_target=bt,
-                     noise=noise, out=out, status=status, **({"nullhypo": tb["nh"]} if tb["nh"] is not None else {}))
-        return out
+        return self._sweep(self.fams["pprng0" if direction == 0 else "pprng1"], opts, out, noise, status)
 
-    def _conv_dev(self, keep, **kw):
-        cd = _lib.ConvDev()
-        for k, v in kw.items():
-            if isinstance(v, int):
-                setattr(cd, k, v)
-            elif v is not None:
-                keep.append(v)
-                setattr(cd, k, v.data_ptr())
-        return cd
+    def sample_priors(self, opts, kind="prior2", out=None, noise=None):
+        return self._sweep(self.fams[kind], opts, out, noise)
 
     def sweep_graph_pose2(self, opts, out_p2p2, out_br1, out_br0, family_offsets=None):
         """The whole convolution sweep of a Pose2 / Point2 graph in ONE library call (rome_sweep_pose2_dev): Pose2Pose2 + PriorPose2
         rows, bearing-range -> pose rows, bearing-range -> landmark rows.  Plain tables run as one fused launch; tables with multihypo
         columns take the per-family launches inside the library -- the proposals are the same bit for bit either way.
-        family_offsets: Philox stream offsets of the three families (default: STREAM_P2P2 / STREAM_BR1 / STREAM_BR0)."""
+        family_offsets: Philox stream offsets of the three families (default: the records' own, STREAM_P2P2 / STREAM_BR1 / STREAM_BR0)."""
         keep = []
-        t2, tb = self.tab["p2p2"], self.tab["br"]
-        mh2 = dict(alt_var=t2["alt"], hypo_w=t2["w"]) if t2["mh"] else {}
-        if t2["nh"] is not None:
-            mh2["nullhypo"] = t2["nh"]
-        c2 = self._conv_dev(keep, n_conv=t2["C"], dir_all=0, rows4=t2["rows4"], factor=t2["factor"], dir=t2["dir"], fixed_var=t2["fixed"],
-                            target_var=t2["target"], mu=t2["mu"], L=t2["L"], bel_fixed=self.bel[Pose2], bel_target=self.bel[Pose2], out=out_p2p2, **mh2)
-        mh1 = dict(alt_var=tb["alt"], hypo_w=tb["w"]) if tb["mh"] else {}
-        if tb["nh"] is not None:
-            mh1["nullhypo"] = tb["nh"]
-        c1 = self._conv_dev(keep, n_conv=tb["F"], dir_all=1, rows4=tb["rows4_1"], fixed_var=tb["point"], target_var=tb["pose"], mu=tb["mu"],
-                            L=tb["sigma"], bel_fixed=self.bel[Point2], bel_target=self.bel[Pose2], out=out_br1, **mh1)
-        mh0 = dict(alt_var=tb["alt0"], hypo_w=tb["w0"]) if tb["mh"] else {}
-        if tb["nh0"] is not None:
-            mh0["nullhypo"] = tb["nh0"]
-        c0 = self._conv_dev(keep, n_conv=tb["F0"], dir_all=0, rows4=tb["rows4_0"], factor=tb["factor0"], fixed_var=tb["pose0"],
-                            target_var=tb["point0"], mu=tb["mu"], L=tb["sigma"], bel_fixed=self.bel[Pose2], bel_target=self.bel[Point2],
-                            out=out_br0, **mh0)
-        offs = (C.c_uint64 * 3)(*(family_offsets if family_offsets is not None else (self.STREAM_P2P2, self.STREAM_BR1, self.STREAM_BR0)))
+        recs = [self.fams[f] for f in ("p2p2", "br1", "br0")]
+        cds = [self._conv_dev(keep, **self._conv_kw(r, out)) for r, out in zip(recs, (out_p2p2, out_br1, out_br0))]
+        offs = (C.c_uint64 * 3)(*(family_offsets if family_offsets is not None else [r["stream"] for r in recs]))
         self._bind_stream()
-        _lib.check(self._lib.rome_sweep_pose2_dev(self.ctx.handle, C.byref(opts), C.byref(c2), C.byref(c1), C.byref(c0), offs), self.ctx.handle)
-
-    def sample_priors(self, opts, kind="prior2", out=None, noise=None):
-        tb = self.tab[kind]
-        d = 3 if kind == "prior2" else 6
-        if out is None:
-            out = self.torch.empty((tb["F"], d, self.N), dtype=self.torch.float64, device=self.device)
-        fn = self._lib.rome_sample_priorpose2_dev if kind == "prior2" else self._lib.rome_sample_priorpose3_dev
-        self._launch(fn, opts, n_conv=tb["F"], dir_all=0, factor=None, dir=None, fixed_var=None, target_var=None,
-                     mu=tb["mu"], L=tb["L"], bel_fixed=None, bel_target=None, noise=noise, out=out, status=None)
-        return out
+        _lib.check(self._lib.rome_sweep_pose2_dev(self.ctx.handle, C.byref(opts), *[C.byref(cd) for cd in cds], offs), self.ctx.handle)

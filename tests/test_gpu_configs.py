@@ -137,7 +137,7 @@ def test_manhattan_m3500_dataset_parametric_solve_and_sweep():
     assert tb["C"] == 10907 and int(status.sum()) == 0 and bool(torch.isfinite(out).all())
     # every proposal sits at its target's parametric estimate within the factor + belief noise
     m, sd = R.belief_stats(out.cpu().numpy()[:2000])
-    tgt = X[tb["target"].cpu().numpy()[:2000]]
+    tgt = X[tb["rows4"][:, 3].cpu().numpy()[:2000]]
     d = m - tgt; d[:, 2] = np.arctan2(np.sin(d[:, 2]), np.cos(d[:, 2]))
     assert np.percentile(np.hypot(d[:, 0], d[:, 1]), 99) < 1.0 and np.percentile(np.abs(d[:, 2]), 99) < 0.3
 

@@ -61,8 +61,8 @@ def test_convolutions_of_reference_beliefs_are_consistent_with_reference_posteri
     torch.cuda.synchronize()
     assert int(status.sum()) == 0
     prop = out.cpu().numpy()
-    target = tb["target"].cpu().numpy()
-    rel = np.nonzero(tb["dir"].cpu().numpy() != 2)[0]   # the fused prior row is checked separately below
+    target = tb["rows4"][:, 3].cpu().numpy()
+    rel = np.nonzero(tb["rows4"][:, 1].cpu().numpy() != 2)[0]   # the fused prior row is checked separately below
     assert len(rel) == 1000
     m_prop, sd_prop = stats(prop[rel])
     m_post, sd_post = stats(ref[target[rel]])
@@ -77,7 +77,7 @@ def test_convolutions_of_reference_beliefs_are_consistent_with_reference_posteri
     ratio = np.median(sd_post / sd_prop, axis=0)
     assert (ratio > 0.5).all() and (ratio < 0.95).all(), ratio
     # prior row: samples of the PriorPose2 on x0 against the reference's x0 belief
-    pr = np.nonzero(tb["dir"].cpu().numpy() == 2)[0]
+    pr = np.nonzero(tb["rows4"][:, 1].cpu().numpy() == 2)[0]
     assert len(pr) == 1 and target[pr[0]] == 0
     m0, s0 = stats(prop[pr[0]])
     assert np.allclose(m0, d["prior_mu"], atol=4 * np.sqrt(np.diag(d["prior_cov"]) / N).max() + 1e-3)
