@@ -9,6 +9,7 @@
  *     Pose3Pose3                 src/factors/Pose3Pose3.jl:9-29      (+ PriorPose3, src/factors/Pose3D.jl:15-19)
  *     Point2Point2Range          src/factors/Range2D.jl:8-17
  *     Pose2Point2Range           src/factors/Range2D.jl:40-54        (partial = (1, 2) on the pose)
+ *     Pose2Point2Bearing         src/factors/Bearing2D.jl:10-32
  * (paths relative to the RoME.jl v0.24.6 checkout).  Each entry point names the reference
  * interface it replaces.  Plain pointers and sizes only; no exceptions cross the ABI; the library
  * never retains caller pointers past a call.  There is NO CPU fallback: without a HIP device
@@ -170,6 +171,10 @@ int rome_residual_priorpose3(rome_ctx*, int32_t n, const double* m /*n*6*/, cons
  *   rome_residual_pose2point2range   (cf::CalcFactor{<:Pose2Point2Range})(rho, p, lm)    Range2D.jl:51-54  (p's heading is not read) */
 int rome_residual_point2point2range(rome_ctx*, int32_t n, const double* z /*n*/, const double* xi /*n*2*/, const double* lm /*n*2*/, double* r /*n*/);
 int rome_residual_pose2point2range(rome_ctx*, int32_t n, const double* z /*n*/, const double* p /*n*3*/, const double* lm /*n*2*/, double* r /*n*/);
+/* Bearing-only residual r = sym_rem(b − atan2(pl)), pl = R(θp)ᵀ (l − p.t): (cf::CalcFactor{<:Pose2Point2Bearing})(b, p, l),
+ * Bearing2D.jl:23-32 -- component 0 of the bearing-range residual (BearingRange2D.jl:57-60).  _pt: p as native points.      */
+int rome_residual_pose2point2bearing(rome_ctx*, int32_t n, const double* z /*n*/, const double* p /*n*3*/, const double* l /*n*2*/, double* r /*n*/);
+int rome_residual_pose2point2bearing_pt(rome_ctx*, int32_t n, const double* z /*n*/, const double* p_pt /*n*6*/, const double* l /*n*2*/, double* r /*n*/);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched factor convolutions, HOST pointers: C independent convolutions x N particles.
@@ -240,6 +245,31 @@ int rome_conv_pose2point2range(rome_ctx*, const rome_opts*, int32_t C, int32_t d
                                const double* mu /*C*/, const double* sigma /*C*/,
                                const double* fixed, const double* noise /*C*N*1 or NULL*/,
                                double* target_inout, int32_t* status);
+/* Bearing-only factor (src/factors/Bearing2D.jl; IIF approxConvBelief through the factor's residual functor, as above):
+ *   Pose2Point2Bearing(Z) over [p::Pose2, l::Point2], r = sym_rem(b − atan2(pl_y, pl_x)), pl = R(θp)ᵀ (l − p.t) (:23-32).
+ *   dir (scalar): 0 solves l (2) from the fixed poses (3); 1 solves the poses (3) from the fixed landmarks (2).
+ *   mu [C], sigma [C]: b = μ + σξ, one standard normal ξ per particle (the particle's own Philox call, first Box-Muller output);
+ *   sigma < 0 encodes Uniform(μ − |σ|, μ + |σ|) through the normal CDF of ξ.  noise [C][N][1]: standard normals, or
+ *   (ROME_NOISE_MEASUREMENTS) caller-sampled bearings for any other SamplableBelief.
+ *   One equation: neither direction has a unique root, so every solver runs inflate_cycles x {entropy, solve} from the start points.
+ *   No partial: the spread, the entropy and the solve act on every target coordinate (a Pose2 target: the compose-form entropy of
+ *   the bearing-range pose direction).
+ *   dir 0 (roots: the open ray from p.t in world direction θp + b).  CLOSED_FORM / NEWTON keep the distance and turn to the measured
+ *     bearing: n = ‖t − p.t‖, t <- p.t + n (cos, sin)(θp + b) -- the exact step (φ, n) += (r, 0) in the pose-frame polar chart.
+ *     t == p.t returns t unchanged (no direction can be given a length; the residual there is sym_rem(b), atan2(0, 0) = 0).
+ *   dir 1 (1 equation, 3 unknowns).  CLOSED_FORM / NEWTON keep the translation and turn the heading: θ <- wrap_pi(atan2(l − t) − b),
+ *     (x, y) returned bit for bit from the jittered point -- what the minimum-norm Gauss-Newton step tends to as ‖l − t‖ grows
+ *     (∂r/∂θ = 1, ‖∂r/∂t‖ = 1/‖l − t‖).  t == l returns θ = wrap_pi(−b).  A proposal samples the constraint surface over the
+ *     jittered start translations; the product over several sightings concentrates the translation.
+ *   GAUSS_NEWTON: that step iterated, the functor evaluated at every iterate until |r| <= tol (status 1 after max_iters).
+ *   NELDER_MEAD: on r² over all target coordinates (2 or 3), the heading wrapped on return.
+ *   status (NEWTON / GAUSS_NEWTON): 0 iff |r| <= tol at the returned point, the functor evaluated after the last cycle; CLOSED_FORM:
+ *   zeros.  nullhypo (opts->nullhypo) is honoured; multihypo is not supported (ROME_ERR_INVALID_ARG from the _dev entry when
+ *   alt_var / hypo_w is set).  N <= ROME_MAX_PARTICLES.                                                                          */
+int rome_conv_pose2point2bearing(rome_ctx*, const rome_opts*, int32_t C, int32_t dir,
+                                 const double* mu /*C*/, const double* sigma /*C*/,
+                                 const double* fixed, const double* noise /*C*N*1 or NULL*/,
+                                 double* target_inout, int32_t* status);
 /* Prior "convolution" = N samples of the prior as points: IIF samplePoint on PriorPose2.Z / PriorPose3.Z
  * (src/factors/PriorPose2.jl:13-17, src/factors/Pose3D.jl:8-12).                                 */
 int rome_sample_priorpose2(rome_ctx*, const rome_opts*, int32_t C, const double* mu /*C*3*/, const double* cov /*C*9*/,
@@ -504,6 +534,8 @@ int rome_conv_pose3pose3_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
  * point2point2range: the row direction from rows4 / dir / dir_all; pose2point2range: dir_all (0 landmark, 1 pose), dir must be NULL */
 int rome_conv_point2point2range_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 int rome_conv_pose2point2range_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
+/* bearing-only factor on device tables: L = [F][1] sigma; dir_all (0 landmark, 1 pose), dir must be NULL; no multihypo */
+int rome_conv_pose2point2bearing_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 /* The whole convolution sweep of a Pose2 / Point2 graph (odometry + bearing-range sightings: MIT.g2o with landmarks, the beehive) in ONE
  * call: the Pose2Pose2 (+ PriorPose2 rows) table, the bearing-range -> pose table (dir_all = 1) and the bearing-range -> landmark table
  * (dir_all = 0); any of them may be NULL.  Philox stream of row r of family k = opts->stream_offset + family_stream_offset[k] + r
@@ -531,9 +563,13 @@ int rome_sample_priorpoint2_dev(rome_ctx*, const rome_opts*, const rome_conv_dev
  *   POSE2POINT2BR    2  2  3  2   src/factors/BearingRange2D.jl:48-64
  *   PRIORPOINT2      2  2  2  -   src/factors/Point2D.jl:14-18
  *   POSE3POSE3       6  6  6  6   src/factors/Pose3Pose3.jl:17-29
- *   PRIORPOSE3       6  6  6  -   src/factors/Pose3D.jl:15-19                                     */
+ *   PRIORPOSE3       6  6  6  -   src/factors/Pose3D.jl:15-19
+ *   POSE2POINT2BEARING 1 1 3  2   src/factors/Bearing2D.jl:23-32  (the bearing row of POSE2POINT2BR, W = [w]; host-pointer entry
+ *                                 only: rome_linearize_dev, called by the multi-rank row sharding alone, answers
+ *                                 ROME_ERR_INVALID_ARG for it as for any kind above 5)                              */
 enum { ROME_FACTOR_PRIORPOSE2 = 0, ROME_FACTOR_POSE2POSE2 = 1, ROME_FACTOR_POSE2POINT2BR = 2,
-       ROME_FACTOR_PRIORPOINT2 = 3, ROME_FACTOR_POSE3POSE3 = 4, ROME_FACTOR_PRIORPOSE3 = 5 };
+       ROME_FACTOR_PRIORPOINT2 = 3, ROME_FACTOR_POSE3POSE3 = 4, ROME_FACTOR_PRIORPOSE3 = 5,
+       ROME_FACTOR_POSE2POINT2BEARING = 6 };
 int rome_linearize(rome_ctx*, int32_t kind, int32_t F, const double* mu, const double* W,
                    const double* xa, const double* xb, double* r, double* Ja, double* Jb);      /* host pointers   */
 int rome_linearize_dev(rome_ctx*, int32_t kind, int32_t F, const double* mu, const double* W,

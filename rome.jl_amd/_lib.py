@@ -18,6 +18,7 @@ MAX_PARTICLES = 4096            # ROME_MAX_PARTICLES (the register-resident kern
 MAX_PARTICLES_REGISTER = 512
 MAX_PARTICLES_KDE, MAX_PARTICLES_PRODUCT, MAX_PARTICLES_PRODUCT_POSE3, MAX_PARTICLES_GIBBS = 512, 512, 256, 256   # per-stage limits (header)
 FACTOR_PRIORPOSE2, FACTOR_POSE2POSE2, FACTOR_POSE2POINT2BR, FACTOR_PRIORPOINT2, FACTOR_POSE3POSE3, FACTOR_PRIORPOSE3 = range(6)
+FACTOR_POSE2POINT2BEARING = 6
 
 
 class RomeError(RuntimeError):
@@ -81,6 +82,10 @@ SIGNATURES = {
     "rome_conv_pose2point2range": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PI]),
     "rome_conv_point2point2range_dev": (C.c_int, [_CTX, _PO, _PT]),
     "rome_conv_pose2point2range_dev": (C.c_int, [_CTX, _PO, _PT]),
+    "rome_residual_pose2point2bearing": (C.c_int, [_CTX, C.c_int32, _PD, _PD, _PD, _PD]),
+    "rome_residual_pose2point2bearing_pt": (C.c_int, [_CTX, C.c_int32, _PD, _PD, _PD, _PD]),
+    "rome_conv_pose2point2bearing": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PI]),
+    "rome_conv_pose2point2bearing_dev": (C.c_int, [_CTX, _PO, _PT]),
     "rome_conv_pose2pose2_mh": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI]),
     "rome_conv_pose3pose3": (C.c_int, [_CTX, _PO, C.c_int32, _PI, _PD, _PD, _PD, _PD, _PD, _PI]),
     "rome_sample_priorpose2": (C.c_int, [_CTX, _PO, C.c_int32, _PD, _PD, _PD, _PD]),

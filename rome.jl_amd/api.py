@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3,
-                      PriorPose3, Point2Point2Range, Pose2Point2Range, getCoordinates)
+                      PriorPose3, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, getCoordinates)
 
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
@@ -93,6 +93,18 @@ def residual_pose2point2range(z, p, lm, ctx=None):
     return _rows(_lib.load().rome_residual_pose2point2range, ctx, (z, p, lm), (1, 3, 2), 1)[:, 0]
 
 
+def residual_pose2point2bearing(z, p, l, ctx=None):
+    """r = sym_rem(b − atan2(pl)), pl = R(θp)ᵀ (l − p.t) per row (Bearing2D.jl:23-32): z (n,) bearings, p (n, 3), l (n, 2) -> (n,)"""
+    z = np.atleast_1d(_d(z)).reshape(-1, 1)
+    return _rows(_lib.load().rome_residual_pose2point2bearing, ctx, (z, p, l), (1, 3, 2), 1)[:, 0]
+
+
+def residual_pose2point2bearing_pt(z, p_pt, l, ctx=None):
+    """the same with the poses as native points (n, 6)"""
+    z = np.atleast_1d(_d(z)).reshape(-1, 1)
+    return _rows(_lib.load().rome_residual_pose2point2bearing_pt, ctx, (z, p_pt, l), (1, 6, 2), 1)[:, 0]
+
+
 def _meas_coords(factor, meas):
     """Accepts the reference's tangent containers (hat form) or plain coordinates."""
     m = np.asarray(meas, dtype=np.float64).ravel()
@@ -109,6 +121,11 @@ def _meas_coords(factor, meas):
     elif isinstance(factor, (Point2Point2Range, Pose2Point2Range)):
         if m.size == 1:   # the range sample ρ
             return m
+    elif isinstance(factor, Pose2Point2Bearing):
+        if m.size == 1:
+            return m
+        if m.size == 4:   # [0 -b; b 0] column-major (the so(2) tangent the reference samples)
+            return m[1:2]
     elif isinstance(factor, (Pose3Pose3, PriorPose3)):
         if m.size == 6:
             return m
@@ -138,6 +155,10 @@ def calcFactorResidualTemporary(factor, vartypes, meas, points, ctx=None):
     if isinstance(factor, Pose2Point2Range):
         c = pts[0] if pts[0].size == 3 else getCoordinates(Pose2, pts[0])
         return residual_pose2point2range(z, [c], [pts[1]], ctx)[0]
+    if isinstance(factor, Pose2Point2Bearing):
+        if pts[0].size == 6:
+            return residual_pose2point2bearing_pt(z, [pts[0]], [pts[1]], ctx)[0]
+        return residual_pose2point2bearing(z, [pts[0]], [pts[1]], ctx)[0]
     if isinstance(factor, Pose3Pose3):
         if pts[0].size == 12:
             return residual_pose3pose3_pt([z], [pts[0]], [pts[1]], ctx)[0]
@@ -150,7 +171,8 @@ def calcFactorResidualTemporary(factor, vartypes, meas, points, ctx=None):
 
 # ------------------------------------------------------------------ parametric linearisation
 _LIN_DIMS = {_lib.FACTOR_PRIORPOSE2: (3, 3, 3, 0), _lib.FACTOR_POSE2POSE2: (3, 3, 3, 3), _lib.FACTOR_POSE2POINT2BR: (2, 2, 3, 2),
-             _lib.FACTOR_PRIORPOINT2: (2, 2, 2, 0), _lib.FACTOR_POSE3POSE3: (6, 6, 6, 6), _lib.FACTOR_PRIORPOSE3: (6, 6, 6, 0)}
+             _lib.FACTOR_PRIORPOINT2: (2, 2, 2, 0), _lib.FACTOR_POSE3POSE3: (6, 6, 6, 6), _lib.FACTOR_PRIORPOSE3: (6, 6, 6, 0),
+             _lib.FACTOR_POSE2POINT2BEARING: (1, 1, 3, 2)}
 
 
 def linearize(kind, mu, W, xa, xb=None, ctx=None):
@@ -381,6 +403,33 @@ def conv_pose2point2range(opts, direction, mu, sigma, fixed, target, noise=None,
     st = np.zeros((C_, N), dtype=np.int32) if want_status else None
     _lib.check(_lib.load().rome_conv_pose2point2range(ctx.handle, C.byref(opts), C_, int(direction), _p(mu), _p(sigma),
                                                      _p(fixed), _p(noise), _p(out), _pi(st)), ctx.handle)
+    return (out, st) if want_status else out
+
+
+def conv_pose2point2bearing(opts, direction, mu, sigma, fixed, target, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None):
+    """C Pose2Point2Bearing convolutions (Bearing2D.jl:10-32), one direction per call: 0 solves the landmarks from the fixed poses
+    (each start point keeps its distance and is turned onto the ray), 1 the poses from the fixed landmarks (each start pose keeps its
+    translation and is turned to the measured bearing).  mu / sigma (C,): the bearing belief (sigma < 0: Uniform(mu ± |sigma|));
+    noise: C blocks of one standard normal per particle (or the bearings themselves under presampled=NOISE_MEASUREMENTS);
+    nullhypo: the fraction of particles the factor does not apply to (opts.nullhypo when None)."""
+    ctx = ctx or default_context()
+    opts = _with_layout(opts, layout)
+    if nullhypo is not None:
+        opts = _lib.Opts.from_buffer_copy(opts)
+        opts.nullhypo = float(nullhypo)
+    if direction not in (0, 1):
+        raise ValueError("direction must be 0 (solve the landmark) or 1 (solve the pose)")
+    mu = np.atleast_1d(_d(mu)).ravel(); C_ = mu.shape[0]; N = opts.n_particles
+    sigma = np.atleast_1d(_d(sigma)).ravel()
+    if sigma.shape != (C_,):
+        raise ValueError("sigma: expected %d values, got %s" % (C_, sigma.shape))
+    df, dt = (3, 2) if direction == 0 else (2, 3)
+    fixed = _blocks(fixed, C_, N, df, opts.layout)
+    out = _blocks(target, C_, N, dt, opts.layout).copy()
+    noise = None if noise is None else _blocks(noise, C_, N, 1, opts.layout, points_ok=False)
+    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
+    _lib.check(_lib.load().rome_conv_pose2point2bearing(ctx.handle, C.byref(opts), C_, int(direction), _p(mu), _p(sigma),
+                                                       _p(fixed), _p(noise), _p(out), _pi(st)), ctx.handle)
     return (out, st) if want_status else out
 
 

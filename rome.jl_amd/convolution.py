@@ -3,7 +3,7 @@ test/testBasicPose2Conv.jl:25, test/TestPoseAndPoint2Constraints.jl:36,97)."""
 import numpy as np
 
 from . import _lib, api
-from .factors import Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range
+from .factors import Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing
 
 
 def approxConv(fg, flabel, target, solver=_lib.SOLVER_NEWTON, seed=None, ctx=None, **optkw):
@@ -56,6 +56,8 @@ def approxConv(fg, flabel, target, solver=_lib.SOLVER_NEWTON, seed=None, ctx=Non
         return api.conv_point2point2range(opts, [f.Z.mu], [f.Z.sigma], fixed, u0, dirs=[direction], ctx=ctx)[0]
     if isinstance(f, Pose2Point2Range):
         return api.conv_pose2point2range(opts, direction, [f.Z.mu], [f.Z.sigma], fixed, u0, ctx=ctx)[0]
+    if isinstance(f, Pose2Point2Bearing):
+        return api.conv_pose2point2bearing(opts, direction, [f.Z.mu], [f.Z.sigma], fixed, u0, ctx=ctx)[0]
     raise TypeError("unsupported factor type %s" % type(f).__name__)
 
 

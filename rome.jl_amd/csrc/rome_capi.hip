@@ -162,7 +162,7 @@ void from_soa(const double* src, int C, int N, int d, int layout, double* dst) {
   }
 }
 
-enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2, kP2R, kPPR };
+enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2, kP2R, kPPR, kPB };
 
 inline int point_len(int dim) { return dim == 3 ? 6 : (dim == 6 ? 12 : dim); }
 
@@ -286,6 +286,7 @@ int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const i
     case kPriorPt2: e = rome::launch_sample_priorpoint2(a, s); break;
     case kP2R: e = rome::launch_conv_point2point2range(a, o->solver, s); break;
     case kPPR: e = rome::launch_conv_pose2point2range(a, o->solver, s); break;
+    case kPB: e = rome::launch_conv_pose2point2bearing(a, o->solver, s); break;
   }
   ROME_HIP(ctx, e);
   ROME_HIP(ctx, hipMemcpyAsync(h_out, d_out, sizeof(double) * blk_t, hipMemcpyDeviceToHost, s));
@@ -476,6 +477,16 @@ int rome_residual_pose2point2range(rome_ctx* c, int32_t n, const double* z, cons
   return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
     return rome::launch_residual_range(n, a, b, 3, d, o, s); });
 }
+int rome_residual_pose2point2bearing(rome_ctx* c, int32_t n, const double* z, const double* p, const double* l, double* r) {
+  RowBuf in[3] = {{z, 1}, {p, 3}, {l, 2}};
+  return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
+    return rome::launch_residual_bearing(n, a, b, 0, d, o, s); });
+}
+int rome_residual_pose2point2bearing_pt(rome_ctx* c, int32_t n, const double* z, const double* p, const double* l, double* r) {
+  RowBuf in[3] = {{z, 1}, {p, 6}, {l, 2}};
+  return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
+    return rome::launch_residual_bearing(n, a, b, 1, d, o, s); });
+}
 
 /* ---- host-pointer convolutions ---- */
 int rome_conv_pose2pose2(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* cov,
@@ -544,6 +555,14 @@ int rome_conv_pose2point2range(rome_ctx* c, const rome_opts* o, int32_t C, int32
   for (int i = 0; i < C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;
   return host_conv(c, o, kPPR, C, nullptr, dir, 1, dir == 0 ? 3 : 2, dir == 0 ? 2 : 3, mu, sigma, 1, fixed, noise, target_inout, status);
 }
+int rome_conv_pose2point2bearing(rome_ctx* c, const rome_opts* o, int32_t C, int32_t dir, const double* mu, const double* sigma,
+                                 const double* fixed, const double* noise, double* target_inout, int32_t* status) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || C < 0 || (dir != 0 && dir != 1) || (C > 0 && (!mu || !sigma || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
+  if (C == 0) return ROME_OK;
+  for (int i = 0; i < C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;  /* sigma < 0 encodes Uniform(mu ± |sigma|) */
+  return host_conv(c, o, kPB, C, nullptr, dir, 1, dir == 0 ? 3 : 2, dir == 0 ? 2 : 3, mu, sigma, 1, fixed, noise, target_inout, status);
+}
 int rome_sample_priorpose2(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* cov, const double* noise, double* out) {
   int rc = check_opts(o); if (rc) return rc;
   if (!c || C < 0 || (C > 0 && (!mu || !cov || !out))) return ROME_ERR_INVALID_ARG;
@@ -609,6 +628,14 @@ int rome_conv_pose2point2range_dev(rome_ctx* c, const rome_opts* o, const rome_c
   if (t->dir != nullptr || (t->dir_all != 0 && t->dir_all != 1)) return ROME_ERR_INVALID_ARG;
   rome::ConvArgs a; args_from_dev(a, o, t);
   ROME_HIP(c, rome::launch_conv_pose2point2range(a, o->solver, c->stream));
+  return ROME_OK;
+}
+int rome_conv_pose2point2bearing_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
+  int rc = dev_common(c, o, t, true); if (rc) return rc;
+  if (t->alt_var || t->hypo_w) return ROME_ERR_INVALID_ARG;   // no multihypo on bearing-only factors
+  if (t->dir != nullptr || (t->dir_all != 0 && t->dir_all != 1)) return ROME_ERR_INVALID_ARG;
+  rome::ConvArgs a; args_from_dev(a, o, t);
+  ROME_HIP(c, rome::launch_conv_pose2point2bearing(a, o->solver, c->stream));
   return ROME_OK;
 }
 int rome_sweep_pose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* p2p2, const rome_conv_dev* br1, const rome_conv_dev* br0,
@@ -1428,6 +1455,7 @@ static bool lin_dims_host(int kind, int& dz, int& dr, int& da, int& db) {
     case ROME_FACTOR_PRIORPOINT2: dz = 2; dr = 2; da = 2; db = 0; return true;
     case ROME_FACTOR_POSE3POSE3: dz = 6; dr = 6; da = 6; db = 6; return true;
     case ROME_FACTOR_PRIORPOSE3: dz = 6; dr = 6; da = 6; db = 0; return true;
+    case ROME_FACTOR_POSE2POINT2BEARING: dz = 1; dr = 1; da = 3; db = 2; return true;
     default: return false;
   }
 }
@@ -1435,6 +1463,9 @@ int rome_linearize_dev(rome_ctx* c, int32_t kind, int32_t F, const double* mu, c
                        const double* xb, double* r, double* Ja, double* Jb) {
   int dz, dr, da, db;
   if (!c || F < 0 || !lin_dims_host(kind, dz, dr, da, db)) return ROME_ERR_INVALID_ARG;
+  // the device-pointer entry serves kinds 0..5: its one caller is the row-sharded multi-rank linearisation, which refuses
+  // bearing-only factors by name (the host-pointer entry below serves kind 6)
+  if (kind == ROME_FACTOR_POSE2POINT2BEARING) return ROME_ERR_INVALID_ARG;
   ROME_BIND(c);
   if (F > 0 && (!mu || !W || !xa || !r || !Ja || (db > 0 && (!xb || !Jb)))) return ROME_ERR_INVALID_ARG;
   ROME_HIP(c, rome::launch_linearize(kind, F, mu, W, xa, xb, r, Ja, Jb, c->stream));

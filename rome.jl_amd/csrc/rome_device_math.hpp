@@ -468,6 +468,15 @@ __device__ __forceinline__ void residual_bearingrange(double b, double rho, cons
   r[1] = rho - fast_sqrt(plx * plx + ply * ply);
 }
 
+// Pose2Point2Bearing (src/factors/Bearing2D.jl:23-32): pl = p.Rᵀ (l - p.t);  r = sym_rem(b - atan2(pl)) -- the bearing row of the
+// bearing-range residual on its own (the literal form: residual entries, the solvers' functor, the Nelder-Mead cost)
+__device__ __forceinline__ double residual_bearing(double b, const Se2& p, double lx, double ly) {
+  const double dx = lx - p.x, dy = ly - p.y;
+  const double plx = p.c * dx + p.s * dy;
+  const double ply = p.c * dy - p.s * dx;
+  return sym_rem(b - fast_atan2(ply, plx));
+}
+
 // entropy: u ← u ∘ exp_ϵ(hat(e))
 __device__ __forceinline__ void se2_add_entropy(double (&t)[3], double spread, const double (&u)[3]) {
   const double ex = spread * (u[0] - 0.5), ey = spread * (u[1] - 0.5), et = spread * (u[2] - 0.5);

@@ -552,6 +552,88 @@ struct P2R : RangeBase<2, 2> {};
 template <int DIR>
 struct PPR : RangeBase<DIR == 0 ? 3 : 2, DIR == 0 ? 2 : 3> {};
 
+// ---- bearing-only factor (src/factors/Bearing2D.jl:23-32): Pose2Point2Bearing over [p::Pose2, l::Point2],
+// r = sym_rem(b − atan2(pl)), pl = R(θp)ᵀ (l − p.t): the bearing row of BR<DIR> on its own.  One equation: neither direction has a
+// unique root, so every solver runs the inflation cycles {entropy, solve} on k_conv / k_conv_big, entropy and spread over ALL target
+// coordinates (no partial: the compose form of BR<1> on a pose target).
+//   DIR 0 (pose fixed -> landmark; roots: the open ray from p.t in world direction θp + b)
+//     CLOSED_FORM / NEWTON: keep the distance, turn to the measured bearing:  n = ‖t − p.t‖,  t ← p.t + n (cos, sin)(θp + b) -- the
+//     exact step (φ, n) += (r, 0) in the pose-frame polar chart (BR<0>'s Gauss-Newton step without its range row).  One sincos per
+//     particle per call (Prep), n from range_norm; no atan2.  t == p.t: n = 0, t is returned unchanged (no direction has a length).
+//   DIR 1 (landmark fixed -> pose; 1 equation, 3 unknowns)
+//     CLOSED_FORM / NEWTON: keep the translation, turn the heading:  θ ← wrap_pi(atan2(l − t) − b), (x, y) untouched -- what the
+//     minimum-norm Gauss-Newton step tends to as ‖l − t‖ grows (∂r/∂θ = 1, ‖∂r/∂t‖ = 1/‖l − t‖).  One atan2 per particle per cycle.
+//     t == l: atan2(0, 0) = 0, θ = wrap_pi(−b) (a select).
+//   GAUSS_NEWTON: that step iterated, the functor (literal form) evaluated at every iterate until |r| ≤ tol.
+//   NELDER_MEAD:  nelder_mead<DT> on r² over all target coordinates, the heading wrapped on return.
+// The measurement, the start-point reference, the tangent and the spread are RangeBase's (one scalar belief, σ < 0: Uniform; one
+// standard normal per particle from the particle's own Philox call); the entropy and the canonical form are BR<DIR>'s.
+template <int DIR>
+struct BearingCost {
+  double b; double fx[3];
+  __device__ __forceinline__ double operator()(const double (&x)[DIR == 0 ? 2 : 3]) const {
+    double r;
+    if constexpr (DIR == 0) r = residual_bearing(b, se2_from_coords(fx[0], fx[1], fx[2]), x[0], x[1]);
+    else r = residual_bearing(b, se2_from_coords(x[0], x[1], x[2]), fx[0], fx[1]);
+    return r * r;
+  }
+};
+template <int DIR>
+struct PB : RangeBase<DIR == 0 ? 3 : 2, DIR == 0 ? 2 : 3> {
+  using Base = RangeBase<DIR == 0 ? 3 : 2, DIR == 0 ? 2 : 3>;
+  using typename Base::Consts;
+  using typename Base::Aux;
+  static constexpr int DF = Base::DF, DT = Base::DT;
+  __device__ static __forceinline__ void canonical(double (&t)[DT]) { BR<DIR>::canonical(t); }
+  __device__ static __forceinline__ void add_entropy(double (&t)[DT], Aux&, double spread, const double (&u)[DT]) {
+    typename BR<DIR>::Aux none;
+    BR<DIR>::add_entropy(t, none, spread, u);
+  }
+  struct Prep { double c, s; };   // DIR 0: (cos, sin)(θp + b)
+  __device__ static __forceinline__ Prep prepare(const Consts&, const double (&z)[1], const double (&fx)[DF]) {
+    Prep P; P.c = 1.0; P.s = 0.0;
+    if constexpr (DIR == 0) fast_sincos(fx[2] + z[0], &P.s, &P.c);
+    return P;
+  }
+  // the residual FUNCTOR itself at the target point t (pose fixed / landmark target, or the reverse)
+  __device__ static __forceinline__ double functor(const double (&z)[1], const double (&fx)[DF], const double (&t)[DT]) {
+    if constexpr (DIR == 0) return residual_bearing(z[0], se2_from_coords(fx[0], fx[1], fx[2]), t[0], t[1]);
+    else return residual_bearing(z[0], se2_from_coords(t[0], t[1], t[2]), fx[0], fx[1]);
+  }
+  __device__ static __forceinline__ int verify(const Consts&, const double (&z)[1], const double (&fx)[DF], const double (&t)[DT], const Aux&, double tol) {
+    return fabs(functor(z, fx, t)) <= tol ? 0 : 1;
+  }
+  __device__ static __forceinline__ void step(const Prep& P, const double (&z)[1], const double (&fx)[DF], double (&t)[DT]) {
+    if constexpr (DIR == 0) {
+      const double n = range_norm(t[0] - fx[0], t[1] - fx[1]);       // (n == 0: fx + 0 (c, s) = t)
+      t[0] = __builtin_fma(n, P.c, fx[0]); t[1] = __builtin_fma(n, P.s, fx[1]);
+    } else {
+      const double dx = fx[0] - t[0], dy = fx[1] - t[1];
+      const bool ok = dx != 0.0 || dy != 0.0;
+      t[2] = wrap_pi((ok ? fast_atan2(dy, dx) : 0.0) - z[0]);
+    }
+  }
+  template <int SOLVER>
+  __device__ static __forceinline__ int solve(const Consts&, const Prep& P, const double (&z)[1], const double (&fx)[DF],
+                                              double (&t)[DT], Aux&, int max_iters, double tol) {
+    if constexpr (SOLVER == kSolverClosedForm || SOLVER == kSolverNewton) {
+      step(P, z, fx, t);
+      return 0;
+    } else if constexpr (SOLVER == kSolverGaussNewton) {
+      for (int it = 0; it < max_iters; ++it) {
+        if (fabs(functor(z, fx, t)) <= tol) return 0;
+        step(P, z, fx, t);
+      }
+      return 1;
+    } else {
+      BearingCost<DIR> cost{z[0], {fx[0], fx[1], DF == 3 ? fx[DF - 1] : 0.0}};
+      const int st = nelder_mead<DT>(cost, t, max_iters, tol);
+      if constexpr (DT == 3) t[2] = wrap_pi(t[2]);
+      return st;
+    }
+  }
+};
+
 // ---- Pose3Pose3.  Belief blocks hold coordinates (t, ω); inside the kernel the rotation of every particle lives as a
 // unit quaternion (Aux) from load to store, so the inflation cycles never go through Exp/Log round trips, and the root
 // (a, qa) of the residual  r = ( p.t + R_p z_t − q.t , Log(R_qᵀ R_p Exp(z_ω)) )  is prepared once per particle:
@@ -1559,6 +1641,15 @@ __global__ void k_residual_bearingrange(int n, const double* z, const double* p,
   residual_bearingrange(z[2 * i], z[2 * i + 1], P, l[2 * i], l[2 * i + 1], rr);
   r[2 * i] = rr[0]; r[2 * i + 1] = rr[1];
 }
+// bearing-only residual; p rows as k_residual_bearingrange
+__global__ void k_residual_bearing(int n, const double* z, const double* p, int p_is_point, const double* l, double* r) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Se2 P;
+  if (p_is_point) { P.x = p[6 * i]; P.y = p[6 * i + 1]; P.c = p[6 * i + 2]; P.s = p[6 * i + 3]; }
+  else P = se2_from_coords(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+  r[i] = residual_bearing(z[i], P, l[2 * i], l[2 * i + 1]);
+}
 // p,q rows are native points (12 doubles: t, R col-major) when pts != 0, else coords (6)
 __global__ void k_residual_pose3pose3(int n, const double* z, const double* p, const double* q, int pts, double* r) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1720,6 +1811,10 @@ hipError_t launch_conv_bearingrange(const ConvArgs& a, int solver, hipStream_t s
 hipError_t launch_conv_point2point2range(const ConvArgs& a, int solver, hipStream_t s) { return launch_solver<P2R>(a, solver, s); }
 hipError_t launch_conv_pose2point2range(const ConvArgs& a, int solver, hipStream_t s) {
   return a.dir_all == 0 ? launch_solver<PPR<0>>(a, solver, s) : launch_solver<PPR<1>>(a, solver, s);
+}
+// bearing-only factor: a ray / a two-parameter family of roots (kUniqueRoot = false) -> k_conv / k_conv_big only
+hipError_t launch_conv_pose2point2bearing(const ConvArgs& a, int solver, hipStream_t s) {
+  return a.dir_all == 0 ? launch_solver<PB<0>>(a, solver, s) : launch_solver<PB<1>>(a, solver, s);
 }
 static bool plain_rows(const ConvArgs& a) { return a.rows4 && !a.noise && !a.alt_var && !a.nullhypo && !a.status && !a.row_stream && !a.meas_block; }
 static bool hypo_rows(const ConvArgs& a) { return a.rows4 && !a.noise && !a.status && !a.row_stream && !a.meas_block && (a.alt_var || a.nullhypo); }
@@ -1929,6 +2024,10 @@ hipError_t launch_residual_priorpose3(int n, const double* m, const double* p, d
 }
 hipError_t launch_residual_range(int n, const double* z, const double* x, int dx, const double* l, double* r, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_residual_range, rows_grid(n), dim3(256), 0, s, n, z, x, dx, l, r);
+  return hipGetLastError();
+}
+hipError_t launch_residual_bearing(int n, const double* z, const double* p, int p_is_point, const double* l, double* r, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(k_residual_bearing, rows_grid(n), dim3(256), 0, s, n, z, p, p_is_point, l, r);
   return hipGetLastError();
 }
 

@@ -103,6 +103,23 @@ __device__ __forceinline__ void lin_row_bearingrange(const double* mu, const dou
   store_whitened<2, 3>(W, JA, Ja);
   store_whitened<2, 2>(W, JB, Jb);
 }
+// Pose2Point2Bearing (Bearing2D.jl:23-32): the bearing row of lin_row_bearingrange, W = [w] a scalar whitening weight
+__device__ __forceinline__ void lin_row_bearing(const double* mu, const double* W, const double* xa, const double* xb,
+                                   double* r, double* Ja, double* Jb) {
+  const Se2 P = se2_from_coords(xa[0], xa[1], xa[2]);
+  const double lx = xb[0], ly = xb[1];
+  const double rr[1] = {residual_bearing(mu[0], P, lx, ly)};
+  const double dx = lx - P.x, dy = ly - P.y;
+  const double plx = P.c * dx + P.s * dy, ply = P.c * dy - P.s * dx;
+  const double n2 = plx * plx + ply * ply;
+  const double a00 = ply / n2, a01 = -plx / n2;  // ∂r/∂pl
+  const double l00 = a00 * P.c - a01 * P.s, l01 = a00 * P.s + a01 * P.c;
+  const double JA[1][3] = {{-l00, -l01, 1.0}};
+  const double JB[1][2] = {{l00, l01}};
+  store_whitened_vec<1>(W, rr, r);
+  store_whitened<1, 3>(W, JA, Ja);
+  store_whitened<1, 2>(W, JB, Jb);
+}
 __device__ __forceinline__ void lin_row_pose3pose3(const double* mu, const double* W, const double* xa, const double* xb,
                                  double* r, double* Ja, double* Jb) {
   Se3 P, Q; se3_from_coords(xa, P); se3_from_coords(xb, Q);
@@ -167,6 +184,7 @@ __host__ inline bool lin_dims(int kind, LinDims& d) {
     case ROME_FACTOR_PRIORPOINT2: d = {2, 2, 2, 0}; return true;
     case ROME_FACTOR_POSE3POSE3: d = {6, 6, 6, 6}; return true;
     case ROME_FACTOR_PRIORPOSE3: d = {6, 6, 6, 0}; return true;
+    case ROME_FACTOR_POSE2POINT2BEARING: d = {1, 1, 3, 2}; return true;
     default: return false;
   }
 }
@@ -208,6 +226,7 @@ __global__ void __launch_bounds__(64) k_lin(int F, const double* mu, const doubl
     else if constexpr (KIND == ROME_FACTOR_POSE2POSE2) lin_row_pose2pose2(m_, w_, a_, b_, r_, ja, jb);
     else if constexpr (KIND == ROME_FACTOR_POSE2POINT2BR) lin_row_bearingrange(m_, w_, a_, b_, r_, ja, jb);
     else if constexpr (KIND == ROME_FACTOR_POSE3POSE3) lin_row_pose3pose3(m_, w_, a_, b_, r_, ja, jb);
+    else if constexpr (KIND == ROME_FACTOR_POSE2POINT2BEARING) lin_row_bearing(m_, w_, a_, b_, r_, ja, jb);
     else lin_row_priorpose3(m_, w_, a_, r_, ja);
   }
   __syncthreads();
@@ -226,6 +245,7 @@ hipError_t launch_linearize(int kind, int F, const double* mu, const double* W, 
     case ROME_FACTOR_POSE2POINT2BR: hipLaunchKernelGGL((k_lin<ROME_FACTOR_POSE2POINT2BR, 2, 2, 3, 2>), g, b, 0, s, F, mu, W, xa, xb, r, Ja, Jb); break;
     case ROME_FACTOR_POSE3POSE3: hipLaunchKernelGGL((k_lin<ROME_FACTOR_POSE3POSE3, 6, 6, 6, 6>), g, b, 0, s, F, mu, W, xa, xb, r, Ja, Jb); break;
     case ROME_FACTOR_PRIORPOSE3: hipLaunchKernelGGL((k_lin<ROME_FACTOR_PRIORPOSE3, 6, 6, 6, 0>), g, b, 0, s, F, mu, W, xa, xb, r, Ja, Jb); break;
+    case ROME_FACTOR_POSE2POINT2BEARING: hipLaunchKernelGGL((k_lin<ROME_FACTOR_POSE2POINT2BEARING, 1, 1, 3, 2>), g, b, 0, s, F, mu, W, xa, xb, r, Ja, Jb); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

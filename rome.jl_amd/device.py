@@ -153,6 +153,16 @@ class DeviceGraph:
                                                     ("pprng0", 0, self.STREAM_PPRNG0, Pose2, Point2, rp["pose"], rp["point"])):
                 add(name, "rome_conv_pose2point2range_dev", vf, vt, d, stream, tg, mu, sigma, rows4=np.stack([fac, col(d, F), fx, tg], axis=1), nh=nh)
             self.tab["pprng"] = dict(F=F)
+        # bearing-only factors (Bearing2D.jl): behind the range families; L = the [F][1] bearing sigmas
+        pb = getattr(pk, "pbear", None)
+        if pb is not None and pb["F"]:
+            F = pb["F"]
+            fac = np.arange(F, dtype=np.int32)
+            mu, sigma, nh = t(pb["mu"], f64), t(pb["sigma"], f64), dev(nh_or_none(pb["nh"]), f64)
+            for name, d, stream, vf, vt, fx, tg in (("pb1", 1, self.STREAM_PB1, Point2, Pose2, pb["point"], pb["pose"]),
+                                                    ("pb0", 0, self.STREAM_PB0, Pose2, Point2, pb["pose"], pb["point"])):
+                add(name, "rome_conv_pose2point2bearing_dev", vf, vt, d, stream, tg, mu, sigma, rows4=np.stack([fac, col(d, F), fx, tg], axis=1), nh=nh)
+            self.tab["pbear"] = dict(F=F)
         sampler("prior2", "rome_sample_priorpose2_dev", Pose2, None, pk.prior2)
         sampler("prior3", "rome_sample_priorpose3_dev", Pose3, None, pk.prior3)
 
@@ -308,6 +318,12 @@ class DeviceGraph:
     STREAM_P2P2, STREAM_BR1, STREAM_BR0, STREAM_PROD2, STREAM_PRODL, STREAM_P3P3, STREAM_PROD3, STREAM_PRIORPT2 = \
         0, 1 << 28, 2 << 28, 3 << 28, 4 << 28, 5 << 28, 6 << 28, 7 << 28
     STREAM_P2RNG, STREAM_PPRNG1, STREAM_PPRNG0 = 8 << 28, 9 << 28, 10 << 28   # range factors (Point2Point2Range, Pose2Point2Range dir 1 / 0)
+
+    STREAM_PB1, STREAM_PB0 = 11 << 28, 12 << 28   # bearing-only factor (Pose2Point2Bearing dir 1 / 0)
+
+    def has_bearing(self):
+        """does the graph hold bearing-only factors (served by conv_step / solve only: not by the multi-rank drivers)"""
+        return "pbear" in self.tab
 
     def has_range(self):
         """does the graph hold range-only factors (served by conv_step / solve only: not by the multi-rank drivers)"""
@@ -504,6 +520,11 @@ class DeviceGraph:
     def sweep_pose2point2range(self, opts, direction, out=None, noise=None, status=None):
         """direction 0: poses -> landmark proposals [F, 2, N]; 1: landmarks -> pose proposals [F, 3, N] ((x, y) only, headings kept)."""
         return self._sweep(self.fams["pprng0" if direction == 0 else "pprng1"], opts, out, noise, status)
+
+    def sweep_pose2point2bearing(self, opts, direction, out=None, noise=None, status=None):
+        """direction 0: poses -> landmark proposals [F, 2, N] (on the sighting rays); 1: landmarks -> pose proposals [F, 3, N]
+        (translations kept, headings turned to the bearing)."""
+        return self._sweep(self.fams["pb0" if direction == 0 else "pb1"], opts, out, noise, status)
 
     def sample_priors(self, opts, kind="prior2", out=None, noise=None):
         return self._sweep(self.fams[kind], opts, out, noise)

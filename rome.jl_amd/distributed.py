@@ -19,6 +19,8 @@ def _refuse_range_tables(dg, where):
     if getattr(dg, "has_range", None) is not None and dg.has_range():
         names = [n for n, k in (("Point2Point2Range", "p2rng"), ("Pose2Point2Range", "pprng")) if k in dg.tab]
         raise TypeError("%s: %s factors are not supported by the multi-rank drivers" % (where, " / ".join(names)))
+    if getattr(dg, "has_bearing", None) is not None and dg.has_bearing():
+        raise TypeError("%s: Pose2Point2Bearing factors are not supported by the multi-rank drivers" % where)
 
 
 def shard_range(n_items, world, rank):

@@ -7,6 +7,7 @@ Same names and argument meaning as the reference (paths relative to the RoME.jl 
   Pose2Point2BearingRange(bearing, range)                    src/factors/BearingRange2D.jl:10-13
   Pose3Pose3(Z), PriorPose3(Z)                               src/factors/Pose3Pose3.jl:9-11, Pose3D.jl:8-10
   Point2Point2Range(Z), Pose2Point2Range(Z)                 src/factors/Range2D.jl:8-17, 40-54
+  Pose2Point2Bearing(Z)                                      src/factors/Bearing2D.jl:10-32
   getMeasurementParametric(::Pose2Point2BearingRange)        src/factors/BearingRange2D.jl:30-37
   Packed* <-> factor converters                              src/factors/Pose2D.jl:76-84 etc.
 These objects only hold the measurement model; all arithmetic is done by the HIP library.
@@ -190,6 +191,20 @@ class Pose2Point2Range(_RelativeFactor):
         self.Z = Z
 
 
+class Pose2Point2Bearing(_RelativeFactor):
+    """Bearing from a `Pose2` to a `Point2` and no distance (src/factors/Bearing2D.jl:10-32): r = sym_rem(b − atan2(pl)),
+    pl = R(θp)ᵀ (l − p.t) over [p, l].  Z is a `Normal` or a `Uniform` belief of the bearing (default Normal(), :15).  One bearing
+    leaves the landmark on a ray from the pose and the pose on a two-parameter family: the convolution keeps the start point's
+    distance (landmark) or translation (pose) and every solver runs the inflation cycles."""
+    variable_types = (Pose2, Point2)
+
+    def __init__(self, Z=None):
+        Z = Normal() if Z is None else Z
+        if not isinstance(Z, (Normal, Uniform)):
+            raise TypeError("Pose2Point2Bearing: this build supports a Normal / Uniform bearing belief, got %s" % type(Z).__name__)
+        self.Z = Z
+
+
 RANGE_FACTORS = (Point2Point2Range, Pose2Point2Range)
 
 
@@ -201,8 +216,20 @@ def refuse_range(factors, where):
                             % (where, type(f).__name__))
 
 
+def refuse_bearing(factors, where):
+    """TypeError naming the first bearing-only factor in `factors` (the paths that refuse range factors refuse these too)."""
+    for f in factors:
+        if isinstance(f, Pose2Point2Bearing):
+            raise TypeError("%s: Pose2Point2Bearing factors are not supported here (solveGraph / approxConv / solveGraphParametric "
+                            "serve bearing-only factors)" % where)
+
+
 def getMeasurementParametric(f):
     """(μ, iΣ) as IIF.getMeasurementParametric; BearingRange override at BearingRange2D.jl:30-37."""
+    if isinstance(f, Pose2Point2Bearing):
+        if not isinstance(f.Z, Normal):
+            raise TypeError("getMeasurementParametric(::Pose2Point2Bearing{<:Normal}) only")
+        return np.array([f.Z.mu]), np.array([[1.0 / f.Z.sigma ** 2]])
     if isinstance(f, Pose2Point2BearingRange):
         if not isinstance(f.bearing, Normal) or not isinstance(f.range, Normal):
             raise TypeError("getMeasurementParametric(::Pose2Point2BearingRange{<:Normal,<:Normal}) only (BearingRange2D.jl:30)")
@@ -240,7 +267,8 @@ def unpack_factor(d):
     if t == "Pose2Point2BearingRange":
         return Pose2Point2BearingRange(_unpack_belief(d["bearstr"]), _unpack_belief(d["rangstr"]))
     cls = {"Pose2Pose2": Pose2Pose2, "PriorPose2": PriorPose2, "Pose3Pose3": Pose3Pose3, "PriorPose3": PriorPose3,
-           "PriorPoint2": PriorPoint2, "Point2Point2Range": Point2Point2Range, "Pose2Point2Range": Pose2Point2Range}[t]
+           "PriorPoint2": PriorPoint2, "Point2Point2Range": Point2Point2Range, "Pose2Point2Range": Pose2Point2Range,
+           "Pose2Point2Bearing": Pose2Point2Bearing}[t]   # PackedPose2Point2Bearing: Z (Bearing2D.jl:36-45)
     return cls(_unpack_belief(d["Z"]))
 
 

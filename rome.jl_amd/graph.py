@@ -13,7 +13,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .factors import (MvNormal, Normal, Uniform, Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange,
-                      Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range)
+                      Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing)
 
 
 @_contextlib.contextmanager
@@ -452,7 +452,7 @@ class PackedGraph:
         for l, t in fg.variables.items():
             self.index[l] = len(self.labels[t])
             self.labels[t].append(l)
-        p2, br, p3, pr2, pr3, prpt, p2r, ppr = [], [], [], [], [], [], [], []
+        p2, br, p3, pr2, pr3, prpt, p2r, ppr, pb = [], [], [], [], [], [], [], [], []
         nullh = getattr(fg, "nullhypo", {})
         for flabel, labels, f in fg.factors:
             ids = [self.index[l] for l in labels]
@@ -464,6 +464,7 @@ class PackedGraph:
             elif isinstance(f, PriorPoint2): prpt.append((ids, f, flabel))
             elif isinstance(f, Point2Point2Range): p2r.append((ids, f, flabel))
             elif isinstance(f, Pose2Point2Range): ppr.append((ids, f, flabel))
+            elif isinstance(f, Pose2Point2Bearing): pb.append((ids, f, flabel))
             else: raise TypeError("factor type %s is outside the hot path" % type(f).__name__)
 
         def rel_tables(items, d):
@@ -521,6 +522,7 @@ class PackedGraph:
 
         self.p2rng = range_tables(p2r, "from", "to")      # Point2Point2Range over [xi, lm]
         self.pprng = range_tables(ppr, "pose", "point")   # Pose2Point2Range over [x, lm]
+        self.pbear = range_tables(pb, "pose", "point")    # Pose2Point2Bearing over [p, l] (Bearing2D.jl): one bearing belief per factor
 
     @classmethod
     def from_pose2_tables(cls, N, n_poses, mu, cov, var_from, var_to, prior_mu=None, prior_cov=None, prior_var=None):
@@ -546,6 +548,7 @@ class PackedGraph:
         self.priorpt2 = dict(F=0, mu=np.zeros((0, 2)), cov=np.zeros((0, 2, 2)), var=np.zeros(0, np.int32), labels=[])
         self.p2rng = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "from": z32, "to": z32, "nh": np.zeros(0), "labels": []}
         self.pprng = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "pose": z32, "point": z32, "nh": np.zeros(0), "labels": []}
+        self.pbear = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "pose": z32, "point": z32, "nh": np.zeros(0), "labels": []}
         return self
 
     @staticmethod
@@ -582,6 +585,9 @@ class PackedGraph:
 
     def has_range(self):
         return bool(getattr(self, "p2rng", {"F": 0})["F"] or getattr(self, "pprng", {"F": 0})["F"])
+
+    def has_bearing(self):
+        return bool(getattr(self, "pbear", {"F": 0})["F"])
 
     def beliefs(self, fg, vartype):
         """(V, dim, N) SoA blocks from fg.vals (all variables of the type must be initialised)."""

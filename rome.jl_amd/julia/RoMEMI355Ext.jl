@@ -171,6 +171,30 @@ function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:
   return manikde!(getManifold(getVariableType(dfg, target)), pts)
 end
 
+# ---- bearing-only factor (src/factors/Bearing2D.jl): Pose2Point2Bearing over [p, l].  dir 0 turns each landmark start point onto the
+# sighting ray at its own distance; dir 1 keeps each start pose's translation and turns its heading to the measured bearing ------------
+function conv_pose2point2bearing(fg, f::Pose2Point2Bearing{<:Normal}, fixedpts, u0pts, dir::Integer; solver=1)
+  o = default_opts(fg; solver)
+  μ = Float64[mean(f.Z)]; σ = Float64[std(f.Z)]
+  Tf, Tt = dir == 0 ? (Pose2, Point2) : (Point2, Pose2)
+  fixed = coords(Tf, fixedpts); target = coords(Tt, u0pts)
+  GC.@preserve μ σ fixed target begin
+    check(ccall((:rome_conv_pose2point2bearing, LIB), Cint,
+      (Ptr{Cvoid}, Ref{RomeOpts}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+      ctx().h, o, 1, dir, μ, σ, fixed, C_NULL, target, C_NULL))
+  end
+  points(Tt, target)
+end
+
+function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:Pose2Point2Bearing{<:Normal}}}, target::Symbol,
+                          measurement::AbstractVector=Tuple[]; solveKey::Symbol=:default, kw...)
+  vars = getVariableOrder(fc)
+  dir = vars[2] == target ? 0 : 1
+  other = dir == 0 ? vars[1] : vars[2]
+  pts = conv_pose2point2bearing(dfg, getFactorType(fc), getVal(dfg, other; solveKey), getVal(dfg, target; solveKey), dir)
+  return manikde!(getManifold(getVariableType(dfg, target)), pts)
+end
+
 # ---- Pose3Pose3: coordinates (t, ω) = get_coordinates(M, ϵ, log(M, ϵ, p), DefaultOrthogonalBasis()) ----------
 const M3 = getManifold(Pose3)
 coords(::Type{Pose3}, pts) = reduce(hcat, [get_coordinates(M3, getPointIdentity(M3), log(M3, getPointIdentity(M3), p), DefaultOrthogonalBasis()) for p in pts])
@@ -579,9 +603,9 @@ run!(bp::RomeBlockOpPlan) = check(ccall((:rome_blockop_plan_run, LIB), Cint, (Pt
 synchronize() = check(ccall((:rome_ctx_synchronize, LIB), Cint, (Ptr{Cvoid},), ctx().h))
 
 # ---- parametric path: batched whitened residuals + Jacobians (rome_linearize) ------------------------------
-# kind: 0 PriorPose2, 1 Pose2Pose2, 2 Pose2Point2BearingRange, 3 PriorPoint2, 4 Pose3Pose3, 5 PriorPose3
+# kind: 0 PriorPose2, 1 Pose2Pose2, 2 Pose2Point2BearingRange, 3 PriorPoint2, 4 Pose3Pose3, 5 PriorPose3, 6 Pose2Point2Bearing
 function linearize(kind::Integer, μ::Matrix{Float64}, W::Array{Float64,3}, xa::Matrix{Float64}, xb::Union{Nothing,Matrix{Float64}})
-  dz, dr, da, db = ((3,3,3,0), (3,3,3,3), (2,2,3,2), (2,2,2,0), (6,6,6,6), (6,6,6,0))[kind + 1]
+  dz, dr, da, db = ((3,3,3,0), (3,3,3,3), (2,2,3,2), (2,2,2,0), (6,6,6,6), (6,6,6,0), (1,1,3,2))[kind + 1]
   F = size(μ, 2)                                  # columns = factors (column-major == row-major F x d on the C side)
   r = Matrix{Float64}(undef, dr, F); Ja = Array{Float64}(undef, da, dr, F)
   Jb = db > 0 ? Array{Float64}(undef, db, dr, F) : nothing
@@ -616,6 +640,12 @@ function residual_pose2pose2(z::AbstractMatrix, p::AbstractMatrix, q::AbstractMa
   r = similar(z)
   check(ccall((:rome_residual_pose2pose2, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
               ctx().h, size(z, 2), z, p, q, r))
+  r
+end
+function residual_pose2point2bearing(z::AbstractVector, p::AbstractMatrix, l::AbstractMatrix)   # n bearings, 3 x n poses, 2 x n landmarks
+  r = similar(z)
+  check(ccall((:rome_residual_pose2point2bearing, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              ctx().h, length(z), z, p, l, r))
   r
 end
 

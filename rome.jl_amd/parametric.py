@@ -7,10 +7,11 @@ import numpy as np
 
 from . import _lib, api
 from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3,
-                      PriorPoint2, getMeasurementParametric)
+                      PriorPoint2, Pose2Point2Bearing, getMeasurementParametric)
 
 _KIND = {PriorPose2: _lib.FACTOR_PRIORPOSE2, Pose2Pose2: _lib.FACTOR_POSE2POSE2, Pose2Point2BearingRange: _lib.FACTOR_POSE2POINT2BR,
-         PriorPoint2: _lib.FACTOR_PRIORPOINT2, Pose3Pose3: _lib.FACTOR_POSE3POSE3, PriorPose3: _lib.FACTOR_PRIORPOSE3}
+         PriorPoint2: _lib.FACTOR_PRIORPOINT2, Pose3Pose3: _lib.FACTOR_POSE3POSE3, PriorPose3: _lib.FACTOR_PRIORPOSE3,
+         Pose2Point2Bearing: _lib.FACTOR_POSE2POINT2BEARING}
 
 
 def _whitening(info):
@@ -183,7 +184,7 @@ class _Problem:
             if k is None:
                 raise TypeError("factor %s is outside the hot path" % type(f).__name__)
             g = groups.setdefault(k, dict(mu=[], W=[], a=[], b=[], cov=[]))
-            if hasattr(f, "Z"):      # MvNormal factors: μ now, the whitening of the whole group in one batched call below
+            if hasattr(f, "Z") and hasattr(f.Z, "cov"):      # MvNormal factors: μ now, the whitening of the whole group in one batched call below
                 g["mu"].append(f.Z.mu); g["cov"].append(f.Z.cov)
             else:
                 mu, info = getMeasurementParametric(f)
@@ -367,6 +368,9 @@ def solveGraphParametric(fg, init=None, max_iters=100, tol=1e-4, ctx=None, retur
     16-CPU quota spin after each of them while the sequential parts of the factorisation want the cores: 10k helix 6.1 -> 2.4 s"""
     from .factors import refuse_range
     refuse_range([f for _, _, f in fg.factors], "solveGraphParametric")
+    if shard is not None:   # the row-sharded linearisation goes through rome_linearize_dev, which serves kinds 0..5
+        from .factors import refuse_bearing
+        refuse_bearing([f for _, _, f in fg.factors], "solveGraphParametric(shard=...)")
     with _blas_single_thread():
         return _solve_graph_parametric(fg, init, max_iters, tol, ctx, return_cov, verbose, shard, stats, polish)
 

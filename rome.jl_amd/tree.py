@@ -30,7 +30,7 @@ import heapq
 
 import numpy as np
 
-from .factors import refuse_range
+from .factors import refuse_range, refuse_bearing
 
 
 class Clique:
@@ -253,6 +253,7 @@ class TreeSolver:
         then dealt to the ranks by clique -- share up-solve, ONE all-gather of the level's written blocks, one scatter; the block
         operations between levels run on every rank (each holds the whole store)."""
         refuse_range([f for _, _, f in fg.factors], "TreeSolver")
+        refuse_bearing([f for _, _, f in fg.factors], "TreeSolver")
         from .graph import FactorGraph
         if messages not in ("relative", "marginal"):
             raise ValueError("messages must be 'relative' or 'marginal'")
