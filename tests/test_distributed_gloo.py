@@ -343,26 +343,8 @@ def test_target_sharded_sweep_assembles_the_unsharded_table(world):
 
 
 # ------------------------------------------------------------------ row-sharded linearisation of the parametric solver
-def _cpu_linearize(kind, mu, W, xa, xb=None, ctx=None):
-    """CPU stand-in (test infrastructure) for one rank's `rome_linearize` on PriorPose2 / Pose2Pose2 rows: whitened residual and
-    Jacobians in the tangent convention of the solver (x ⊕ δ = (t + δt, θ + δθ))."""
-    sys.path.insert(0, ROOT)
-    from rome_jl_amd import _lib
-    wrap = lambda a: np.arctan2(np.sin(a), np.cos(a))
-    F = len(mu)
-    if kind == _lib.FACTOR_PRIORPOSE2:
-        r = np.stack([mu[:, 0] - xa[:, 0], mu[:, 1] - xa[:, 1], wrap(mu[:, 2] - xa[:, 2])], 1)
-        Ja = np.tile(-np.eye(3), (F, 1, 1)); Jb = None
-    elif kind == _lib.FACTOR_POSE2POSE2:
-        c, s = np.cos(xa[:, 2]), np.sin(xa[:, 2])
-        r = np.stack([xa[:, 0] + c * mu[:, 0] - s * mu[:, 1] - xb[:, 0], xa[:, 1] + s * mu[:, 0] + c * mu[:, 1] - xb[:, 1],
-                      wrap(xa[:, 2] + mu[:, 2] - xb[:, 2])], 1)
-        Ja = np.tile(np.eye(3), (F, 1, 1)); Ja[:, 0, 2] = -s * mu[:, 0] - c * mu[:, 1]; Ja[:, 1, 2] = c * mu[:, 0] - s * mu[:, 1]
-        Jb = np.tile(-np.eye(3), (F, 1, 1))
-    else:
-        raise NotImplementedError(kind)
-    W = np.asarray(W)
-    return np.einsum("fij,fj->fi", W, r), W @ Ja, (None if Jb is None else W @ Jb)
+from lin_ref import np_linearize as _cpu_linearize  # noqa: E402  CPU stand-in (test infrastructure) for one rank's `rome_linearize`:
+# whitened residual and Jacobians in the tangent convention of the solver; one copy, checked against mpmath in test_lin_ref_host.py
 
 
 def _lin_worker(rank, world, port, ret):
