@@ -43,6 +43,22 @@ __device__ __forceinline__ void block_stats(const double* __restrict__ P, int N,
   }
 }
 
+// SE(3) points as (t, unit quaternion): one Exp per point when it is loaded, one Log per pair
+struct Se3Pt { double t[3], q[4]; };
+__device__ __forceinline__ void se3_load(const double* __restrict__ P, int N, int i, Se3Pt& a) {
+  double w[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { a.t[k] = P[k * N + i]; w[k] = P[(3 + k) * N + i]; }
+  quat_exp(w, a.q);
+}
+__device__ __forceinline__ void se3_diff(const Se3Pt& x, const Se3Pt& y, double (&d)[6]) {
+  double e[4];
+  quat_cmul(y.q, x.q, e);
+  quat_log(e, d + 3);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) d[k] = x.t[k] - y.t[k];
+}
+
 template <int D>
 __global__ void __launch_bounds__(64) k_belief_stats(int V, int N, double inv_n, double inv_nm1, const double* __restrict__ bel,
                                                      double* __restrict__ mean, double* __restrict__ sdev) {
@@ -51,18 +67,15 @@ __global__ void __launch_bounds__(64) k_belief_stats(int V, int N, double inv_n,
   const int lane = threadIdx.x;
   const double* P = bel + (size_t)v * D * N;
   if constexpr (D == 6) {
-    // SE(3): translations as above; rotation: d_i = Log(R_0ᵀ R_i), mean = R_0 Exp(mean d)
-    double c0[6], R0[9];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c0[k] = P[k * N];
-    so3_exp(c0 + 3, R0);
+    // SE(3): translations as above; rotation: d_i = Log(R_0ᵀ R_i), mean = R_0 Exp(mean d).  On unit quaternions, as the SE(3) product
+    // does: a matrix logarithm through acos(c) and sqrt(1 − c²) loses 1e-16 / sin²θ of the angle, 1e-10 rad at π − 1e-3.
+    Se3Pt x0; se3_load(P, N, 0, x0);
     double s[12];
 #pragma unroll
     for (int j = 0; j < 12; ++j) s[j] = 0.0;
     for (int i = lane; i < N; i += 64) {
-      double w[3] = {P[3 * N + i], P[4 * N + i], P[5 * N + i]}, R[9], U[9], d[6];
-      so3_exp(w, R); mat3_tmul(R0, R, U); so3_log(U, d + 3);
-      d[0] = P[i] - c0[0]; d[1] = P[N + i] - c0[1]; d[2] = P[2 * N + i] - c0[2];
+      Se3Pt xi; se3_load(P, N, i, xi);
+      double d[6]; se3_diff(xi, x0, d);
 #pragma unroll
       for (int k = 0; k < 6; ++k) { s[2 * k] += d[k]; s[2 * k + 1] += d[k] * d[k]; }
     }
@@ -70,11 +83,11 @@ __global__ void __launch_bounds__(64) k_belief_stats(int V, int N, double inv_n,
     double md[6];
 #pragma unroll
     for (int k = 0; k < 6; ++k) md[k] = s[2 * k] * inv_n;
-    double E[9], Rm[9], wm[3];
-    so3_exp(md + 3, E); mat3_mul(R0, E, Rm); so3_log(Rm, wm);
+    double qe[4], qm[4], wm[3];
+    quat_exp(md + 3, qe); quat_mul(x0.q, qe, qm); quat_log(qm, wm);
     if (lane == 0) {
 #pragma unroll
-      for (int k = 0; k < 3; ++k) { mean[6 * v + k] = c0[k] + md[k]; mean[6 * v + 3 + k] = wm[k]; }
+      for (int k = 0; k < 3; ++k) { mean[6 * v + k] = x0.t[k] + md[k]; mean[6 * v + 3 + k] = wm[k]; }
 #pragma unroll
       for (int k = 0; k < 6; ++k) sdev[6 * v + k] = fast_sqrt(fmax(0.0, (s[2 * k + 1] - s[2 * k] * s[2 * k] * inv_n) * inv_nm1));
     }
@@ -307,20 +320,6 @@ __global__ void __launch_bounds__(64 * kProdWaves) k_product(const ProductArgs a
 // Same definition as k_product (oracle: ro_product_bw, dim 6) with the tangent difference of SE(3):
 //   d(x, y) = (x.t − y.t, Log(R_yᵀ R_x)),   jitter  t += h_t ⊙ ξ_t,  R ← R Exp(h_ω ⊙ ξ_ω).
 // Rotations are unit quaternions from load to store (one Exp per point when it is loaded or staged, one Log per pair).
-struct Se3Pt { double t[3], q[4]; };
-__device__ __forceinline__ void se3_load(const double* __restrict__ P, int N, int i, Se3Pt& a) {
-  double w[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) { a.t[k] = P[k * N + i]; w[k] = P[(3 + k) * N + i]; }
-  quat_exp(w, a.q);
-}
-__device__ __forceinline__ void se3_diff(const Se3Pt& x, const Se3Pt& y, double (&d)[6]) {
-  double e[4];
-  quat_cmul(y.q, x.q, e);
-  quat_log(e, d + 3);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) d[k] = x.t[k] - y.t[k];
-}
 __device__ __forceinline__ void proposal_bandwidth_se3(const ProductArgs& a, int row, const double* __restrict__ P, int N, int lane,
                                                        double (&h)[6]) {
   if (a.prop_bw) {
