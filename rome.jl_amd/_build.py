@@ -10,7 +10,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "librome_mi355.so")
 OBJDIR = os.path.join(HERE, "build")
-UNITS = ("rome_kernels.hip", "rome_parametric.hip", "rome_product.hip", "rome_kde.hip", "rome_gibbs.hip", "rome_capi.hip")
+UNITS = ("rome_kernels.hip", "rome_parametric.hip", "rome_product.hip", "rome_kde.hip", "rome_gibbs.hip", "rome_capi.hip",
+         "rome_capi_clique.hip", "rome_capi_batch.hip")
 SOURCES = [os.path.join(HERE, "csrc", f) for f in UNITS if os.path.exists(os.path.join(HERE, "csrc", f))]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(HERE, "csrc"))) if f.endswith((".h", ".hpp"))] + \
     [os.path.join(os.path.dirname(HERE), "include", "rome_mi355.h")]

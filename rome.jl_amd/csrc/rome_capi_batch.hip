@@ -1,0 +1,207 @@
+// rome_capi_batch.hip -- parametric linearisation, belief statistics, KDE, products and raw device memory behind the extern "C"
+// boundary of librome_mi355.so.  Host-side plumbing only: argument checks, staging through the context's workspaces, launches.
+#include "rome_capi_internal.h"
+
+using namespace rome;
+
+extern "C" {
+
+/* ---- parametric linearisation ---- */
+static bool lin_dims_host(int kind, int& dz, int& dr, int& da, int& db) {
+  switch (kind) {
+    case ROME_FACTOR_PRIORPOSE2: dz = 3; dr = 3; da = 3; db = 0; return true;
+    case ROME_FACTOR_POSE2POSE2: dz = 3; dr = 3; da = 3; db = 3; return true;
+    case ROME_FACTOR_POSE2POINT2BR: dz = 2; dr = 2; da = 3; db = 2; return true;
+    case ROME_FACTOR_PRIORPOINT2: dz = 2; dr = 2; da = 2; db = 0; return true;
+    case ROME_FACTOR_POSE3POSE3: dz = 6; dr = 6; da = 6; db = 6; return true;
+    case ROME_FACTOR_PRIORPOSE3: dz = 6; dr = 6; da = 6; db = 0; return true;
+    case ROME_FACTOR_POSE2POINT2BEARING: dz = 1; dr = 1; da = 3; db = 2; return true;
+    default: return false;
+  }
+}
+int rome_linearize_dev(rome_ctx* c, int32_t kind, int32_t F, const double* mu, const double* W, const double* xa,
+                       const double* xb, double* r, double* Ja, double* Jb) {
+  int dz, dr, da, db;
+  if (!c || F < 0 || !lin_dims_host(kind, dz, dr, da, db)) return ROME_ERR_INVALID_ARG;
+  // the device-pointer entry serves kinds 0..5: its one caller is the row-sharded multi-rank linearisation, which refuses
+  // bearing-only factors by name (the host-pointer entry below serves kind 6)
+  if (kind == ROME_FACTOR_POSE2POINT2BEARING) return ROME_ERR_INVALID_ARG;
+  ROME_BIND(c);
+  if (F > 0 && (!mu || !W || !xa || !r || !Ja || (db > 0 && (!xb || !Jb)))) return ROME_ERR_INVALID_ARG;
+  ROME_HIP(c, launch_linearize(kind, F, mu, W, xa, xb, r, Ja, Jb, c->stream));
+  return ROME_OK;
+}
+int rome_linearize(rome_ctx* c, int32_t kind, int32_t F, const double* mu, const double* W, const double* xa,
+                   const double* xb, double* r, double* Ja, double* Jb) {
+  int dz, dr, da, db;
+  if (!c || F < 0 || !lin_dims_host(kind, dz, dr, da, db)) return ROME_ERR_INVALID_ARG;
+  if (F == 0) return ROME_OK;
+  if (!mu || !W || !xa || !r || !Ja || (db > 0 && (!xb || !Jb))) return ROME_ERR_INVALID_ARG;
+  ROME_HIP(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  void *d_mu, *d_W, *d_xa, *d_xb = nullptr, *d_r, *d_Ja, *d_Jb = nullptr;
+  int rc;
+  const size_t n = (size_t)F;
+  if ((rc = ensure(c, 0, 8 * n * dz, &d_mu))) return rc;
+  if ((rc = ensure(c, 1, 8 * n * dr * dr, &d_W))) return rc;
+  if ((rc = ensure(c, 2, 8 * n * da, &d_xa))) return rc;
+  if ((rc = ensure(c, 4, 8 * n * dr, &d_r))) return rc;
+  if ((rc = ensure(c, 5, 8 * n * dr * da, &d_Ja))) return rc;
+  ROME_HIP(c, hipMemcpyAsync(d_mu, mu, 8 * n * dz, hipMemcpyHostToDevice, s));
+  ROME_HIP(c, hipMemcpyAsync(d_W, W, 8 * n * dr * dr, hipMemcpyHostToDevice, s));
+  ROME_HIP(c, hipMemcpyAsync(d_xa, xa, 8 * n * da, hipMemcpyHostToDevice, s));
+  if (db > 0) {
+    if ((rc = ensure(c, 3, 8 * n * db, &d_xb))) return rc;
+    if ((rc = ensure(c, 6, 8 * n * dr * db, &d_Jb))) return rc;
+    ROME_HIP(c, hipMemcpyAsync(d_xb, xb, 8 * n * db, hipMemcpyHostToDevice, s));
+  }
+  ROME_HIP(c, launch_linearize(kind, F, (const double*)d_mu, (const double*)d_W, (const double*)d_xa,
+                                     (const double*)d_xb, (double*)d_r, (double*)d_Ja, (double*)d_Jb, s));
+  ROME_HIP(c, hipMemcpyAsync(r, d_r, 8 * n * dr, hipMemcpyDeviceToHost, s));
+  ROME_HIP(c, hipMemcpyAsync(Ja, d_Ja, 8 * n * dr * da, hipMemcpyDeviceToHost, s));
+  if (db > 0) ROME_HIP(c, hipMemcpyAsync(Jb, d_Jb, 8 * n * dr * db, hipMemcpyDeviceToHost, s));
+  ROME_HIP(c, hipStreamSynchronize(s));
+  return ROME_OK;
+}
+
+/* ---- belief statistics / product ---- */
+int rome_belief_stats_dev(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, double* mean, double* sd) {
+  if (!c || V < 0 || N < 1 || (dim != 2 && dim != 3 && dim != 6) || (V > 0 && (!bel || !mean || !sd))) return ROME_ERR_INVALID_ARG;
+  ROME_BIND(c);
+  ROME_HIP(c, launch_belief_stats(dim, V, N, bel, mean, sd, c->stream));
+  return ROME_OK;
+}
+int rome_belief_stats(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, double* mean, double* sd) {
+  if (!c || V < 0 || N < 1 || (dim != 2 && dim != 3 && dim != 6) || (V > 0 && (!bel || !mean || !sd))) return ROME_ERR_INVALID_ARG;
+  if (V == 0) return ROME_OK;
+  ROME_HIP(c, hipSetDevice(c->device));
+  void *d_b, *d_m, *d_s; int rc;
+  const size_t nb = 8ull * V * dim * N, nm = 8ull * V * dim;
+  if ((rc = ensure(c, 0, nb, &d_b))) return rc;
+  if ((rc = ensure(c, 1, nm, &d_m))) return rc;
+  if ((rc = ensure(c, 2, nm, &d_s))) return rc;
+  ROME_HIP(c, hipMemcpyAsync(d_b, bel, nb, hipMemcpyHostToDevice, c->stream));
+  ROME_HIP(c, launch_belief_stats(dim, V, N, (const double*)d_b, (double*)d_m, (double*)d_s, c->stream));
+  ROME_HIP(c, hipMemcpyAsync(mean, d_m, nm, hipMemcpyDeviceToHost, c->stream));
+  ROME_HIP(c, hipMemcpyAsync(sd, d_s, nm, hipMemcpyDeviceToHost, c->stream));
+  ROME_HIP(c, hipStreamSynchronize(c->stream));
+  return ROME_OK;
+}
+static int check_kde(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, const double* bw) {
+  if (!c || V < 0 || N < 2 || N > ROME_MAX_PARTICLES_REGISTER || dim < 1 || dim > 6 || (V > 0 && (!bel || !bw))) return ROME_ERR_INVALID_ARG;
+  return ROME_OK;
+}
+int rome_kde_bandwidth_dev(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, uint32_t circular_mask,
+                           double tol_euclid, double tol_circular, double* bw) {
+  int rc = check_kde(c, dim, V, N, bel, bw); if (rc) return rc;
+  ROME_BIND(c);
+  ROME_HIP(c, launch_kde_bandwidth(dim, V, N, bel, circular_mask, tol_euclid > 0 ? tol_euclid : 1e-2,
+                                         tol_circular > 0 ? tol_circular : 1e-6, bw, nullptr, c->stream));
+  return ROME_OK;
+}
+int rome_kde_bandwidth(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, uint32_t circular_mask,
+                       double tol_euclid, double tol_circular, double* bw) {
+  int rc = check_kde(c, dim, V, N, bel, bw); if (rc) return rc;
+  if (V == 0) return ROME_OK;
+  ROME_HIP(c, hipSetDevice(c->device));
+  void *d_b, *d_h;
+  const size_t nb = 8ull * V * dim * N, nh = 8ull * V * dim;
+  if ((rc = ensure(c, 0, nb, &d_b))) return rc;
+  if ((rc = ensure(c, 1, nh, &d_h))) return rc;
+  ROME_HIP(c, hipMemcpyAsync(d_b, bel, nb, hipMemcpyHostToDevice, c->stream));
+  ROME_HIP(c, launch_kde_bandwidth(dim, V, N, (const double*)d_b, circular_mask, tol_euclid > 0 ? tol_euclid : 1e-2,
+                                         tol_circular > 0 ? tol_circular : 1e-6, (double*)d_h, nullptr, c->stream));
+  ROME_HIP(c, hipMemcpyAsync(bw, d_h, nh, hipMemcpyDeviceToHost, c->stream));
+  ROME_HIP(c, hipStreamSynchronize(c->stream));
+  return ROME_OK;
+}
+int rome_kde_max_dev(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, const double* bw, int32_t grid_points,
+                     double* out) {
+  int rc = check_kde(c, dim, V, N, bel, bw); if (rc) return rc;
+  ROME_BIND(c);
+  const int G = grid_points > 0 ? grid_points : 200;
+  if (G < 2 || G > 256 || (V > 0 && !out)) return ROME_ERR_INVALID_ARG;
+  ROME_HIP(c, launch_kde_max(dim, V, N, G, 0.1, bel, bw, out, c->stream));
+  return ROME_OK;
+}
+int rome_kde_max(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, const double* bw, int32_t grid_points, double* out) {
+  int rc = check_kde(c, dim, V, N, bel, bw); if (rc) return rc;
+  const int G = grid_points > 0 ? grid_points : 200;
+  if (G < 2 || G > 256 || (V > 0 && !out)) return ROME_ERR_INVALID_ARG;
+  if (V == 0) return ROME_OK;
+  ROME_HIP(c, hipSetDevice(c->device));
+  void *d_b, *d_h, *d_o;
+  const size_t nb = 8ull * V * dim * N, nh = 8ull * V * dim;
+  if ((rc = ensure(c, 0, nb, &d_b))) return rc;
+  if ((rc = ensure(c, 1, nh, &d_h))) return rc;
+  if ((rc = ensure(c, 2, nh, &d_o))) return rc;
+  ROME_HIP(c, hipMemcpyAsync(d_b, bel, nb, hipMemcpyHostToDevice, c->stream));
+  ROME_HIP(c, hipMemcpyAsync(d_h, bw, nh, hipMemcpyHostToDevice, c->stream));
+  ROME_HIP(c, launch_kde_max(dim, V, N, G, 0.1, (const double*)d_b, (const double*)d_h, (double*)d_o, c->stream));
+  ROME_HIP(c, hipMemcpyAsync(out, d_o, nh, hipMemcpyDeviceToHost, c->stream));
+  ROME_HIP(c, hipStreamSynchronize(c->stream));
+  return ROME_OK;
+}
+int rome_product_bw_dev(rome_ctx* c, const rome_opts* o, int32_t dim, int32_t V, const int32_t* prop_ptr, const int32_t* prop_rows,
+                        const double* prop, const double* prop_bw, const double* bel_in, double* bel_out) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || V < 0 || (dim != 2 && dim != 3 && dim != 6)) return ROME_ERR_INVALID_ARG;
+  ROME_BIND(c);
+  if (V > 0 && (!prop_ptr || !bel_in || !bel_out)) return ROME_ERR_INVALID_ARG;
+  const int N = o->n_particles;
+  if (dim == 6 && N > 256) return ROME_ERR_UNSUPPORTED_N;   /* Pose3 product: points staged in LDS */
+  const double c_n = std::pow(4.0 / ((dim + 2.0) * N), 1.0 / (dim + 4.0));
+  ROME_HIP(c, launch_product(dim, V, N, prop_ptr, prop_rows, prop, prop_bw, bel_in, bel_out, c_n, o->seed, o->stream_offset, c->stream));
+  return ROME_OK;
+}
+int rome_product_dev(rome_ctx* c, const rome_opts* o, int32_t dim, int32_t V, const int32_t* prop_ptr, const int32_t* prop_rows,
+                     const double* prop, const double* bel_in, double* bel_out) {
+  return rome_product_bw_dev(c, o, dim, V, prop_ptr, prop_rows, prop, nullptr, bel_in, bel_out);
+}
+
+int rome_product_gibbs_dev(rome_ctx* c, const rome_opts* o, int32_t dim, int32_t V, const int32_t* prop_ptr, const int32_t* prop_rows,
+                           const double* prop, const double* prop_bw, int32_t n_prop_rows, const double* bel_in, double* bel_out,
+                           uint32_t circular_mask, int32_t gibbs_iters, int32_t max_proposals) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || V < 0 || n_prop_rows < 0 || (dim != 2 && dim != 3 && dim != 6) || max_proposals < 1) return ROME_ERR_INVALID_ARG;
+  if (V > 0 && (!prop_ptr || !prop_rows || !bel_in || !bel_out)) return ROME_ERR_INVALID_ARG;
+  if (n_prop_rows > 0 && (!prop || !prop_bw)) return ROME_ERR_INVALID_ARG;
+  if (o->n_particles > ROME_MAX_PARTICLES_GIBBS) return ROME_ERR_UNSUPPORTED_N;   /* lane = output sample: 128- or 256-thread blocks */
+  ROME_BIND(c);
+  void* trees = nullptr;   /* one ball tree per proposal row, context-owned workspace (grown on demand, kept) */
+  rc = ensure(c, 10, gibbs_workspace_bytes(dim, n_prop_rows, V, o->n_particles), &trees); if (rc) return rc;
+  ROME_HIP(c, launch_product_gibbs(dim, V, o->n_particles, n_prop_rows, prop_ptr, prop_rows, prop, prop_bw, bel_in, bel_out, trees,
+                                         circular_mask, gibbs_iters, max_proposals, o->seed, o->stream_offset, c->stream));
+  return ROME_OK;
+}
+
+/* ---- device memory helpers ---- */
+int rome_dev_alloc(rome_ctx* c, uint64_t bytes, void** out) {
+  if (!c || !out) return ROME_ERR_INVALID_ARG;
+  ROME_HIP(c, hipSetDevice(c->device));
+  ROME_HIP(c, hipMalloc(out, bytes ? bytes : 8));
+  return ROME_OK;
+}
+int rome_dev_free(rome_ctx* c, void* p) {
+  if (!c) return ROME_ERR_INVALID_ARG;
+  ROME_BIND(c);
+  DevBuf b; b.p = p;   // (adopted for the one release)
+  ROME_HIP(c, b.release());
+  return ROME_OK;
+}
+int rome_dev_upload(rome_ctx* c, void* dst, const void* src, uint64_t bytes) {
+  if (!c || (bytes && (!dst || !src))) return ROME_ERR_INVALID_ARG;
+  ROME_BIND(c);
+  ROME_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+  ROME_HIP(c, hipStreamSynchronize(c->stream));
+  return ROME_OK;
+}
+int rome_dev_download(rome_ctx* c, void* dst, const void* src, uint64_t bytes) {
+  if (!c || (bytes && (!dst || !src))) return ROME_ERR_INVALID_ARG;
+  ROME_BIND(c);
+  ROME_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+  ROME_HIP(c, hipStreamSynchronize(c->stream));
+  return ROME_OK;
+}
+
+}  // extern "C"
