@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define ROME_MI355_VERSION 122 /* 0.1.22: ROME_BLOCKOP_COMPOSE / MIX, rome_blockop_plan_create_ex (round 6: solveTree as variable elimination in relative-factor algebra); rome_ctx_set_stream orders streams by event.  0.1.21: store-resident messages (smsg_*) in rome_clique_upsolve_host (a tree level reads its children's separator beliefs from HBM); multihypo / nullhypo / stream-id columns in rome_clique_host; rome_store + rome_upsolve_plan
+#define ROME_MI355_VERSION 122 /* 0.1.22 (appended since, the number unchanged: ROME_BLOCKOP_COMPOSE on Pose3 blocks, ROME_BLOCKOP_ANCHOR_MEAN, p3p3_meas at the end of rome_clique_host -- solveTree as variable elimination on Pose3 graphs): ROME_BLOCKOP_COMPOSE / MIX, rome_blockop_plan_create_ex (round 6: solveTree as variable elimination in relative-factor algebra); rome_ctx_set_stream orders streams by event.  0.1.21: store-resident messages (smsg_*) in rome_clique_upsolve_host (a tree level reads its children's separator beliefs from HBM); multihypo / nullhypo / stream-id columns in rome_clique_host; rome_store + rome_upsolve_plan
                                  * (device-resident clique up-solves: beliefs stay in HBM across frontiers) */
 
 enum {
@@ -335,6 +335,10 @@ typedef struct rome_clique_host {
   /* the same for bearing-range rows: br1_meas / br0_meas [rows] = POINT2 block whose N (x, y) entries are the row's (bearing, range)
    * samples -- the relative message pose -> landmark of a child clique (ROME_BLOCKOP_RELATIVE with a Point2 source) */
   const int32_t* br1_meas; const int32_t* br0_meas;
+  /* the same for Pose3Pose3 rows (optional [n_p3p3], rome_upsolve_plan only): p3p3_meas[r] >= 0 = POSE3 block whose N entries (t, omega) are
+   * the row's six tangent coordinates -- exp_eps is uncoupled here (p.t + R_p z_t, R_p Exp(z_omega)), so the coordinates of a relative pose
+   * (ROME_BLOCKOP_COMPOSE on Pose3 blocks) are what the row consumes.  -1: an ordinary row. */
+  const int32_t* p3p3_meas;
 } rome_clique_host;
 int rome_clique_proposals(rome_ctx*, const rome_opts*, const rome_clique_host*);
 
@@ -450,24 +454,31 @@ void rome_upsolve_plan_destroy(rome_upsolve_plan*);
  *                          coordinates of ref^-1 * s_i for the N particles s_i of Pose2 block b[k] (what a p2p2_meas row consumes);
  *                          type[k] = 1: Point2 block dst[k] <- (bearing, range) of the N landmarks of Point2 block b[k] seen from ref
  *                          (what a br1_meas / br0_meas row consumes)
- *   ROME_BLOCKOP_COMPOSE   Pose2 blocks of relative-pose samples, particle by particle: dst[k]_i <- A'_i (+) B'_i, A' = a[k] or its
- *                          inverse (type[k] |= ROME_BLOCKOP_INVERT_A), B' likewise.  Eliminating a variable v of a pose graph with
+ *   ROME_BLOCKOP_COMPOSE   Pose2 or Pose3 blocks of relative-pose samples (one plan: one type), particle by particle: dst[k]_i <- A'_i (+) B'_i, A' = a[k] or its
+ *                          inverse (type[k] |= ROME_BLOCKOP_INVERT_A), B' likewise.  Pose3 coordinates (t, omega), q = Exp(omega): inverse
+ *                          (-R(q)^T t, conj q), composition (t_a + R(q_a) t_b, q_a * q_b), stored as Log of the w >= 0 representative.  Eliminating a variable v of a pose graph with
  *                          sampled edges z_c = v^-1 c, z_k = v^-1 k leaves c^-1 k = z_c^-1 (+) z_k: the pair marginal of the
  *                          neighbours, exactly (elimination.py: variable elimination in relative-factor algebra)
  *   ROME_BLOCKOP_MIX       pooling of independent passes: particle i of dst[k] <- particle i of a[k] unless i % p == p - 1, with
  *                          p = type[k] >> 8 >= 1: after pass p wrote dst, a = the pool of the p - 1 passes before it -- dst becomes a
  *                          mixture in which every pass holds ~N / p particles (its mean: the running average of the passes)
+ *   ROME_BLOCKOP_ANCHOR_MEAN  block dst[k] <- N copies of the MEAN point of belief a[k].  Pose3: (mean translation, q_m) with
+ *                          q_m = q_0 * Exp(mean_i Log(conj q_0 * q_i)), the mean rome_belief_stats reports -- what a back substitution
+ *                          conditions on (ANCHOR keeps the rotation of particle 0: one noisy sample).  Pose2 / Point2: exactly ANCHOR.
+ * One block runs per entry and nothing orders the entries of a run: the entries of one COMPOSE / MIX plan must be mutually disjoint in
+ * `dst` against every a, b and dst of the plan (no entry may read or write a block another entry writes); the caller guarantees it.
  * type[k] = variable type of entry k (0 Pose2 / 1 Point2 / 2 Pose3; RELATIVE: of b and dst); b may be NULL except for RELATIVE / COMPOSE.
  * Replaces (with smsg_* and p2p2_meas): the up-message channels between cliques of IIF's solveTree! (put!/take! of
  * TreeBelief messages), kept device-resident. */
-enum { ROME_BLOCKOP_COPY = 0, ROME_BLOCKOP_ANCHOR = 1, ROME_BLOCKOP_RELATIVE = 2, ROME_BLOCKOP_COMPOSE = 3, ROME_BLOCKOP_MIX = 4 };
+enum { ROME_BLOCKOP_COPY = 0, ROME_BLOCKOP_ANCHOR = 1, ROME_BLOCKOP_RELATIVE = 2, ROME_BLOCKOP_COMPOSE = 3, ROME_BLOCKOP_MIX = 4,
+       ROME_BLOCKOP_ANCHOR_MEAN = 5 };
 #define ROME_BLOCKOP_INVERT_A 0x100   /* COMPOSE: OR into type[k] -- take the inverse of every particle of block a[k] ... */
 #define ROME_BLOCKOP_INVERT_B 0x200   /* ... of block b[k] */
 typedef struct rome_blockop_plan rome_blockop_plan;
 int  rome_blockop_plan_create(rome_ctx*, rome_store*, int32_t op, int32_t n, const int32_t* type, const int32_t* a, const int32_t* b,
                               const int32_t* dst, rome_blockop_plan** out);
 /* COMPOSE with per-entry inflation: params[2k], params[2k + 1] > 0 scale the deviations of entry k's composed samples about their mean
- * (translation, heading) -- the star-mesh transform of an eliminated star: the edge between two of its legs keeps the composed mean and takes
+ * (translation, heading; Pose3: rotation, q_i' = q_m * Exp(g Log(conj q_m * q_i)) about the mean q_m of ANCHOR_MEAN) -- the star-mesh transform of an eliminated star: the edge between two of its legs keeps the composed mean and takes
  * the variance v_j + v_k + v_j v_k sum_{i != j,k} 1 / v_i.  params = NULL: plain compositions (rome_blockop_plan_create). */
 int  rome_blockop_plan_create_ex(rome_ctx*, rome_store*, int32_t op, int32_t n, const int32_t* type, const int32_t* a, const int32_t* b,
                                  const int32_t* dst, const double* params, rome_blockop_plan** out);

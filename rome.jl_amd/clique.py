@@ -38,7 +38,8 @@ class CliqueHost(C.Structure):
                 ("br0_alt", C.c_void_p), ("br0_hypo_w", C.c_void_p), ("br0_nullhypo", C.c_void_p),
                 ("p3p3_nullhypo", C.c_void_p),
                 ("p2p2_stream", C.c_void_p), ("br1_stream", C.c_void_p), ("br0_stream", C.c_void_p), ("p3p3_stream", C.c_void_p),
-                ("prpt2_stream", C.c_void_p), ("p2p2_meas", C.c_void_p), ("br1_meas", C.c_void_p), ("br0_meas", C.c_void_p)]
+                ("prpt2_stream", C.c_void_p), ("p2p2_meas", C.c_void_p), ("br1_meas", C.c_void_p), ("br0_meas", C.c_void_p),
+                ("p3p3_meas", C.c_void_p)]
 
 
 class SampledPose2Pose2:
@@ -46,6 +47,15 @@ class SampledPose2Pose2:
     accepts any SamplableBelief as `Z`): `meas` = label of the Pose2 block with the tangent coordinates (x, y, theta).  This is what the
     relative up-message of a child clique is to its parent (tree.TreeSolver, messages="relative"); only plans over a store take it."""
     variable_types = (Pose2, Pose2)
+
+    def __init__(self, meas):
+        self.meas = meas
+
+
+class SampledPose3Pose3:
+    """The same for Pose3: `meas` = label of the Pose3 block with the six tangent coordinates (t, omega) of the relative pose (exp_eps is
+    uncoupled here, so the coordinates of a composed relative pose are the tangent coordinates the row consumes)."""
+    variable_types = (Pose3, Pose3)
 
     def __init__(self, meas):
         self.meas = meas
@@ -124,6 +134,13 @@ class CliqueBatch:
                 other = labels[0] if d == 0 else labels[1]
                 fam, meas = "p2p2", (var_index[f.meas] if var_index is not None else -2)   # (-2: no store -- only the oracle-side restatement)
                 row = (fac(fam, "<sampled>", np.zeros(3), np.eye(3)), d, var(other), var(target))
+            elif isinstance(f, SampledPose3Pose3):
+                if mh is not None:
+                    raise TypeError("a sampled-measurement factor carries no multihypo")
+                d = 0 if labels[1] == target else 1
+                other = labels[0] if d == 0 else labels[1]
+                fam, meas = "p3p3", (var_index[f.meas] if var_index is not None else -2)
+                row = (fac(fam, "<sampled>", np.zeros(6), np.eye(6)), d, var(other), var(target))
             elif isinstance(f, SampledBearingRange):
                 if mh is not None:
                     raise TypeError("a sampled-measurement factor carries no multihypo")
@@ -199,7 +216,7 @@ class CliqueBatch:
         q.prpt2_mu, q.prpt2_cov = ptr(np.array(t["prpt2"]["mu"]).reshape(-1, 2)), ptr(np.array(t["prpt2"]["spread"]).reshape(-1, 4))
         q.out_p2p2, q.out_br1, q.out_br0, q.out_p3p3, q.out_prpt2 = (out[f].ctypes.data_as(C.c_void_p) if out[f].size else None
                                                                     for f in ("p2p2", "br1", "br0", "p3p3", "prpt2"))
-        for fam in ("p2p2", "br1", "br0"):
+        for fam in ("p2p2", "br1", "br0", "p3p3"):
             if any(m == -2 for m in self.fam_meas[fam]):
                 raise TypeError("a sampled-measurement factor needs a device-resident store (UpsolvePlan / tree.TreeLevelPlan)")
             if any(m >= 0 for m in self.fam_meas[fam]):

@@ -13,7 +13,8 @@ struct Fam {
   int n; const int32_t* rows4; int F; const double* mu; const double* spread; int dz, nL, dfx, dt; double* out; int vf, vt; int dir_all;
   uint64_t off; int kind; int base;
   const int32_t* alt; const double* hw; const double* nh; const int32_t* sid; int valt;
-  const int32_t* meas;   // per-row block of the measurement samples (Pose2Pose2 rows only), or nullptr
+  const int32_t* meas;   // per-row block of the measurement samples (Pose2Pose2 / bearing-range / Pose3Pose3 rows), or nullptr
+  int vmeas() const { return kind == 1 ? 1 : (kind == 2 ? 2 : 0); }   // variable type of the store array a `meas` entry indexes
 };
 constexpr int NF = 5;
 void make_fams(const rome_clique_host* q, Fam (&fam)[NF]) {
@@ -25,7 +26,7 @@ void make_fams(const rome_clique_host* q, Fam (&fam)[NF]) {
     {q->n_br0, q->br0_rows4, q->f_br, q->br_mu, q->br_sigma, 2, 2, 3, 2, q->out_br0, 0, 1, 0, 2ull << 28, 1, 0,
      q->br0_alt, q->br0_hypo_w, q->br0_nullhypo, q->br0_stream, 1, q->br0_meas},
     {q->n_p3p3, q->p3p3_rows4, q->f_p3p3, q->p3p3_mu, q->p3p3_cov, 6, 21, 6, 6, q->out_p3p3, 2, 2, 0, 5ull << 28, 2, 0,
-     nullptr, nullptr, q->p3p3_nullhypo, q->p3p3_stream, -1, nullptr},
+     nullptr, nullptr, q->p3p3_nullhypo, q->p3p3_stream, -1, q->p3p3_meas},
     {q->n_prpt2, q->prpt2_rows4, q->f_prpt2, q->prpt2_mu, q->prpt2_cov, 2, 3, 2, 2, q->out_prpt2, 1, 1, 0, 7ull << 28, 3, q->n_br0,
      nullptr, nullptr, nullptr, q->prpt2_stream, -1, nullptr}};
   for (int k = 0; k < NF; ++k) fam[k] = f[k];
@@ -42,7 +43,7 @@ int check_fam_rows(const Fam& f, const int (&nv)[3]) {
     } else if (f.alt && f.alt[r] < -1) return ROME_ERR_INVALID_ARG;
     if (f.nh && !(f.nh[r] >= 0.0 && f.nh[r] <= 1.0)) return ROME_ERR_INVALID_ARG;
     if (f.sid && (f.sid[r] < 0 || f.sid[r] >= (1 << 28))) return ROME_ERR_INVALID_ARG;
-    if (f.meas && (f.meas[r] < -1 || f.meas[r] >= nv[f.kind == 1 ? 1 : 0] || (f.meas[r] >= 0 && e[1] == 2))) return ROME_ERR_INVALID_ARG;
+    if (f.meas && (f.meas[r] < -1 || f.meas[r] >= nv[f.vmeas()] || (f.meas[r] >= 0 && e[1] == 2))) return ROME_ERR_INVALID_ARG;
   }
   return ROME_OK;
 }
@@ -169,6 +170,7 @@ struct rome_scatter_plan {
 struct rome_blockop_plan {
   rome_ctx* ctx = nullptr; rome_store* st = nullptr;
   int op = 0, n = 0;
+  int n_lo = 0;  // entries [0, n_lo) run in k_block_ops, [n_lo, n) in k_block_ops_pose3 (COMPOSE on Pose3 blocks: 0; ANCHOR_MEAN: its Pose2 / Point2 entries first)
   DevBuf ent;   // int32 [n][4] = (type, a, b, dst)
   DevBuf prm;   // COMPOSE: double [n][2] = (translation, heading) inflation of the composed deviations, or empty
 };
@@ -431,7 +433,7 @@ int plan_run(rome_upsolve_plan* P, const rome_opts* o, double* mirror_out, int64
         const int k4 = fam_a[i], lo = lo_a[i], hi = hi_a[i];
         const Fam& f = P->fam[k4];
         double* out = P->d_prop[f.vt] + (size_t)(f.base + lo) * f.dt * N;
-        ROME_HIP(c, launch_fam(f, P->fd[k4], o, base, lo, hi, st->bel[f.vf], st->bel[f.vt], out, sx, st->bel[f.kind == 1 ? 1 : 0]));
+        ROME_HIP(c, launch_fam(f, P->fd[k4], o, base, lo, hi, st->bel[f.vf], st->bel[f.vt], out, sx, st->bel[f.vmeas()]));
         if (P->max_k[f.vt] > 1)   // (a plan whose destinations take ONE proposal each -- sampling a graph's measurements, transporting a belief -- multiplies nothing: no manikde!)
           ROME_HIP(c, launch_kde_bandwidth(f.dt, hi - lo, N, out, kCircBw[f.vt], 1e-2, 1e-6, P->d_pbw[f.vt] + (size_t)(f.base + lo) * f.dt, nullptr, sx));
         return ROME_OK;
@@ -590,7 +592,7 @@ int rome_blockop_plan_create(rome_ctx* c, rome_store* st, int32_t op, int32_t n,
 }
 int rome_blockop_plan_create_ex(rome_ctx* c, rome_store* st, int32_t op, int32_t n, const int32_t* type, const int32_t* a, const int32_t* b,
                                 const int32_t* dst, const double* params, rome_blockop_plan** out) {
-  if (!c || !st || !out || st->ctx != c || n < 0 || op < ROME_BLOCKOP_COPY || op > ROME_BLOCKOP_MIX) return ROME_ERR_INVALID_ARG;
+  if (!c || !st || !out || st->ctx != c || n < 0 || op < ROME_BLOCKOP_COPY || op > ROME_BLOCKOP_ANCHOR_MEAN) return ROME_ERR_INVALID_ARG;
   if (params && op != ROME_BLOCKOP_COMPOSE) return ROME_ERR_INVALID_ARG;
   if (params) for (int k = 0; k < 2 * n; ++k) if (!(params[k] > 0.0) || !(params[k] < 1e6)) return ROME_ERR_INVALID_ARG;
   if (n > 0 && (!type || !a || !dst || ((op == ROME_BLOCKOP_RELATIVE || op == ROME_BLOCKOP_COMPOSE) && !b))) return ROME_ERR_INVALID_ARG;
@@ -601,13 +603,21 @@ int rome_blockop_plan_create_ex(rome_ctx* c, rome_store* st, int32_t op, int32_t
     if (op != ROME_BLOCKOP_COMPOSE && op != ROME_BLOCKOP_MIX && fl != 0) return ROME_ERR_INVALID_ARG;
     if (op == ROME_BLOCKOP_MIX && (fl < 1 || dst[k] == a[k])) return ROME_ERR_INVALID_ARG;
     if (op == ROME_BLOCKOP_RELATIVE && (t > 1 || b[k] < 0 || b[k] >= st->nv[t] || a[k] >= st->nv[0])) return ROME_ERR_INVALID_ARG;
-    if (op == ROME_BLOCKOP_COMPOSE && (t != 0 || fl > 3 || b[k] < 0 || b[k] >= st->nv[0] || dst[k] == a[k] || dst[k] == b[k])) return ROME_ERR_INVALID_ARG;
-    ent[4 * (size_t)k] = type[k]; ent[4 * (size_t)k + 1] = a[k]; ent[4 * (size_t)k + 2] = b ? b[k] : 0; ent[4 * (size_t)k + 3] = dst[k];
+    // (a COMPOSE plan is all-Pose2 or all-Pose3: a run stays one launch)
+    if (op == ROME_BLOCKOP_COMPOSE && ((t != 0 && t != 2) || t != (type[0] & 0xff) || fl > 3 || b[k] < 0 || b[k] >= st->nv[t] || dst[k] == a[k] || dst[k] == b[k])) return ROME_ERR_INVALID_ARG;
+  }
+  // entries of k_block_ops first, those of k_block_ops_pose3 behind them (the entries of a plan are independent: their order is free)
+  const bool p3_compose = op == ROME_BLOCKOP_COMPOSE && n > 0 && (type[0] & 0xff) == 2;
+  int n_lo = 0;
+  for (int k = 0; k < n; ++k) n_lo += !(p3_compose || (op == ROME_BLOCKOP_ANCHOR_MEAN && (type[k] & 0xff) == 2));
+  for (int k = 0, lo = 0, hi = n_lo; k < n; ++k) {
+    const size_t r = (size_t)((p3_compose || (op == ROME_BLOCKOP_ANCHOR_MEAN && (type[k] & 0xff) == 2)) ? hi++ : lo++);
+    ent[4 * r] = type[k]; ent[4 * r + 1] = a[k]; ent[4 * r + 2] = b ? b[k] : 0; ent[4 * r + 3] = dst[k];
   }
   ROME_BIND(c);
   rome_blockop_plan* B = new (std::nothrow) rome_blockop_plan();
   if (!B) return ROME_ERR_ALLOC;
-  B->ctx = c; B->st = st; B->op = op; B->n = n;
+  B->ctx = c; B->st = st; B->op = op; B->n = n; B->n_lo = n_lo;
   hipError_t e = B->ent.alloc((size_t)n * 16 + 16);
   if (e == hipSuccess) e = hipMemcpy(B->ent.p, ent.data(), (size_t)n * 16 + 16, hipMemcpyHostToDevice);
   if (e == hipSuccess && params && n > 0) e = B->prm.alloc((size_t)n * 16);
@@ -620,7 +630,12 @@ int rome_blockop_plan_run(rome_blockop_plan* B) {
   if (!B) return ROME_ERR_INVALID_ARG;
   rome_ctx* c = B->ctx;
   ROME_BIND(c);
-  ROME_HIP(c, launch_block_ops(B->op, B->n, B->st->N, (const int32_t*)B->ent.p, B->st->bel[0], B->st->bel[1], B->st->bel[2], c->stream, (const double*)B->prm.p));
+  // (ANCHOR_MEAN on Pose2 / Point2 entries IS the anchor of k_block_ops; COMPOSE params belong to one kernel or the other: a plan is one type)
+  ROME_HIP(c, launch_block_ops(B->op == ROME_BLOCKOP_ANCHOR_MEAN ? ROME_BLOCKOP_ANCHOR : B->op, B->n_lo, B->st->N, (const int32_t*)B->ent.p, B->st->bel[0],
+                               B->st->bel[1], B->st->bel[2], c->stream, (const double*)B->prm.p));
+  if (B->n > B->n_lo)
+    ROME_HIP(c, launch_block_ops_pose3(B->op, B->n - B->n_lo, B->st->N, (const int32_t*)B->ent.p + 4 * (size_t)B->n_lo, B->st->bel[2], c->stream,
+                                       (const double*)B->prm.p));
   return ROME_OK;
 }
 void rome_blockop_plan_destroy(rome_blockop_plan* B) {

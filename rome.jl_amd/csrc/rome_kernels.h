@@ -97,5 +97,7 @@ hipError_t launch_scatter_blocks(int n, int N, const int32_t* ent /*[n][4]*/, co
 
 // block operations inside a store (include/rome_mi355.h ROME_BLOCKOP_*): entry k = (type, a, b, dst); one 256-thread block per entry
 hipError_t launch_block_ops(int op, int n, int N, const int32_t* ent /*[n][4]*/, double* st2, double* st_pt, double* st3, hipStream_t s, const double* prm /*[n][2] or NULL*/ = nullptr);
+// the same launch shape on Pose3 blocks: op = ROME_BLOCKOP_COMPOSE (every entry Pose3) or ROME_BLOCKOP_ANCHOR_MEAN (its Pose3 entries)
+hipError_t launch_block_ops_pose3(int op, int n, int N, const int32_t* ent /*[n][4]*/, double* st3, hipStream_t s, const double* prm /*[n][2] or NULL*/ = nullptr);
 
 }  // namespace rome

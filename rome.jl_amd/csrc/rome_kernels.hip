@@ -2001,6 +2001,109 @@ hipError_t launch_block_ops(int op, int n, int N, const int32_t* ent, double* st
   return hipGetLastError();
 }
 
+// ---- block operations on POSE3 blocks (compose / mean anchor): a kernel of its own with the launch shape of k_block_ops -- one 256-thread
+//      block per entry (type | flags << 8, a, b, dst), particles strided by 256.  Store coordinates (t, ω); the rotation is the unit
+//      quaternion Exp(ω) from load to store (quat_log: the w >= 0 representative, θ = π snap).
+__device__ __forceinline__ void p3_load(const double* P, int N, int q, double (&t)[3], double (&r)[4]) {
+  double w[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { t[k] = P[(size_t)k * N + q]; w[k] = P[(size_t)(3 + k) * N + q]; }
+  quat_exp(w, r);
+}
+__device__ __forceinline__ void p3_invert(double (&t)[3], double (&r)[4]) {   // (t, q) -> (-R(q)ᵀ t, conj q)
+  r[1] = -r[1]; r[2] = -r[2]; r[3] = -r[3];
+  double u[3];
+  quat_rot(r, t, u);
+  t[0] = -u[0]; t[1] = -u[1]; t[2] = -u[2];
+}
+// the mean point of a Pose3 block: mean translation; rotation q_m = q_0 ⊗ Exp(mean_i Log(conj q_0 ⊗ q_i)) (k_belief_stats, D == 6).
+// Sums in a fixed order (lane partials -> LDS tree) so that the result does not depend on scheduling.  Every thread of the block calls it.
+__device__ __forceinline__ void p3_block_mean(const double* P, int N, int i, double (*red)[256], double (&tm)[3], double (&qm)[4]) {
+  double t0[3], q0[4];
+  p3_load(P, N, 0, t0, q0);
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  for (int q = i; q < N; q += 256) {
+    double t[3], r[4], e[4], d[3];
+    p3_load(P, N, q, t, r);
+    quat_cmul(q0, r, e);
+    quat_log(e, d);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { acc[k] += t[k]; acc[3 + k] += d[k]; }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) red[k][i] = acc[k];
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (i < w) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) red[k][i] += red[k][i + w];
+    }
+    __syncthreads();
+  }
+  const double inv = 1.0 / (double)N;
+  double md[3], qe[4];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { tm[k] = red[k][0] * inv; md[k] = red[3 + k][0] * inv; }
+  quat_exp(md, qe);
+  quat_mul(q0, qe, qm);
+}
+__global__ void __launch_bounds__(256) k_block_ops_pose3(int op, int N, const int4* __restrict__ ent, double* d3, const double* __restrict__ prm) {
+  const int4 e = ent[blockIdx.x];
+  const int flags = e.x >> 8;   // (compose: bit 0 = take A^-1, bit 1 = take B^-1)
+  const double* A = d3 + (size_t)e.y * 6 * N;
+  double* D = d3 + (size_t)e.w * 6 * N;
+  const int i = threadIdx.x;
+  __shared__ double red[6][256];
+  double tm[3], qm[4];
+  if (op == 5) {   // mean anchor: N copies of (mean translation, q_m)
+    p3_block_mean(A, N, i, red, tm, qm);
+    double wm[3];
+    quat_log(qm, wm);
+    for (int q = i; q < N; q += 256) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { D[(size_t)k * N + q] = tm[k]; D[(size_t)(3 + k) * N + q] = wm[k]; }
+    }
+    return;
+  }
+  // compose, particle by particle: D_i = A'_i (+) B'_i = (t_a + R(q_a) t_b, q_a ⊗ q_b) with A' = A or A^-1, B' = B or B^-1
+  const double* B = d3 + (size_t)e.z * 6 * N;
+  for (int q = i; q < N; q += 256) {
+    double ta[3], qa[4], tb[3], qb[4], u[3], qd[4], w[3];
+    p3_load(A, N, q, ta, qa);
+    p3_load(B, N, q, tb, qb);
+    if (flags & 1) p3_invert(ta, qa);
+    if (flags & 2) p3_invert(tb, qb);
+    quat_rot(qa, tb, u);
+    quat_mul(qa, qb, qd);
+    quat_log(qd, w);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { D[(size_t)k * N + q] = ta[k] + u[k]; D[(size_t)(3 + k) * N + q] = w[k]; }
+  }
+  const double gt = prm ? prm[2 * (size_t)blockIdx.x] : 1.0, gth = prm ? prm[2 * (size_t)blockIdx.x + 1] : 1.0;
+  if (gt == 1.0 && gth == 1.0) return;
+  // star-mesh inflation of the deviations of the composed samples about their mean (as k_block_ops does for Pose2): translation by gt,
+  // rotation q_i' = q_m ⊗ Exp(gth · Log(conj q_m ⊗ q_i)).  The mean reads the block as stored.
+  __syncthreads();
+  p3_block_mean(D, N, i, red, tm, qm);
+  for (int q = i; q < N; q += 256) {
+    double t[3], r[4], dq[4], d[3], qe[4], qn[4], w[3];
+    p3_load(D, N, q, t, r);
+    quat_cmul(qm, r, dq);
+    quat_log(dq, d);
+    d[0] *= gth; d[1] *= gth; d[2] *= gth;
+    quat_exp(d, qe);
+    quat_mul(qm, qe, qn);
+    quat_log(qn, w);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { D[(size_t)k * N + q] = tm[k] + gt * (t[k] - tm[k]); D[(size_t)(3 + k) * N + q] = w[k]; }
+  }
+}
+hipError_t launch_block_ops_pose3(int op, int n, int N, const int32_t* ent, double* st3, hipStream_t s, const double* prm) {
+  if (op != 3 && op != 5) return hipErrorInvalidValue;
+  if (n > 0) hipLaunchKernelGGL(k_block_ops_pose3, dim3(n), dim3(256), 0, s, op, N, reinterpret_cast<const int4*>(ent), st3, prm);
+  return hipGetLastError();
+}
+
 static inline dim3 rows_grid(int n) { return dim3((n + 255) / 256); }
 hipError_t launch_residual_pose2pose2(int n, const double* z, const double* p, const double* q, double* r, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(k_residual_pose2pose2, rows_grid(n), dim3(256), 0, s, n, z, p, q, r);

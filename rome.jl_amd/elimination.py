@@ -22,9 +22,16 @@ given its neighbours' VALUES.  For a pose graph both exist in sample form withou
             reference's product.  A belief is therefore the conditional of a pose given its neighbours at their posterior means.
 
 No init pass, no linearisation point, no iteration: a pass is a function of the seed.  `passes > 1` pool the particles of
-independent passes (a belief is then a mixture over passes; its mean the running average).  Scope: Pose2 variables, Pose2Pose2 and
-PriorPose2 factors (BASELINE configs[0-1]); anything else -> tree.TreeSolver.  Structural decisions (which neighbour is tightest, the
-order) are taken on the host from first-order covariances of the edges ("shadow"), once per graph.
+independent passes (a belief is then a mixture over passes; its mean the running average).  Scope: Pose2 variables with Pose2Pose2 and
+PriorPose2 factors (BASELINE configs[0-1]), or Pose3 variables with Pose3Pose3 and PriorPose3 factors (configs[4], SE3:QUAT g2o files);
+no hypotheses, at least one prior, no mixed graphs; anything else -> tree.TreeSolver.  Structural decisions (which neighbour is tightest,
+the order) are taken on the host from first-order covariances of the edges ("shadow"), once per graph.
+
+The algorithm does not know the variable type: what depends on it is one small description per type (`_Pose2Kind`, `_Pose3Kind`) -- the
+variable type of the ZERO / anchor / pool blocks, the sampled factor class, the anchor operation ("anchor" for Pose2; "anchor_mean" for
+Pose3, whose "anchor" keeps the rotation of ONE particle) and the shadow arithmetic.  Pose3 products are not staged (`max_product` splits
+Pose2 products only) and take N <= 256 (ROME_MAX_PARTICLES_PRODUCT_POSE3).  `solveTree(messages="auto")` chooses this form for Pose2
+graphs only, as before (`covers(fg)`; `covers(fg, pose3=True)` is the constructor's predicate).
 
 Reference: examples/ManhattanDatasetBatch.jl:43 (`tree = solveTree!(fg)`); the operations are the hot path's own
 (sampled-measurement rows of `approxConvBelief`, `manikde!`, `manifoldProduct`)."""
@@ -46,16 +53,108 @@ def _comp(a, b):
     return (a[0] + c * b[0] - s * b[1], a[1] + s * b[0] + c * b[1], math.atan2(math.sin(t), math.cos(t)))
 
 
+class _Pose2Kind:
+    """what the elimination needs to know about Pose2: block type, factor classes, anchor op, shadow arithmetic on (x, y, theta)"""
+    name, dim, anchor_op, max_n = "Pose2", 3, "anchor", None
+    inv, comp = staticmethod(_inv), staticmethod(_comp)
+
+    def __init__(self):
+        from .clique import SampledPose2Pose2
+        from .factors import Pose2, Pose2Pose2, PriorPose2
+        self.vt, self.between, self.prior, self.sampled = Pose2, Pose2Pose2, PriorPose2, SampledPose2Pose2
+
+    @staticmethod
+    def shadow(Z):
+        """(mean, vt, vth) of a factor's measurement distribution"""
+        C = Z.cov
+        return ((float(Z.mu[0]), float(Z.mu[1]), float(Z.mu[2])), math.sqrt(max(float(C[0, 0] * C[1, 1] - C[0, 1] * C[1, 0]), 1e-300)), float(C[2, 2]))
+
+    @staticmethod
+    def t2(m):
+        return m[0] * m[0] + m[1] * m[1]
+
+    @staticmethod
+    def spread(vt, vth):
+        return (vt * vt * vth) ** (1.0 / 3.0)
+
+    @staticmethod
+    def merge(seen):
+        """information-weighted mean of parallel edges [(mean, vt, vth)] -> (mean, vt, vth)"""
+        m0 = seen[0][0]
+        it = ith = hx = hy = hth = 0.0
+        for m_, vt_, vth_ in seen:
+            dth = m_[2] - m0[2]
+            dth = math.atan2(math.sin(dth), math.cos(dth))
+            it += 1.0 / vt_; ith += 1.0 / vth_
+            hx += (m_[0] - m0[0]) / vt_; hy += (m_[1] - m0[1]) / vt_; hth += dth / vth_
+        return (m0[0] + hx / it, m0[1] + hy / it, m0[2] + hth / ith), 1.0 / it, 1.0 / ith
+
+
+def _rot(w):
+    from scipy.spatial.transform import Rotation as Rot
+    return Rot.from_rotvec(w).as_matrix()
+
+
+def _rotlog(R):
+    from scipy.spatial.transform import Rotation as Rot
+    return Rot.from_matrix(R).as_rotvec()
+
+
+class _Pose3Kind:
+    """Pose3: the mean relative pose is a (t, R) pair; vt = det(S_tt)^(1/3), vth = det(S_ww)^(1/3) (isotropic variances with the determinant of
+    the block); the lever arm |t|^2 vth enters an inverse / a composition as in 2-D; s = (vt^3 vth^3)^(1/6).  Plain float arithmetic."""
+    name, dim, anchor_op = "Pose3", 6, "anchor_mean"
+
+    def __init__(self):
+        from . import _lib
+        from .clique import SampledPose3Pose3
+        from .factors import Pose3, Pose3Pose3, PriorPose3
+        self.vt, self.between, self.prior, self.sampled = Pose3, Pose3Pose3, PriorPose3, SampledPose3Pose3
+        self.max_n = _lib.MAX_PARTICLES_PRODUCT_POSE3
+
+    @staticmethod
+    def inv(m):
+        return (-(m[1].T @ m[0]), m[1].T)
+
+    @staticmethod
+    def comp(a, b):
+        return (a[0] + a[1] @ b[0], a[1] @ b[1])
+
+    @staticmethod
+    def shadow(Z):
+        mu, C = np.asarray(Z.mu, dtype=float), np.asarray(Z.cov, dtype=float)
+        return ((mu[:3].copy(), _rot(mu[3:])), max(float(np.linalg.det(C[:3, :3])), 1e-300) ** (1.0 / 3.0),
+                max(float(np.linalg.det(C[3:, 3:])), 1e-300) ** (1.0 / 3.0))
+
+    @staticmethod
+    def t2(m):
+        return float(m[0] @ m[0])
+
+    @staticmethod
+    def spread(vt, vth):
+        return (vt ** 3 * vth ** 3) ** (1.0 / 6.0)
+
+    @staticmethod
+    def merge(seen):
+        t0, R0 = seen[0][0]
+        it = ith = 0.0
+        ht, hw = np.zeros(3), np.zeros(3)
+        for (t_, R_), vt_, vth_ in seen:
+            it += 1.0 / vt_; ith += 1.0 / vth_
+            ht += (t_ - t0) / vt_; hw += _rotlog(R0.T @ R_) / vth_
+        return (t0 + ht / it, R0 @ _rot(hw / ith)), 1.0 / it, 1.0 / ith
+
+
 class _Edge:
     """N samples of a^-1 b in store block `block`.  (m, vt, vth) = the SHADOW used for structural decisions only (which neighbour is
     tightest, what an elimination loses): mean relative pose, an isotropic translation variance and the heading variance, propagated to
     first order in plain float arithmetic (the lever arm |t|^2 * vth enters the translation variance of an inverse / a composition);
-    s = (vt^2 vth)^(1/3), the geometric mean of the eigenvalues of diag(vt, vt, vth)."""
-    __slots__ = ("a", "b", "block", "m", "vt", "vth", "s", "_rev")
+    s = (vt^2 vth)^(1/3), the geometric mean of the eigenvalues of diag(vt, vt, vth) (Pose3: of diag(vt x3, vth x3)).  K = the type's kind."""
+    __slots__ = ("a", "b", "block", "m", "vt", "vth", "s", "_rev", "K")
 
-    def __init__(self, a, b, block, m, vt, vth):
-        self.a, self.b, self.block, self.m, self.vt, self.vth = a, b, block, m, vt, vth
-        self.s = (vt * vt * vth) ** (1.0 / 3.0)
+    def __init__(self, a, b, block, m, vt, vth, K):
+        self.a, self.b, self.block, self.m, self.vt, self.vth, self.K = a, b, block, m, vt, vth, K
+        self.s = K.spread(vt, vth)
         self._rev = None
 
     def seen_from(self, v):
@@ -64,7 +163,7 @@ class _Edge:
             return self.m, self.vt, self.vth
         if self._rev is None:
             m = self.m
-            self._rev = (_inv(m), self.vt + (m[0] * m[0] + m[1] * m[1]) * self.vth, self.vth)
+            self._rev = (self.K.inv(m), self.vt + self.K.t2(m) * self.vth, self.vth)
         return self._rev
 
 
@@ -72,11 +171,16 @@ class RelativeEliminationSolver:
     """interface of tree.TreeSolver (upload / solve / download / stats / store); backend as there (device by default)"""
 
     def __init__(self, fg, backend=None, ctx=None, max_product=8, shard=None, loss_slack=1e9, loss_factor=1.0, priors_last=1, order_seed=0, structures=1, centre="tight", near_weight=0.0, mesh_max=0):
-        from .factors import Pose2
+        from .factors import Pose3
         from .graph import FactorGraph
-        why = self.covers(fg, why=True)
+        why = self.covers(fg, why=True, pose3=True)
         if why is not True:
-            raise TypeError("messages='elimination' covers Pose2 graphs of Pose2Pose2 / PriorPose2 factors without hypotheses (%s): use messages='relative' / 'marginal'" % why)
+            raise TypeError("messages='elimination' covers Pose2 graphs of Pose2Pose2 / PriorPose2 factors and Pose3 graphs of Pose3Pose3 / PriorPose3 "
+                            "factors, without hypotheses (%s): use messages='relative' / 'marginal'" % why)
+        K = self.kind = _Pose3Kind() if next(iter(fg.variables.values()), None) is Pose3 else _Pose2Kind()
+        if K.max_n is not None and fg.N > K.max_n:
+            raise ValueError("the %s product takes N <= %d particles (ROME_MAX_PARTICLES_PRODUCT_POSE3); fg.N = %d" % (K.name, K.max_n, fg.N))
+        VT = K.vt            # (the one variable type of the graph, of the ZERO / anchor / pool blocks)
         self.fg, self.N, self.messages = fg, fg.N, "elimination"
         self.backend = backend or DeviceBackend(ctx)
         self.max_product = int(max_product or 0)
@@ -89,12 +193,12 @@ class RelativeEliminationSolver:
         U = FactorGraph(fg.N)
         for l, vt in fg.variables.items():
             U.addVariable(l, vt)
-        U.addVariable(ZERO, Pose2)
+        U.addVariable(ZERO, VT)
         self.universe = U
-        self.Pose2 = Pose2
+        self.VT = VT
         for l in list(fg.variables):
-            U.addVariable(l + "^", Pose2)          # anchor block: N copies of the posterior mean
-            U.addVariable(l + "&", Pose2)          # pool block: the mixture over the passes so far (solve(passes > 1))
+            U.addVariable(l + "^", VT)          # anchor block: N copies of the posterior mean
+            U.addVariable(l + "&", VT)          # pool block: the mixture over the passes so far (solve(passes > 1))
         from .graph import gc_paused
         self.structures = max(1, int(structures))
         with gc_paused():     # (~1e6 live small objects, nothing to free: the generation scans cost a third of the build)
@@ -112,7 +216,7 @@ class RelativeEliminationSolver:
         self.schedules = schedules
         t1 = time.perf_counter()
         self.store = self.backend.Store(U)
-        self.store.put(ZERO, np.zeros((3, fg.N)))
+        self.store.put(ZERO, np.zeros((self.kind.dim, fg.N)))
         B = self.backend
         self.shard = shard(self.store) if shard is not None else None
         if self.shard is not None:
@@ -129,9 +233,13 @@ class RelativeEliminationSolver:
         self.build_s = dict(structure=t1 - t0, store_and_plans=time.perf_counter() - t1)
 
     @staticmethod
-    def covers(fg, why=False):
-        """True when the graph is in this solver's scope (else False, or the reason with why=True)"""
-        from .factors import Pose2, Pose2Pose2, PriorPose2
+    def covers(fg, why=False, pose3=False):
+        """True when the graph is in this solver's scope (else False, or the reason with why=True).  pose3=False (what solveTree's
+        messages="auto" asks): the Pose2 scope only; pose3=True (what the constructor asks): an all-Pose3 graph of Pose3Pose3 / PriorPose3
+        factors is in scope too."""
+        from .factors import Pose2, Pose2Pose2, PriorPose2, Pose3, Pose3Pose3, PriorPose3
+        if pose3 and fg.variables and next(iter(fg.variables.values())) is Pose3:
+            Pose2, Pose2Pose2, PriorPose2 = Pose3, Pose3Pose3, PriorPose3
         bad = None
         for l, vt in fg.variables.items():
             if vt is not Pose2:
@@ -193,39 +301,38 @@ class RelativeEliminationSolver:
         return best
 
     def _structure(self, k_struct=0):
-        from .clique import SampledPose2Pose2
-        from .factors import Pose2Pose2, PriorPose2
         from .graph import FactorGraph
-        fg, N, Pose2 = self.fg, self.N, self.Pose2
+        fg, N, VT = self.fg, self.N, self.VT
+        K = self.kind
+        Prior, Sampled, _inv, _comp = K.prior, K.sampled, K.inv, K.comp
         U = self.universe
         n_edge = [0]
 
         def new_block(prefix):
             l = "%s%d.%d~" % (prefix, k_struct, n_edge[0]); n_edge[0] += 1
-            U.addVariable(l, Pose2)
+            U.addVariable(l, VT)
             return l
 
         adj = {v: {} for v in fg.variables}            # v -> {u: [edges]}
         unary = {v: [] for v in fg.variables}          # v -> [blocks of ABSOLUTE samples of v]: priors, and priors transported along edges
         sched = []
         # ---- step 0: the samples of every factor's measurement (a row from the ZERO block: 0 (+) z = z; a prior: its own row), ONE launch chain
-        L = FactorGraph(N); L.addVariable(ZERO, Pose2)
+        L = FactorGraph(N); L.addVariable(ZERO, VT)
         ent = []
         for fl, ls, f in fg.factors:
-            if isinstance(f, PriorPose2):
+            if isinstance(f, Prior):
                 blk = new_block("p")
-                L.addVariable(blk, Pose2)
+                L.addVariable(blk, VT)
                 ent.append((blk, [self._lift(L, fl, 0, "p", [blk], f)]))
                 unary[ls[0]].append(blk)
                 continue
             a, b = ls
             blk = new_block("e")
-            L.addVariable(blk, Pose2)
+            L.addVariable(blk, VT)
             nfl = "s:" + fl
             L.factors.append((nfl, [ZERO, blk], f)); L._findex[nfl] = L.factors[-1]
             ent.append((blk, [nfl]))
-            C = f.Z.cov
-            e = _Edge(a, b, blk, (float(f.Z.mu[0]), float(f.Z.mu[1]), float(f.Z.mu[2])), math.sqrt(max(float(C[0, 0] * C[1, 1] - C[0, 1] * C[1, 0]), 1e-300)), float(C[2, 2]))
+            e = _Edge(a, b, blk, *K.shadow(f.Z), K)
             adj[a].setdefault(b, []).append(e); adj[b].setdefault(a, []).append(e)
         pri = {v for v in fg.variables if unary[v]}
         if not pri:
@@ -259,10 +366,10 @@ class RelativeEliminationSolver:
             rows = []
             for k, blk in enumerate(blocks):
                 if blk not in Lx.variables:
-                    Lx.addVariable(blk, Pose2)
+                    Lx.addVariable(blk, VT)
                 nfl = "g:%s:%d" % (dst, k)
                 labels = [dst, ZERO] if k in flip else [ZERO, dst]
-                Lx.factors.append((nfl, labels, SampledPose2Pose2(blk))); Lx._findex[nfl] = Lx.factors[-1]
+                Lx.factors.append((nfl, labels, Sampled(blk))); Lx._findex[nfl] = Lx.factors[-1]
                 rows.append(nfl)
             return rows
 
@@ -281,7 +388,7 @@ class RelativeEliminationSolver:
                 if not adj[v] and not unary[v]:
                     raise ValueError("variable %s is not connected to a prior" % v)
                 sel.append(v); blocked.add(v); blocked.update(adj[v])
-            Lm = FactorGraph(N); Lm.addVariable(ZERO, Pose2)
+            Lm = FactorGraph(N); Lm.addVariable(ZERO, VT)
             Lt = FactorGraph(N)
             merges, transports, comps, dn = [], [], [], []
             for v in sel:
@@ -289,24 +396,16 @@ class RelativeEliminationSolver:
                 for u, es in adj[v].items():
                     if len(es) > 1:     # parallel edges -> one: product of their samples, all seen from v
                         blk = new_block("m")
-                        Lm.addVariable(blk, Pose2)
-                        m0 = es[0].seen_from(v)[0]
-                        it = ith = hx = hy = hth = 0.0
-                        for e in es:
-                            m_, vt_, vth_ = e.seen_from(v)
-                            dth = m_[2] - m0[2]
-                            dth = math.atan2(math.sin(dth), math.cos(dth))
-                            it += 1.0 / vt_; ith += 1.0 / vth_
-                            hx += (m_[0] - m0[0]) / vt_; hy += (m_[1] - m0[1]) / vt_; hth += dth / vth_
-                        mm = (m0[0] + hx / it, m0[1] + hy / it, m0[2] + hth / ith)
+                        Lm.addVariable(blk, VT)
+                        mm, mvt, mvth = K.merge([e.seen_from(v) for e in es])
                         merges.append((blk, identity_rows(Lm, blk, [e.block for e in es], flip={k for k, e in enumerate(es) if e.a != v})))
                         n_merge += 1
-                        nb[u] = _Edge(v, u, blk, mm, 1.0 / it, 1.0 / ith)
+                        nb[u] = _Edge(v, u, blk, mm, mvt, mvth, K)
                     else:
                         nb[u] = es[0]
                 if len(unary[v]) > 1:   # several absolute beliefs of v -> one
                     blk = new_block("q")
-                    Lm.addVariable(blk, Pose2)
+                    Lm.addVariable(blk, VT)
                     merges.append((blk, identity_rows(Lm, blk, unary[v]))); n_merge += 1
                     unary[v] = [blk]
                 for u in nb:
@@ -322,13 +421,13 @@ class RelativeEliminationSolver:
                         for bi in range(ai + 1, len(us)):
                             j, k = us[ai], us[bi]
                             zj, vtj, vthj = seen[j]; zk, vtk, vthk = seen[k]
-                            zi = _inv(zj); vti = vtj + (zj[0] * zj[0] + zj[1] * zj[1]) * vthj
-                            vt0 = vti + vtk + (zk[0] * zk[0] + zk[1] * zk[1]) * vthj
+                            zi = _inv(zj); vti = vtj + K.t2(zj) * vthj
+                            vt0 = vti + vtk + K.t2(zk) * vthj
                             vth0 = vthj + vthk
                             gt = 1.0 + vtj * vtk * (it_all - 1.0 / vtj - 1.0 / vtk) / (vtj + vtk)
                             gth = 1.0 + vthj * vthk * (ith_all - 1.0 / vthj - 1.0 / vthk) / (vthj + vthk)
                             blk = new_block("c")
-                            e = _Edge(j, k, blk, _comp(zi, zk), vt0 * gt, vth0 * gth)
+                            e = _Edge(j, k, blk, _comp(zi, zk), vt0 * gt, vth0 * gth, K)
                             comps.append((nb[j].block, nb[k].block, blk, nb[j].a == v, nb[k].a != v, math.sqrt(gt), math.sqrt(gth)))
                             adj[j].setdefault(k, []).append(e); adj[k].setdefault(j, []).append(e)
                             n_comp += 1
@@ -341,7 +440,7 @@ class RelativeEliminationSolver:
                             continue
                         zk, vtk, vthk = ek.seen_from(v)
                         blk = new_block("c")
-                        e = _Edge(c, k, blk, _comp(zi, zk), vti + vtk + (zk[0] * zk[0] + zk[1] * zk[1]) * vthi, vthi + vthk)
+                        e = _Edge(c, k, blk, _comp(zi, zk), vti + vtk + K.t2(zk) * vthi, vthi + vthk, K)
                         # c^-1 k = (v^-1 c)^-1 (+) (v^-1 k): invert the block of c when it holds v^-1 c, the block of k when it holds k^-1 v
                         comps.append((nb[c].block, ek.block, blk, nb[c].a == v, ek.a != v))
                         adj[c].setdefault(k, []).append(e); adj[k].setdefault(c, []).append(e)
@@ -350,9 +449,9 @@ class RelativeEliminationSolver:
                         blk, pv, ec = new_block("a"), unary[v][0], nb[c]
                         for l in (blk, pv, ec.block):
                             if l not in Lt.variables:
-                                Lt.addVariable(l, Pose2)
+                                Lt.addVariable(l, VT)
                         nfl = "t:%s" % blk
-                        Lt.factors.append((nfl, [pv, blk] if ec.a == v else [blk, pv], SampledPose2Pose2(ec.block))); Lt._findex[nfl] = Lt.factors[-1]
+                        Lt.factors.append((nfl, [pv, blk] if ec.a == v else [blk, pv], Sampled(ec.block))); Lt._findex[nfl] = Lt.factors[-1]
                         transports.append((blk, [nfl])); unary[c].append(blk); n_transport += 1
                     n_approx += len(nb) > 2
                 dn.append((v, list(nb.items()), list(unary[v])))
@@ -373,25 +472,25 @@ class RelativeEliminationSolver:
             Ld = FactorGraph(N)
             need, ent, sm = [], [], []
             for v, nbs, un in dn:
-                Ld.addVariable(v, Pose2)
+                Ld.addVariable(v, VT)
                 rows = []
                 for u, e in nbs:
                     if u not in anchored:
                         anchored.add(u); need.append((u, anchor(u)))
                     for l in (anchor(u), e.block):
                         if l not in Ld.variables:
-                            Ld.addVariable(l, Pose2)
+                            Ld.addVariable(l, VT)
                     nfl = "d:%s:%s:%s" % (v, u, e.block)
                     labels = [v, anchor(u)] if e.a == v else [anchor(u), v]
-                    Ld.factors.append((nfl, labels, SampledPose2Pose2(e.block))); Ld._findex[nfl] = Ld.factors[-1]
+                    Ld.factors.append((nfl, labels, Sampled(e.block))); Ld._findex[nfl] = Ld.factors[-1]
                     rows.append(nfl)
                 for blk in un:
                     if blk not in Ld.variables:
-                        Ld.addVariable(blk, Pose2)
+                        Ld.addVariable(blk, VT)
                     sm.append((blk, v))
                 ent.append((v, rows))
             if need:
-                sched.append(("anchor", need))
+                sched.append((K.anchor_op, need))
             sched.append(("plan", self._spec(Ld, ent, sm)))
         self.rounds = rounds
         self._stats = dict(rounds=len(rounds), round_sizes=rounds[:16], merges=n_merge, compositions=n_comp, transports=n_transport,

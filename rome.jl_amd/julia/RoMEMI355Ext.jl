@@ -260,6 +260,7 @@ struct RomeCliqueHost            # include/rome_mi355.h: rome_clique_host
   # rome_upsolve_plan only: per-row store block holding the row's N MEASUREMENT samples (-1 = ordinary row): the relative up-message of a
   # child clique as a sampled-measurement factor of its parent (C_NULL = none)
   p2p2_meas::Ptr{Int32}; br1_meas::Ptr{Int32}; br0_meas::Ptr{Int32}
+  p3p3_meas::Ptr{Int32}
 end
 
 const _accelerated = Union{Pose2Pose2, PriorPose2, Pose2Point2BearingRange{<:Normal,<:Normal}, Pose3Pose3, PriorPose3, PriorPoint2}
@@ -336,7 +337,7 @@ _clique_host(t, o2, o1, o0, o3, opt = Float64[], nv = (length(t.vars[Pose2]), le
                  _p(t.alt[:p2p2]), _p(t.hw[:p2p2]), _p(t.nh[:p2p2]), _p(t.alt[:br1]), _p(t.hw[:br1]), _p(t.nh[:br1]),
                  _p(t.alt[:br0]), _p(t.hw[:br0]), _p(t.nh[:br0]), _p(t.nh[:p3p3]),
                  Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL),
-                 Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL))
+                 Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL), Ptr{Int32}(C_NULL))
 _points_opts(dfg, N) = (d0 = default_opts(dfg);
   RomeOpts(Int32(N), d0.solver, d0.max_iters, d0.inflate_cycles, d0.tol, d0.inflation, d0.seed, d0.stream_offset, 2 #=points=#, 0, d0.spread_nh, 0.0))
 
@@ -577,7 +578,7 @@ end
 # marginal c^-1 k = (v^-1 c)^-1 (+) (v^-1 k) of an eliminated pose's neighbours; `inflate` (n x 2: translation, heading) scales the composed
 # deviations about their mean: star-mesh transform) and :mix (pooling of independent passes: types[k] |= p << 8).  Python twin of the
 # elimination driver: rome_jl_amd.elimination.RelativeEliminationSolver.
-const _BLOCKOPS = Dict(:copy => Int32(0), :anchor => Int32(1), :relative => Int32(2), :compose => Int32(3), :mix => Int32(4))
+const _BLOCKOPS = Dict(:copy => Int32(0), :anchor => Int32(1), :relative => Int32(2), :compose => Int32(3), :mix => Int32(4), :anchor_mean => Int32(5))
 function RomeBlockOpPlan(st::RomeStore, op::Symbol, types::AbstractVector{<:Integer}, a::AbstractVector{<:Integer}, b::AbstractVector{<:Integer},
                          dst::AbstractVector{<:Integer}, inflate::AbstractMatrix{Float64})
   ty = Int32.(types); va = Int32.(a); vb = Int32.(b); vd = Int32.(dst)

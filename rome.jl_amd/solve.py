@@ -101,9 +101,11 @@ def solveTree(fg, tree=None, messages="auto", passes=1, seed=0x524F4D45, ctx=Non
     `tree.TreeSolver` of a previous call to re-solve from the current beliefs: plans are reused), up pass + down pass on the device,
     beliefs written back, PPEs set.  messages: "auto" (default) = "elimination" where it applies, else "marginal"; "marginal" = IIF's
     per-variable separator beliefs (the reference's semantics; hexagon windows, landmarks, multihypo, Pose3), "relative" (tree.py: relative
-    messages between the separators of a clique), or "elimination" (elimination.py; Pose2 graphs of Pose2Pose2 / PriorPose2 factors:
+    messages between the separators of a clique), or "elimination" (elimination.py; Pose2 graphs of Pose2Pose2 / PriorPose2 factors, or
+    Pose3 graphs of Pose3Pose3 / PriorPose3 factors with N <= 256; no hypotheses, at least one prior, no mixed graphs:
     variable elimination in relative-factor algebra -- the form that SOLVES a large single-prior pose graph: Manhattan-3500 to 0.4 - 1.2 m
-    of the MAP in one pass from the factors alone, no init pass).
+    of the MAP in one pass from the factors alone, no init pass).  "auto" chooses "elimination" for the Pose2 scope only; a Pose3 graph
+    gets "marginal" unless messages="elimination" is asked for.
     -> the TreeSolver (its store keeps the beliefs on the device; pass it back as `tree=` after adding nothing to the graph)."""
     refuse_range([f for _, _, f in fg.factors], "solveTree")
     refuse_bearing([f for _, _, f in fg.factors], "solveTree")

@@ -749,8 +749,9 @@ class DeviceBackend:
 class BlockOpPlan:
     """block operations inside a DeviceStore (rome_blockop_plan), ONE launch per run:
     "copy" [(source, destination)], "anchor" [(belief, destination)], "relative" [(anchor block, separator block, destination)],
-    "compose" [(a, b, destination, invert a, invert b)], "mix" [(pool, destination, p)]"""
-    OPS = {"copy": 0, "anchor": 1, "relative": 2, "compose": 3, "mix": 4}
+    "compose" [(a, b, destination, invert a, invert b)] (Pose2 or Pose3 blocks, one type per plan), "mix" [(pool, destination, p)],
+    "anchor_mean" [(belief, destination)] (Pose3: mean translation and mean rotation; Pose2 / Point2: as "anchor")"""
+    OPS = {"copy": 0, "anchor": 1, "relative": 2, "compose": 3, "mix": 4, "anchor_mean": 5}
 
     def __init__(self, store, op, entries):
         import ctypes as C
