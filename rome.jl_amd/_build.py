@@ -1,7 +1,8 @@
 """Builds librome_mi355.so (hipcc, gfx950 only) in-tree next to this file.
 
-Every .hip translation unit is compiled to its own object (in parallel: hipcc takes 10-50 s per file) and the
-objects are linked into one shared library; objects are reused when neither their source nor a header changed."""
+Every csrc/*.hip translation unit (the Makefile's rule) is compiled to its own object, in parallel -- hipcc takes 10 s to 1.5 min per
+file on one core, the convolution families of rome_conv.hpp longest -- and the objects are linked into one shared library; objects are
+reused when neither their source nor a header changed."""
 import os
 import shutil
 import subprocess
@@ -10,9 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "librome_mi355.so")
 OBJDIR = os.path.join(HERE, "build")
-UNITS = ("rome_kernels.hip", "rome_parametric.hip", "rome_product.hip", "rome_kde.hip", "rome_gibbs.hip", "rome_capi.hip",
-         "rome_capi_clique.hip", "rome_capi_batch.hip")
-SOURCES = [os.path.join(HERE, "csrc", f) for f in UNITS if os.path.exists(os.path.join(HERE, "csrc", f))]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(HERE, "csrc"))) if f.endswith(".hip")]
 HEADERS = [os.path.join(HERE, "csrc", f) for f in sorted(os.listdir(os.path.join(HERE, "csrc"))) if f.endswith((".h", ".hpp"))] + \
     [os.path.join(os.path.dirname(HERE), "include", "rome_mi355.h")]
 DEPS = SOURCES + HEADERS
@@ -46,7 +45,7 @@ def build(force=False, verbose=False):
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as ex:
         list(ex.map(compile_one, SOURCES))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SO] + [_obj(s) for s in SOURCES]
     if verbose:

@@ -477,6 +477,13 @@ __device__ __forceinline__ double residual_bearing(double b, const Se2& p, doubl
   return sym_rem(b - fast_atan2(ply, plx));
 }
 
+// ‖(dx, dy)‖ from one v_rsq_f64 + two Newton steps (fast_rsqrt), 0 at the origin: the range residuals r = ρ − ‖lm − x‖
+// (src/factors/Range2D.jl:14-17, :51-54) of the range policies and the residual entry point
+__device__ __forceinline__ double range_norm(double dx, double dy) {
+  const double n2 = dx * dx + dy * dy;
+  return n2 > 0.0 ? n2 * fast_rsqrt(n2) : 0.0;
+}
+
 // entropy: u ← u ∘ exp_ϵ(hat(e))
 __device__ __forceinline__ void se2_add_entropy(double (&t)[3], double spread, const double (&u)[3]) {
   const double ex = spread * (u[0] - 0.5), ey = spread * (u[1] - 0.5), et = spread * (u[2] - 0.5);

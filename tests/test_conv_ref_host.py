@@ -23,7 +23,7 @@ def _references():
 
 
 def test_launch_arithmetic_and_every_shape_hits_its_case():
-    src = open(os.path.join(ROOT, "rome.jl_amd", "csrc", "rome_kernels.hip")).read()
+    src = open(os.path.join(ROOT, "rome.jl_amd", "csrc", "rome_conv.hpp")).read()
     assert int(re.search(r"constexpr int kFlatThreads = (\d+);", src).group(1)) == CR.FLAT_THREADS
     assert int(re.search(r"constexpr int kFlatMaxRows = (\d+);", src).group(1)) == CR.FLAT_MAX_ROWS
     assert "lean && a.N >= %d && (a.N + 1) / 2 <= kFlatThreads" % CR.FLAT_MIN_N in src
