@@ -319,11 +319,28 @@ class CliqueUpsolveHost(C.Structure):
 
 
 # ------------------------------------------------------------------------------------------ device-resident store + plans
-class DeviceStore:
+class LibHandle:
+    """An object of the library behind `handle` (set last by the constructor), released through the entry point named by `_destroy`:
+    close() may be called any number of times; collection closes what its owner did not."""
+    handle = _destroy = None
+
+    def close(self):
+        if self.handle:
+            getattr(self._lib, self._destroy)(self.handle); self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceStore(LibHandle):
     """The beliefs of a whole graph resident in HBM across clique up-solves (rome_store): [n][dim][N] SoA blocks per variable type,
     variables numbered per type in the graph's insertion order (`index[label]`).  `wrap=`: {vartype: torch tensor} of caller-owned
     device memory (e.g. DeviceGraph.bel) instead of an allocation of the library's own."""
     TYPES = (Pose2, Point2, Pose3)
+    _destroy = "rome_store_destroy"
 
     def __init__(self, fg, ctx=None, wrap=None, upload=True):
         refuse_range([f for _, _, f in fg.factors], "DeviceStore")
@@ -404,16 +421,6 @@ class DeviceStore:
         _lib.check(self._lib.rome_store_ptr(self.handle, self.TYPES.index(vt), C.byref(p), C.byref(n)), self.ctx.handle)
         return p.value, n.value
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.rome_store_destroy(self.handle); self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def frontier_order(cliques):
     """update order and groups of a frontier of independent cliques: group g = the g-th frontal of every clique"""
@@ -453,51 +460,94 @@ def frontier_pairs(fg, cliques, order, usable=None):
     return pairs
 
 
-def plan_frontier(fg, cliques, share=None, usable=None, var_index=None):
-    """The host-side plan of a frontier up-solve, for the whole frontier or one rank's share of it:
-      order / groups   this share's update list (group g = the g-th frontal of every clique) and `order_all` of the whole frontier
-      pairs            this share's (factor, destination) pairs in update order
-      stream_ids       {(factor, destination): row index within its family in the WHOLE frontier's tables}
-      up_stream        {label: position among the updated variables of its type in the WHOLE frontier}
-    Philox streams are positions in the whole frontier, so the shares of a frontier together draw exactly what the unsharded call
-    draws (partition-independent results).  Independence is checked over the whole frontier on every rank."""
-    cliques = [list(c) for c in cliques]
-    order_all, groups_all = frontier_order(cliques)
-    pairs_all = frontier_pairs(fg, cliques, order_all, usable)
-    full = CliqueBatch(fg, pairs_all, var_index=var_index)
-    sid = {pair: r for pair, (fam, r) in full.rows.items()}
+def upsolve_share(fg, order, groups, owner, pairs, share=None, var_index=None, gibbs_iters=3, product_iters=1, smsgs=(), whole_ids=False):
+    """The description of ONE up-solve plan -- the whole update list (order / groups / owner[k] = clique of entry k; pairs and
+    store-resident messages `smsgs` in update order), or the share of it that the cliques `share` make up:
+      order / groups / pairs / smsgs   the share's entries
+      stream_ids       {(factor, destination): row index within its family in the WHOLE tables}; None for the whole list unless
+                       `whole_ids` asks for them there too.  The draws are the same either way, the kernels are not: the library serves a
+                       table with a `<family>_stream` column by the wave-per-row kernels only (csrc/rome_kernels.h, ConvArgs.row_stream),
+                       so each caller keeps the form it has always passed (frontier plans the column, whole tree levels none)
+      up_stream        {label: position among the updated variables of its type in the WHOLE list}
+      gibbs_iters / product_iters
+    Philox streams are positions in the whole list, so the shares of a frontier or tree level together draw exactly what the unsharded
+    plan draws (partition-independent results)."""
     pos_t, cnt = {}, {Pose2: 0, Point2: 0, Pose3: 0}
-    for l in order_all:
+    for l in order:
         vt = fg.variables[l]; pos_t[l] = cnt[vt]; cnt[vt] += 1
-    mine = set(order_all) if share is None else {l for k in share for l in cliques[k]}
-    return dict(order=[l for l in order_all if l in mine], groups=[g for l, g in zip(order_all, groups_all) if l in mine],
-                pairs=[p for p in pairs_all if p[1] in mine], stream_ids=sid, up_stream=pos_t, order_all=order_all)
+    d = dict(order=list(order), groups=list(groups), pairs=list(pairs), smsgs=list(smsgs), stream_ids=None, up_stream=pos_t,
+             gibbs_iters=gibbs_iters, product_iters=product_iters)
+    if share is not None or whole_ids:
+        d["stream_ids"] = {pair: r for pair, (fam, r) in CliqueBatch(fg, pairs, var_index=var_index).rows.items()}
+    if share is not None:
+        mine = set(share)
+        keep = [k for k in range(len(order)) if owner[k] in mine]
+        oset = {order[k] for k in keep}
+        d.update(order=[order[k] for k in keep], groups=[groups[k] for k in keep], pairs=[p for p in pairs if p[1] in oset],
+                 smsgs=[m for m in smsgs if m[1] in oset])
+    return d
 
 
-class UpsolvePlan:
-    """One clique / frontier up-solve bound to a DeviceStore (rome_upsolve_plan): the validated row tables live on the device, `run`
-    issues only kernel launches on the context's stream -- beliefs never leave HBM.  `cliques`: list of frontal lists (one clique, or
-    a frontier of independent cliques: group g = the g-th frontals).
-    share: indices of the cliques THIS plan updates (a rank's share of the frontier; default all): see plan_frontier.
+def plan_frontier(fg, cliques, share=None, usable=None, var_index=None, gibbs_iters=3, product_iters=1):
+    """`upsolve_share` of a frontier of independent cliques given as frontal lists (group g = the g-th frontal of every clique; the
+    pairs: `frontier_pairs`; stream ids always), plus `order_all`, the update list of the whole frontier.  Independence is checked over
+    the whole frontier on every rank."""
+    cliques = [list(c) for c in cliques]
+    order, groups = frontier_order(cliques)
+    pairs = frontier_pairs(fg, cliques, order, usable)
+    of = {l: k for k, c in enumerate(cliques) for l in c}
+    return dict(upsolve_share(fg, order, groups, [of[l] for l in order], pairs, share, var_index, gibbs_iters, product_iters, whole_ids=True),
+                order_all=order)
+
+
+def plan_level(spec, share=None, var_index=None):
+    """`upsolve_share` of a tree level (levels.LevelSpec); share: positions within the level of the cliques to update"""
+    return upsolve_share(spec.fg, spec.order, spec.groups, spec.owner, spec.pairs, share, var_index, spec.gibbs_iters, 1, spec.smsgs)
+
+
+def fill_upsolve_plan(u, keep, fg, var_index, d, mirror=None, outputs=False):
+    """an `upsolve_share` description over the store numbering `var_index` -> the fields of the CliqueUpsolveHost `u` (their arrays
+    are appended to `keep`) -> (the share's CliqueBatch, result arrays as `_fill_upsolve` returns them)"""
+    order = d["order"]
+    batch = CliqueBatch(fg, d["pairs"], var_index=var_index, stream_ids=d["stream_ids"])
+    for l in order:
+        if l not in batch.vidx:
+            batch.vidx[l] = var_index[l]
+    res = batch._fill_upsolve(u, keep, order, d["gibbs_iters"], d["product_iters"], "sequential", None, d["groups"],
+                              up_stream=[d["up_stream"][l] for l in order],
+                              up_mirror=None if mirror is None else [mirror.get(l, -1) for l in order], outputs=outputs)
+    pos_of = {l: k for k, l in enumerate(order)}
+    for vt, nm in ((Pose2, "pose2"), (Point2, "point2"), (Pose3, "pose3")):      # store-resident messages: (source block, updated entry)
+        ms = [(var_index[s], pos_of[l]) for s, l in d["smsgs"] if fg.variables[l] is vt]
+        setattr(u, "n_smsg_" + nm, len(ms))
+        if ms:
+            a = np.array(ms, dtype=np.int32)
+            src, up = np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1])
+            keep += [src, up]
+            setattr(u, "smsg_%s_src" % nm, src.ctypes.data_as(C.c_void_p)); setattr(u, "smsg_%s_up" % nm, up.ctypes.data_as(C.c_void_p))
+    return batch, res
+
+
+class UpsolvePlan(LibHandle):
+    """One clique / frontier / tree-level up-solve bound to a DeviceStore (rome_upsolve_plan): the validated row tables live on the
+    device, `run` issues only kernel launches on the context's stream -- beliefs never leave HBM.
+    `cliques` = list of frontal lists (one clique, or a frontier of independent cliques: group g = the g-th frontals); the subclass
+    tree.TreeLevelPlan is the same plan built from a levels.LevelSpec (`plan_level`).
+    share: indices of the cliques (positions within the level) THIS plan updates (a rank's share; default all): see upsolve_share.
     mirror: {label: block} of a device send buffer that the new belief of `label` is also written to by the product kernel."""
+    _destroy = "rome_upsolve_plan_destroy"
 
     def __init__(self, store, cliques, share=None, gibbsIters=3, Niter=1, mirror=None, usable=None, outputs=False):
-        self.store, fg = store, store.fg
-        self.ctx, self._lib = store.ctx, _lib.load()
-        fp = plan_frontier(fg, cliques, share, usable, var_index=store.index)
-        order = fp["order"]
-        self.batch = CliqueBatch(fg, fp["pairs"], var_index=store.index, stream_ids=fp["stream_ids"])
-        for l in order:
-            if l not in self.batch.vidx:
-                self.batch.vidx[l] = store.index[l]
-        self.order, self.order_all = order, fp["order_all"]
-        u = CliqueUpsolveHost()
-        keep = []
-        self.res = self.batch._fill_upsolve(u, keep, order, gibbsIters, Niter, "sequential", None, fp["groups"],
-                                            up_stream=[fp["up_stream"][l] for l in order],
-                                            up_mirror=None if mirror is None else [mirror.get(l, -1) for l in order], outputs=outputs)
-        self._keep = keep
-        self.has_mirror = mirror is not None
+        d = plan_frontier(store.fg, cliques, share, usable, store.index, gibbsIters, Niter)
+        self.order_all = d["order_all"]
+        self._create(store, store.fg, d, mirror, outputs)
+
+    def _create(self, store, fg, d, mirror, outputs):
+        """the body of both constructors: the description d (`upsolve_share`) -> row tables -> the library's plan"""
+        self.store, self.ctx, self._lib = store, store.ctx, _lib.load()
+        self.order, self.has_mirror = d["order"], mirror is not None
+        u, keep = CliqueUpsolveHost(), []             # (keep: the host tables, until the library has copied them)
+        self.batch, self.res = fill_upsolve_plan(u, keep, fg, store.index, d, mirror, outputs)
         o = api.make_opts(N=fg.N)
         o.layout = _lib.LAYOUT_SOA
         h = C.c_void_p()
@@ -505,7 +555,7 @@ class UpsolvePlan:
         self.handle = h
 
     def run(self, opts, mirror_out=None, mirror_stride=0):
-        """gibbsIters x {proposals -> manikde! -> product -> in-place write}; asynchronous unless the plan was created with outputs.
+        """gibbs_iters x {proposals -> manikde! -> product -> in-place write}; asynchronous unless the plan was created with outputs.
         mirror_out: the send buffer -- a device pointer (int) or a tensor (its data_ptr())."""
         o = _lib.Opts.from_buffer_copy(opts)
         o.layout = _lib.LAYOUT_SOA
@@ -517,20 +567,11 @@ class UpsolvePlan:
             return {l: (new[k].copy(), bw[k].copy()) for vt, (ls, new, bw) in self.res.items() for k, l in enumerate(ls)}
         return None
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.rome_upsolve_plan_destroy(self.handle); self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ScatterPlan:
+class ScatterPlan(LibHandle):
     """The receive side of a frontier exchange (rome_scatter_plan): block src_block[k] of a device buffer becomes the belief of
     labels[k] in the store -- one launch, index lists uploaded once."""
+    _destroy = "rome_scatter_plan_destroy"
 
     def __init__(self, store, labels, src_blocks, stride=0):
         self.store, self.ctx, self._lib = store, store.ctx, _lib.load()
@@ -551,16 +592,6 @@ class ScatterPlan:
             src_dev = src_dev.data_ptr()
         _lib.check(self._lib.rome_scatter_plan_run(self.handle, C.c_void_p(src_dev)), self.ctx.handle)
         self.store.touched.update(self.labels)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.rome_scatter_plan_destroy(self.handle); self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def upGibbsCliqueFrontier(fg, cliques, gibbsIters=3, Niter=1, solver=_lib.SOLVER_NEWTON, seed=None, ctx=None, setvals=True, **optkw):

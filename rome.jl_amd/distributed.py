@@ -504,7 +504,7 @@ class FrontierShard:
             self.store, cliques, share=shares[self.rank], gibbsIters=gibbsIters, Niter=Niter, mirror=mirror, usable=usable))
 
     def plan_level(self, spec, level_plan_cls):
-        """One level of a Bayes tree (tree.LevelSpec: multi-frontal cliques, separator copies, messages of the children) dealt round-robin
+        """One level of a Bayes tree (levels.LevelSpec: multi-frontal cliques, separator copies, messages of the children) dealt round-robin
         by CLIQUE: a rank solves all updated variables of its cliques; what travels is every block the level writes (frontals, the
         cliques' private copies) -- the next level's messages are read from them on every rank.  level_plan_cls(store, spec, share=,
         mirror=) -> plan (tree.TreeLevelPlan; the CPU tests inject the oracle-backed one)."""

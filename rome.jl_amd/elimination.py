@@ -39,7 +39,8 @@ import math
 
 import numpy as np
 
-from .tree import LevelSpec, ZERO, DeviceBackend, TreeSolver
+from .levels import ZERO, LevelSpec, LevelGraph, LevelSolver, split_products
+from .tree import DeviceBackend
 
 
 def _inv(z):
@@ -167,12 +168,11 @@ class _Edge:
         return self._rev
 
 
-class RelativeEliminationSolver:
+class RelativeEliminationSolver(LevelSolver):
     """interface of tree.TreeSolver (upload / solve / download / stats / store); backend as there (device by default)"""
 
     def __init__(self, fg, backend=None, ctx=None, max_product=8, shard=None, loss_slack=1e9, loss_factor=1.0, priors_last=1, order_seed=0, structures=1, centre="tight", near_weight=0.0, mesh_max=0):
         from .factors import Pose3
-        from .graph import FactorGraph
         why = self.covers(fg, why=True, pose3=True)
         if why is not True:
             raise TypeError("messages='elimination' covers Pose2 graphs of Pose2Pose2 / PriorPose2 factors and Pose3 graphs of Pose3Pose3 / PriorPose3 "
@@ -181,20 +181,16 @@ class RelativeEliminationSolver:
         if K.max_n is not None and fg.N > K.max_n:
             raise ValueError("the %s product takes N <= %d particles (ROME_MAX_PARTICLES_PRODUCT_POSE3); fg.N = %d" % (K.name, K.max_n, fg.N))
         VT = K.vt            # (the one variable type of the graph, of the ZERO / anchor / pool blocks)
-        self.fg, self.N, self.messages = fg, fg.N, "elimination"
-        self.backend = backend or DeviceBackend(ctx)
+        self.messages = "elimination"
         self.max_product = int(max_product or 0)
         self.loss_slack, self.loss_factor, self.priors_last = float(loss_slack), float(loss_factor), bool(priors_last)
         self.order_seed = int(order_seed)
         self.centre = centre
         self.near_weight = float(near_weight)
         self.mesh_max = int(mesh_max)
-        self.findex = {fl: (fl, ls, f) for fl, ls, f in fg.factors}
-        U = FactorGraph(fg.N)
-        for l, vt in fg.variables.items():
-            U.addVariable(l, vt)
+        self._open_universe(fg, backend or DeviceBackend(ctx))
+        U = self.universe
         U.addVariable(ZERO, VT)
-        self.universe = U
         self.VT = VT
         for l in list(fg.variables):
             U.addVariable(l + "^", VT)          # anchor block: N copies of the posterior mean
@@ -205,25 +201,15 @@ class RelativeEliminationSolver:
             self._build(fg, shard)
         self._to_pool = self.backend.BlockOp(self.store, "copy", [(l, l + "&") for l in fg.variables])
         self._mix = {}
-        self.runs = 0
         self.passes_pooled = 0
 
     def _build(self, fg, shard):
         import time
-        U = self.universe
         t0 = time.perf_counter()
         schedules = [self._structure(k) for k in range(self.structures)]
         self.schedules = schedules
         t1 = time.perf_counter()
-        self.store = self.backend.Store(U)
-        self.store.put(ZERO, np.zeros((self.kind.dim, fg.N)))
-        B = self.backend
-        self.shard = shard(self.store) if shard is not None else None
-        if self.shard is not None:
-            from .tree import _ShardedPlans
-            base = B
-            B = _ShardedPlans(base, lambda s: self.shard.plan_level(s, base.Plan))
-        self._B = B
+        B = self._open_store(shard)
         self.steps = []
         for sched in schedules:
             st = []
@@ -252,19 +238,13 @@ class RelativeEliminationSolver:
             bad = "no prior"
         return (True if bad is None else bad) if why else bad is None
 
-    # borrowed helpers (they use self.universe / self.max_product / self.fg only)
-    _need = TreeSolver._need
-    _lift = TreeSolver._lift
-    _split_products = TreeSolver._split_products
-
     # ------------------------------------------------------------------------------------------------ structure (host, once per graph)
     def _spec(self, L, entries, smsgs=()):
         """entries: [(destination label, [factor labels])] -> a one-group LevelSpec (every destination its own 'clique': a level is dealt
         to the ranks by variable), two-stage products where a destination has more than max_product proposals"""
         cliques = [([l], [0]) for l, _ in entries]
         pairs_of = {l: list(rows) for l, rows in entries}
-        cliques, pairs_of, sm = self._split_products(L, cliques, pairs_of, list(smsgs))
-        return LevelSpec(L, cliques, pairs_of, sm, 1)
+        return LevelSpec(L, *split_products(L, cliques, pairs_of, list(smsgs), self.max_product), 1)
 
     def _loss(self, v, adj):
         """what eliminating v NOW costs, and the centre of its star: the star about neighbour c replaces the pair (j, k) of spread
@@ -301,8 +281,7 @@ class RelativeEliminationSolver:
         return best
 
     def _structure(self, k_struct=0):
-        from .graph import FactorGraph
-        fg, N, VT = self.fg, self.N, self.VT
+        fg, VT = self.fg, self.VT
         K = self.kind
         Prior, Sampled, _inv, _comp = K.prior, K.sampled, K.inv, K.comp
         U = self.universe
@@ -317,21 +296,19 @@ class RelativeEliminationSolver:
         unary = {v: [] for v in fg.variables}          # v -> [blocks of ABSOLUTE samples of v]: priors, and priors transported along edges
         sched = []
         # ---- step 0: the samples of every factor's measurement (a row from the ZERO block: 0 (+) z = z; a prior: its own row), ONE launch chain
-        L = FactorGraph(N); L.addVariable(ZERO, VT)
+        L = LevelGraph(U); L.need(ZERO, VT)
         ent = []
         for fl, ls, f in fg.factors:
             if isinstance(f, Prior):
                 blk = new_block("p")
-                L.addVariable(blk, VT)
-                ent.append((blk, [self._lift(L, fl, 0, "p", [blk], f)]))
+                L.need(blk, VT)
+                ent.append((blk, [L.lift(fl, 0, "p", [blk], f, fg)]))
                 unary[ls[0]].append(blk)
                 continue
             a, b = ls
             blk = new_block("e")
-            L.addVariable(blk, VT)
-            nfl = "s:" + fl
-            L.factors.append((nfl, [ZERO, blk], f)); L._findex[nfl] = L.factors[-1]
-            ent.append((blk, [nfl]))
+            L.need(blk, VT)
+            ent.append((blk, [L.putFactor("s:" + fl, [ZERO, blk], f)]))
             e = _Edge(a, b, blk, *K.shadow(f.Z), K)
             adj[a].setdefault(b, []).append(e); adj[b].setdefault(a, []).append(e)
         pri = {v for v in fg.variables if unary[v]}
@@ -365,12 +342,8 @@ class RelativeEliminationSolver:
             """rows that re-emit the samples of `blocks` as proposals of `dst` (0 (+) z = z; flipped: 0 (-) z = z^-1)"""
             rows = []
             for k, blk in enumerate(blocks):
-                if blk not in Lx.variables:
-                    Lx.addVariable(blk, VT)
-                nfl = "g:%s:%d" % (dst, k)
-                labels = [dst, ZERO] if k in flip else [ZERO, dst]
-                Lx.factors.append((nfl, labels, Sampled(blk))); Lx._findex[nfl] = Lx.factors[-1]
-                rows.append(nfl)
+                Lx.need(blk, VT)
+                rows.append(Lx.putFactor("g:%s:%d" % (dst, k), [dst, ZERO] if k in flip else [ZERO, dst], Sampled(blk)))
             return rows
 
         while alive:
@@ -388,15 +361,15 @@ class RelativeEliminationSolver:
                 if not adj[v] and not unary[v]:
                     raise ValueError("variable %s is not connected to a prior" % v)
                 sel.append(v); blocked.add(v); blocked.update(adj[v])
-            Lm = FactorGraph(N); Lm.addVariable(ZERO, VT)
-            Lt = FactorGraph(N)
+            Lm = LevelGraph(U); Lm.need(ZERO, VT)
+            Lt = LevelGraph(U)
             merges, transports, comps, dn = [], [], [], []
             for v in sel:
                 nb = {}
                 for u, es in adj[v].items():
                     if len(es) > 1:     # parallel edges -> one: product of their samples, all seen from v
                         blk = new_block("m")
-                        Lm.addVariable(blk, VT)
+                        Lm.need(blk, VT)
                         mm, mvt, mvth = K.merge([e.seen_from(v) for e in es])
                         merges.append((blk, identity_rows(Lm, blk, [e.block for e in es], flip={k for k, e in enumerate(es) if e.a != v})))
                         n_merge += 1
@@ -405,7 +378,7 @@ class RelativeEliminationSolver:
                         nb[u] = es[0]
                 if len(unary[v]) > 1:   # several absolute beliefs of v -> one
                     blk = new_block("q")
-                    Lm.addVariable(blk, VT)
+                    Lm.need(blk, VT)
                     merges.append((blk, identity_rows(Lm, blk, unary[v]))); n_merge += 1
                     unary[v] = [blk]
                 for u in nb:
@@ -448,11 +421,9 @@ class RelativeEliminationSolver:
                     if unary[v]:        # the absolute belief of v travels to c: p(c) = p(v) (+) z_c -- a convolution of BELIEF samples
                         blk, pv, ec = new_block("a"), unary[v][0], nb[c]
                         for l in (blk, pv, ec.block):
-                            if l not in Lt.variables:
-                                Lt.addVariable(l, VT)
-                        nfl = "t:%s" % blk
-                        Lt.factors.append((nfl, [pv, blk] if ec.a == v else [blk, pv], Sampled(ec.block))); Lt._findex[nfl] = Lt.factors[-1]
-                        transports.append((blk, [nfl])); unary[c].append(blk); n_transport += 1
+                            Lt.need(l, VT)
+                        transports.append((blk, [Lt.putFactor("t:%s" % blk, [pv, blk] if ec.a == v else [blk, pv], Sampled(ec.block))]))
+                        unary[c].append(blk); n_transport += 1
                     n_approx += len(nb) > 2
                 dn.append((v, list(nb.items()), list(unary[v])))
                 del adj[v]
@@ -469,24 +440,19 @@ class RelativeEliminationSolver:
         anchor = lambda v: v + "^"     # noqa: E731
         anchored = set()
         for dn in reversed(down):
-            Ld = FactorGraph(N)
+            Ld = LevelGraph(U)
             need, ent, sm = [], [], []
             for v, nbs, un in dn:
-                Ld.addVariable(v, VT)
+                Ld.need(v, VT)
                 rows = []
                 for u, e in nbs:
                     if u not in anchored:
                         anchored.add(u); need.append((u, anchor(u)))
                     for l in (anchor(u), e.block):
-                        if l not in Ld.variables:
-                            Ld.addVariable(l, VT)
-                    nfl = "d:%s:%s:%s" % (v, u, e.block)
-                    labels = [v, anchor(u)] if e.a == v else [anchor(u), v]
-                    Ld.factors.append((nfl, labels, Sampled(e.block))); Ld._findex[nfl] = Ld.factors[-1]
-                    rows.append(nfl)
+                        Ld.need(l, VT)
+                    rows.append(Ld.putFactor("d:%s:%s:%s" % (v, u, e.block), [v, anchor(u)] if e.a == v else [anchor(u), v], Sampled(e.block)))
                 for blk in un:
-                    if blk not in Ld.variables:
-                        Ld.addVariable(blk, VT)
+                    Ld.need(blk, VT)
                     sm.append((blk, v))
                 ent.append((v, rows))
             if need:
@@ -499,15 +465,6 @@ class RelativeEliminationSolver:
         return sched
 
     # ------------------------------------------------------------------------------------------------ the solve
-    def _run(self, plan, opts):
-        o = type(opts).from_buffer_copy(opts)
-        o.stream_offset = opts.stream_offset + (self.runs << 36)
-        if self.shard is not None:
-            self.shard.step(plan, o)
-        else:
-            plan.run(o)
-        self.runs += 1
-
     def upload(self, fg=None):
         """(nothing to upload: the solve starts from the factors alone; present so that solveTree treats every solver alike)"""
 
@@ -533,9 +490,6 @@ class RelativeEliminationSolver:
 
     def reset(self):
         self.passes_pooled = 0
-
-    def download(self, fg=None):
-        self.store.download(fg or self.fg, labels=list(self.fg.variables))
 
     def stats(self):
         return dict(self._stats, messages=self.messages, build_s=self.build_s)

@@ -85,14 +85,19 @@ class FactorGraph:
         while "".join(labels) + "f%d" % k in used:
             k += 1
         flabel = "".join(labels) + "f%d" % k
+        if nullhypo and not 0.0 <= float(nullhypo) <= 1.0:
+            raise ValueError("nullhypo must be a probability")
+        return self.putFactor(flabel, labels, factor, (w[1], w[2]) if extra is not None else None, float(nullhypo) if nullhypo else None)
+
+    def putFactor(self, flabel, labels, factor, multihypo=None, nullhypo=None):
+        """the factor under a label of the CALLER's choice, with none of addFactor's checks: what the level graphs of the tree solvers
+        hold (levels.LevelGraph: lifted copies, sampled-measurement rows over the ZERO block).  multihypo: (w1, w2); nullhypo: p."""
         self.factors.append((flabel, labels, factor))
         self._findex[flabel] = self.factors[-1]
-        if extra is not None:
-            self.multihypo[flabel] = (w[1], w[2])
-        if nullhypo:
-            if not 0.0 <= float(nullhypo) <= 1.0:
-                raise ValueError("nullhypo must be a probability")
-            self.nullhypo[flabel] = float(nullhypo)
+        if multihypo is not None:
+            self.multihypo[flabel] = multihypo
+        if nullhypo is not None:
+            self.nullhypo[flabel] = nullhypo
         return flabel
 
     def deleteFactor(self, flabel):

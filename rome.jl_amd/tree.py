@@ -26,11 +26,15 @@ marginalisation, `multiproc`.  A level (all cliques of equal height: mutually in
 `rome_upsolve_plan` -- every launch covers every clique of the level, and a level is what `distributed.FrontierShard` deals to the
 ranks.  The tree is built on the host once per graph; a solve is plan runs only (beliefs never leave HBM).
 """
+import ctypes as C
 import heapq
 
 import numpy as np
 
+from . import _lib
+from .clique import DeviceStore, LibHandle, UpsolvePlan, plan_level
 from .factors import refuse_range, refuse_bearing
+from .levels import ZERO, LevelSpec, LevelGraph, LevelSolver, split_products   # noqa: F401  (ZERO, LevelSpec: importable from here as before)
 
 
 class Clique:
@@ -143,19 +147,33 @@ class BayesTree:
 
 
 # ------------------------------------------------------------------------------------------------------------------ the solve
-ZERO = "0~"          # a Pose2 block that stays zero: the samples of an identity row (tree.TreeSolver max_product)
 
 
-def _colour(order, nbr):
-    """greedy colouring of `order` (list) under adjacency nbr(v) -> iterable; -> {v: colour}"""
+def _gibbs_colours(order, factor_vars):
+    """Gibbs order of a clique's solve: greedy colour classes of `order` (list) in the graph that the factors (their variable lists) draw
+    among its members -> {v: colour}"""
+    nb = {v: set() for v in order}
+    for ls in factor_vars:
+        for v in ls:
+            if v in nb:
+                nb[v].update(o for o in ls if o != v and o in nb)
     col = {}
     for v in order:
-        used = {col[o] for o in nbr(v) if o in col}
+        used = {col[o] for o in nb[v] if o in col}
         c = 0
         while c in used:
             c += 1
         col[v] = c
     return col
+
+
+def _factors_on(pw):
+    """{variable: the factors [(id, variables, factor)] of pw on it, in pw's order}"""
+    on = {}
+    for p in pw:
+        for o in p[1]:
+            on.setdefault(o, []).append(p)
+    return on
 
 
 def _outward(targets, informed, pairwise, unary):
@@ -187,40 +205,12 @@ def _outward(targets, informed, pairwise, unary):
     return rounds, pending
 
 
-class LevelSpec:
-    """One tree level as ONE up-solve description over lifted labels:
-      fg        FactorGraph holding the level's variables and (relabelled) factors -- what CliqueBatch / the oracle restatement consume
-      cliques   per clique of the level: (update labels, their group numbers)
-      order / groups / owner   the level's update list: group g of every clique together, groups in order; owner[k] = clique (position
-                in the level) of entry k
-      pairs     (factor, destination) rows in update order
-      smsgs     (source label, destination label): store-resident messages, in destination order
-      copies / anchors   block operations BEFORE the run: (source, destination) copies; (belief, destination) anchors (N copies of the mean)
-      relatives          AFTER the run: (anchor block, separator block, destination): samples of anchor^-1 * separator"""
-
-    def __init__(self, fg, cliques, pairs_of, smsgs, gibbs_iters, copies=(), anchors=(), relatives=()):
-        self.fg, self.cliques, self.gibbs_iters = fg, cliques, gibbs_iters
-        self.copies, self.anchors, self.relatives = list(copies), list(anchors), list(relatives)
-        self.order, self.groups, self.owner = [], [], []
-        for g in sorted({g for _, gs in cliques for g in gs}):
-            for k, (upd, gs) in enumerate(cliques):
-                for l, gl in zip(upd, gs):
-                    if gl == g:
-                        self.order.append(l); self.groups.append(g); self.owner.append(k)
-        self.pairs = [(fl, l) for l in self.order for fl in pairs_of.get(l, ())]
-        by_dest = {}
-        for src, dst in smsgs:
-            by_dest.setdefault(dst, []).append(src)
-        self.smsgs = [(src, l) for l in self.order for src in by_dest.get(l, ())]
-
-
-class TreeSolver:
+class TreeSolver(LevelSolver):
     """`solveTree!` over a BayesTree: builds, once, the lifted variable universe (home blocks + the cliques' private copies), one up and
     one down LevelSpec per tree level and their plans through `backend`; `solve(opts)` = plan runs and block operations only.
 
-    backend: object with Store(universe_fg) -> store (`.index`, `.upload(fg)`, `.download(fg, labels)`), Plan(store, spec, share=None)
-    -> `.run(opts)`, BlockOp(store, op, entries) -> `.run()` (op "copy" / "anchor" / "relative").  Default: the device
-    (`DeviceBackend`); the CPU tests inject an oracle-backed one.
+    backend: as levels.LevelSolver describes (block operations "copy" / "anchor" / "relative").  Default: the device (`DeviceBackend`);
+    the CPU tests inject an oracle-backed one.
     messages: "marginal" (default: IIF's form -- the reference's semantics, and the more robust one on small or multimodal graphs: hexagon
     windows, beehive, the reference's Manhattan-500 graph) or "relative" (what moves a LARGE pose graph with a single prior off its init
     pass: Manhattan-3500 5.3 m -> metres; module docstring).  gibbsIters / downIters: iterations of the up / down clique solves in
@@ -254,123 +244,30 @@ class TreeSolver:
         operations between levels run on every rank (each holds the whole store)."""
         refuse_range([f for _, _, f in fg.factors], "TreeSolver")
         refuse_bearing([f for _, _, f in fg.factors], "TreeSolver")
-        from .graph import FactorGraph
         if messages not in ("relative", "marginal"):
             raise ValueError("messages must be 'relative' or 'marginal'")
         if message_tree not in ("hop", "star"):
             raise ValueError("message_tree must be 'hop' or 'star'")
-        self.message_tree = message_tree
-        self.fg, self.N, self.messages = fg, fg.N, messages
+        self.message_tree, self.messages = message_tree, messages
+        self._open_universe(fg, backend or DeviceBackend(ctx))
         self.tree = tree or BayesTree.build(list(fg.variables), [(fl, tuple(ls)) for fl, ls, _ in fg.factors], order=order, last=last)
-        self.backend = backend or DeviceBackend(ctx)
         self.gibbsIters, self.downIters, self.rootIters, self.refineIters = int(gibbsIters), int(downIters), int(rootIters), int(refineIters)
         self.relIters, self.max_product = int(relIters), int(max_product or 0)
         if not 0 <= self.relIters <= 16:
             raise ValueError("relIters must be in 0..16")
         if not (1 <= self.gibbsIters <= 16 and 1 <= self.downIters <= 16 and 0 <= self.rootIters <= 16 and 0 <= self.refineIters <= 16):
             raise ValueError("gibbsIters / downIters must be in 1..16")       # Philox: run k draws from k << 36
-        self.findex = {fl: (fl, ls, f) for fl, ls, f in fg.factors}
-        U = FactorGraph(fg.N)
-        for l, vt in fg.variables.items():
-            U.addVariable(l, vt)
-        self.universe = U
-        if messages == "marginal":
-            ups, downs = self._specs_marginal()
-        else:
-            ups, downs = self._specs_relative()
+        self.root_specs = self.refine_specs = self.rel_specs = [None] * len(self.tree.levels)
+        ups, downs = self._specs_marginal() if messages == "marginal" else self._specs_relative()
         self.up_specs, self.down_specs = ups, downs
-        self.store = self.backend.Store(U)
-        if ZERO in U.variables:
-            self.store.put(ZERO, np.zeros((3, fg.N)))
-        B = self.backend
-        ops = lambda s: ([B.BlockOp(self.store, "copy", s.copies)] if s.copies else []) + ([B.BlockOp(self.store, "anchor", s.anchors)] if s.anchors else [])
+        B = self._open_store(shard)
+        st = self.store
+        ops = lambda s: ([B.BlockOp(st, "copy", s.copies)] if s.copies else []) + ([B.BlockOp(st, "anchor", s.anchors)] if s.anchors else [])  # noqa: E731
+        plans = lambda specs: [B.Plan(st, s) if s is not None and s.order else None for s in specs]  # noqa: E731
         self.up_pre = [ops(s) for s in ups]
-        self.shard = shard(self.store) if shard is not None else None
-        if self.shard is not None:
-            base = B
-            B = _ShardedPlans(base, lambda s: self.shard.plan_level(s, base.Plan))
-        self.up_plans = [B.Plan(self.store, s) if s.order else None for s in ups]
-        self.up_post = [[B.BlockOp(self.store, "relative", s.relatives)] if s.relatives else [] for s in ups]
-        self.down_plans = [B.Plan(self.store, s) if s.order else None for s in downs]
-        self.root_plans = [B.Plan(self.store, s) if s is not None and s.order else None for s in getattr(self, "root_specs", [None] * len(ups))]
-        self.refine_plans = [B.Plan(self.store, s) if s is not None and s.order else None for s in getattr(self, "refine_specs", [None] * len(ups))]
-        self.rel_plans = [B.Plan(self.store, s) if s is not None and s.order else None for s in getattr(self, "rel_specs", [None] * len(ups))]
-        self.runs = 0
-
-    def _lift(self, L, fl, cid, tag, labels, factor):
-        """the factor `fl` of clique `cid` over lifted labels, as a factor of the level graph L"""
-        fg = self.fg
-        nfl = "%s%s%d" % (fl, tag, cid)
-        L.factors.append((nfl, labels, factor)); L._findex[nfl] = L.factors[-1]
-        if fl in fg.multihypo:
-            L.multihypo[nfl] = fg.multihypo[fl]
-        if fl in getattr(fg, "nullhypo", {}):
-            L.nullhypo[nfl] = fg.nullhypo[fl]
-        return nfl
-
-    def _split_products(self, L, cliques, pairs_of, smsgs):
-        """staged products for Pose2 variables with more than max_product proposals (class docstring): a variable with K proposals is
-        the root of a tree of partial products with fan-in <= max_product; a variable of update group g is solved in step
-        g * (D + 1) + D, its partial products of depth d below it in step g * (D + 1) + D - d (D = the deepest tree of the level)"""
-        from .factors import Pose2
-        from .clique import SampledPose2Pose2
-        G = self.max_product
-        by_dest = {}
-        for src, dst in smsgs:
-            by_dest.setdefault(dst, []).append(src)
-        count = lambda l: len(pairs_of.get(l, ())) + len(by_dest.get(l, ()))     # noqa: E731
-
-        def depth(k):
-            d = 0
-            while k > G:
-                k = -(-k // G); d += 1
-            return d
-        D = max((depth(count(l)) for upd, _ in cliques for l in upd if L.variables[l] is Pose2), default=0) if G > 1 else 0
-        if D == 0:
-            return cliques, pairs_of, smsgs
-        out_cliques, out_smsgs = [], []
-        for upd, grp in cliques:
-            nu, ng = [], []
-
-            def build(l, items, g, lvl):
-                """make `l` the product of `items` ((kind, id): a factor row, a store message, or a partial-product label) in step
-                g * (D + 1) + D - lvl"""
-                if len(items) > G and L.variables[l] is Pose2:
-                    nch = -(-len(items) // G)
-                    parts = []
-                    for k in range(nch):
-                        pl = "%s^%d" % (l, k)
-                        self._need(L, pl, Pose2)
-                        build(pl, [(kind, x, l) for kind, x, _ in items[k::nch]], g, lvl + 1)
-                        parts.append(("p", pl, l))
-                    items = parts
-                rows = []
-                for kind, x, owner in items:
-                    if kind == "f":          # a factor row of the ORIGINAL variable `owner`, retargeted to l
-                        if owner == l:
-                            rows.append(x)
-                        else:
-                            _, labels, f = L.getFactor(x)
-                            nfl = "%s>%s" % (x, l)
-                            L.factors.append((nfl, [l if o == owner else o for o in labels], f)); L._findex[nfl] = L.factors[-1]
-                            if x in L.multihypo:
-                                L.multihypo[nfl] = L.multihypo[x]
-                            if x in L.nullhypo:
-                                L.nullhypo[nfl] = L.nullhypo[x]
-                            rows.append(nfl)
-                    elif kind == "m":
-                        out_smsgs.append((x, l))
-                    else:                    # a partial product enters through an identity row (sampled row whose samples are zero)
-                        idf = "=%s" % x
-                        self._need(L, ZERO, Pose2)
-                        L.factors.append((idf, [x, l], SampledPose2Pose2(ZERO))); L._findex[idf] = L.factors[-1]
-                        rows.append(idf)
-                pairs_of[l] = rows
-                nu.append(l); ng.append(g * (D + 1) + D - lvl)
-            for l, g in zip(upd, grp):
-                build(l, [("f", fl, l) for fl in pairs_of.get(l, ())] + [("m", src, l) for src in by_dest.get(l, ())], g, 0)
-            out_cliques.append((nu, ng))
-        return out_cliques, pairs_of, out_smsgs
+        self.up_plans = plans(ups)
+        self.up_post = [[B.BlockOp(st, "relative", s.relatives)] if s.relatives else [] for s in ups]
+        self.down_plans, self.root_plans, self.refine_plans, self.rel_plans = (plans(x) for x in (downs, self.root_specs, self.refine_specs, self.rel_specs))
 
     @staticmethod
     def _message_tree(V, S, root, edges, can_anchor, star=False):
@@ -412,21 +309,14 @@ class TreeSolver:
             out.append((best[1], best[2], best[0])); intree.append(best[2]); left.remove(best[2])
         return out
 
-    def _need(self, L, label, vt):
-        if label not in self.universe.variables:
-            self.universe.addVariable(label, vt)
-        if label not in L.variables:
-            L.addVariable(label, vt)
-
     # ---------------------------------------------------------------- "marginal": IIF's per-variable separator beliefs
     def _specs_marginal(self):
-        from .graph import FactorGraph
         fg, t = self.fg, self.tree
         ups, downs = [], []
         copy_label = lambda cid, s: "%s@%d" % (s, cid)
         for lvl in t.levels:
             for up in (True, False):
-                L = FactorGraph(fg.N)
+                L = LevelGraph(self.universe)
                 cliques, pairs_of, smsgs, copies = [], {}, [], []
                 for cid in lvl:
                     c = t.cliques[cid]
@@ -435,17 +325,16 @@ class TreeSolver:
                     lab = {v: v for v in c.frontals}
                     lab.update({s: (copy_label(cid, s) if up else s) for s in c.separators})
                     for v in c.frontals + c.separators:
-                        self._need(L, lab[v], fg.variables[v])
+                        L.need(lab[v], fg.variables[v])
                     upd = list(c.frontals) + (list(c.separators) if up else [])
-                    nb = {v: set() for v in upd}
                     touching = {v: [] for v in upd}
                     for fl in c.factors:
                         _, ls, f = self.findex[fl]
-                        nfl = self._lift(L, fl, cid, "@" if up else "!", [lab[v] for v in ls], f)
+                        nfl = L.lift(fl, cid, "@" if up else "!", [lab[v] for v in ls], f, fg)
                         for v in ls:
-                            if v in nb:
-                                nb[v].update(o for o in ls if o != v and o in nb); touching[v].append(nfl)
-                    col = _colour(upd, nb.__getitem__)                   # Gibbs order: colour classes of the clique's own factor graph
+                            if v in touching:
+                                touching[v].append(nfl)
+                    col = _gibbs_colours(upd, [self.findex[fl][1] for fl in c.factors])
                     cliques.append(([lab[v] for v in upd], [col[v] for v in upd]))
                     for v in upd:
                         pairs_of[lab[v]] = touching[v]
@@ -454,29 +343,61 @@ class TreeSolver:
                     for d in c.children:                                 # messages: the child's separator copies, written one level earlier
                         for s in t.cliques[d].separators:
                             if up or s in c.frontals:
-                                self._need(L, copy_label(d, s), fg.variables[s])
+                                L.need(copy_label(d, s), fg.variables[s])
                                 smsgs.append((copy_label(d, s), lab[s]))
                 (ups if up else downs).append(LevelSpec(L, cliques, pairs_of, smsgs, self.gibbsIters if up else self.downIters, copies=copies))
         return ups, downs
 
     # ---------------------------------------------------------------- "relative": anchor marginal + samples of anchor^-1 * separator
+    def _rows(self, L, pairs_of, smsgs, cid, v, lab, tag, pw, pri=(), srcs=(), key=None):
+        """The rows of variable v of clique `cid` in the level graph L: the pairwise factors `pw` [(id, variables, factor)] over the label
+        map `lab` (a dict) under the tag prefix `tag` (a factor has one row per destination: + `key`, default the label of v), those of the priors
+        `pri` [(id, variable, factor)] that sit on v, and the store messages `srcs` [source label] onto v.  -> the label of v.
+        The ORDER of the need / lift calls is part of the result: block indices in the store follow the universe's insertion order, and
+        row order fixes the Philox stream ids."""
+        fg, vt, l = self.fg, self.fg.variables, lab[v]
+        L.need(l, vt[v])
+        rows, rtag = [], tag + (key or l) + ":"
+        for fid, ls, f in pw:
+            labels = [lab[o] for o in ls]
+            for o, lo in zip(ls, labels):
+                if lo not in L.variables:      # (most are there already: the test saves the call)
+                    L.need(lo, vt[o])
+            rows.append(L.lift(fid, cid, rtag, labels, f, fg))
+        rows += [L.lift(fl, cid, tag, [l], f, fg) for fl, pv, f in pri if pv == v]
+        for src in srcs:
+            L.need(src, vt[v]); smsgs.append((src, l))
+        pairs_of[l] = rows
+        return l
+
+    def _outward_rows(self, L, pairs_of, smsgs, cid, rounds, lab, tag, pw, pri=None):
+        """the rows of an outward solve (`_outward`: round r = update group r, a variable takes the factors the round selected);
+        pri: the clique's priors where unary sources count (priors, store messages), None for a relative solve -> (labels, groups)"""
+        upd, grp = [], []
+        by_id = {p[0]: p for p in pw}        # (a round lists a variable's factors in pw's order)
+        for r, rnd in enumerate(rounds):
+            for v, fids, sids in rnd:
+                srcs = () if pri is None else [src for src in sids if not str(src).startswith("prior:")]
+                upd.append(self._rows(L, pairs_of, smsgs, cid, v, lab, tag, pw=[by_id[f] for f in fids], pri=pri or (), srcs=srcs)); grp.append(r)
+        return upd, grp
+
     def _specs_relative(self):
-        from .graph import FactorGraph
         from .factors import Pose2, Point2
         from .clique import SampledPose2Pose2, SampledBearingRange
-        fg, t = self.fg, self.tree
+        fg, t, vt = self.fg, self.tree, self.fg.variables
         ups, downs = [], []
         abs_msgs, rel_msgs = {}, {}          # clique -> [(source label, variable)] / [(anchor, separator, samples label)]
         msg_len = {}                         # clique -> [(anchor, separator, path length)]: the message tree's edges, for the parent's own tree
         self.anchor, self.unreached = {}, []
         down_parts, rel_parts = {}, {}
+        home = {v: v for v in vt}            # label map of the solves that write the home blocks
+        split = lambda L, cliques, pairs_of, smsgs: split_products(L, cliques, pairs_of, smsgs, self.max_product)   # noqa: E731
         for lvl in t.levels:
-            L = FactorGraph(fg.N)
+            L = LevelGraph(self.universe)
             cliques, pairs_of, smsgs, anchors, relatives = [], {}, [], [], []
             for cid in lvl:
                 c = t.cliques[cid]
                 F, S = c.frontals, c.separators
-                vt = fg.variables
                 pw = [(fl, self.findex[fl][1], self.findex[fl][2]) for fl in c.factors if len(self.findex[fl][1]) > 1]
                 pri = [(fl, self.findex[fl][1][0], self.findex[fl][2]) for fl in c.factors if len(self.findex[fl][1]) == 1]
                 for d in c.children:
@@ -486,27 +407,6 @@ class TreeSolver:
                 anc = next((s for s in S if vt[s] is Pose2), None) if c.parent >= 0 else None
                 self.anchor[cid] = anc
                 upd, grp = [], []
-
-                def add(rounds, lab, tag, with_unary):
-                    for r, rnd in enumerate(rounds):
-                        for v, fids, sids in rnd:
-                            self._need(L, lab[v], vt[v])
-                            rows = []
-                            for fid, ls, f in pw:
-                                if fid in fids:
-                                    for o in ls:
-                                        self._need(L, lab[o], vt[o])
-                                    rows.append(self._lift(L, fid, cid, tag + lab[v] + ":", [lab[o] for o in ls], f))
-                            if with_unary:
-                                for fl, pv, f in pri:
-                                    if pv == v:
-                                        rows.append(self._lift(L, fl, cid, tag, [lab[v]], f))
-                                for src in sids:
-                                    if not str(src).startswith("prior:"):
-                                        self._need(L, src, vt[v]); smsgs.append((src, lab[v]))
-                            pairs_of[lab[v]] = rows
-                            upd.append(lab[v]); grp.append(r)
-
                 pwl = [(fid, ls) for fid, ls, _ in pw]
                 unary = [("prior:" + fl, pv) for fl, pv, _ in pri] + srcs
                 # ---- absolute solve: outward from the priors and the children's anchor marginals
@@ -515,7 +415,7 @@ class TreeSolver:
                     lab = {v: v for v in F}
                     lab.update({s: "%s#%d" % (s, cid) for s in S})
                     rounds, left = _outward(list(F) + list(S), (), pwl, unary)
-                    add(rounds, lab, "#", True)
+                    upd, grp = self._outward_rows(L, pairs_of, smsgs, cid, rounds, lab, "#", pw, pri=pri)
                     reached = {v for rnd in rounds for v, _, _ in rnd}
                     if c.parent >= 0:
                         abs_msgs[cid] = [(lab[s], s) for s in ([anc] if anc is not None else S) if s in reached]
@@ -537,10 +437,11 @@ class TreeSolver:
                             lab = {v: "%s@%d" % (v, cid) for v in F + S}
                         else:
                             lab = {v: "%s@%d^%s" % (v, cid, j) for v in F + S}
-                        self._need(L, lab[j], vt[j])
+                        L.need(lab[j], vt[j])
                         anchors.append((j, lab[j]))
                         rounds, left = _outward(list(F) + [s for s in S if s != j], (j,), pwl, ())
-                        add(rounds, lab, "@" if j == anc else "@^%s" % j, False)
+                        u, g = self._outward_rows(L, pairs_of, smsgs, cid, rounds, lab, "@" if j == anc else "@^%s" % j, pw)
+                        upd += u; grp += g
                         reached = {v for rnd in rounds for v, _, _ in rnd}
                         if j == anc:
                             rel_parts[cid] = (pw, reached, anc)
@@ -552,48 +453,26 @@ class TreeSolver:
                                 relatives.append((lab[j], lab[k], zl)); rel_msgs[cid].append((j, k, zl)); msg_len[cid].append((j, k, w))
                 cliques.append((upd, grp))
                 down_parts[cid] = (pw, pri, srcs)
-            cliques, pairs_of, smsgs = self._split_products(L, cliques, pairs_of, smsgs)
-            ups.append(LevelSpec(L, cliques, pairs_of, smsgs, 1, anchors=anchors, relatives=relatives))
+            ups.append(LevelSpec(L, *split(L, cliques, pairs_of, smsgs), 1, anchors=anchors, relatives=relatives))
         # ---- down pass: the frontals outward from the separators (at their posteriors), the priors and the children's anchor marginals
         for lvl in t.levels:
-            L = FactorGraph(fg.N)
+            L = LevelGraph(self.universe)
             cliques, pairs_of, smsgs = [], {}, []
             for cid in lvl:
                 c = t.cliques[cid]
                 if c.parent < 0:
                     cliques.append(([], [])); continue
                 pw, pri, srcs = down_parts[cid]
-                vt = fg.variables
-                F, S = c.frontals, c.separators
-                rounds, left = _outward(list(F), S, [(fid, ls) for fid, ls, _ in pw], [("prior:" + fl, pv) for fl, pv, _ in pri] + srcs)
-                upd, grp = [], []
-                for r, rnd in enumerate(rounds):
-                    for v, fids, sids in rnd:
-                        self._need(L, v, vt[v])
-                        rows = []
-                        for fid, ls, f in pw:
-                            if fid in fids:
-                                for o in ls:
-                                    self._need(L, o, vt[o])
-                                rows.append(self._lift(L, fid, cid, "!" + v + ":", list(ls), f))
-                        for fl, pv, f in pri:
-                            if pv == v:
-                                rows.append(self._lift(L, fl, cid, "!", [v], f))
-                        for src in sids:
-                            if not str(src).startswith("prior:"):
-                                self._need(L, src, vt[v]); smsgs.append((src, v))
-                        pairs_of[v] = rows
-                        upd.append(v); grp.append(r)
+                rounds, left = _outward(list(c.frontals), c.separators, [(fid, ls) for fid, ls, _ in pw], [("prior:" + fl, pv) for fl, pv, _ in pri] + srcs)
+                cliques.append(self._outward_rows(L, pairs_of, smsgs, cid, rounds, home, "!", pw, pri=pri))
                 self.unreached += [(cid, v) for v in left]
-                cliques.append((upd, grp))
-            cliques, pairs_of, smsgs = self._split_products(L, cliques, pairs_of, smsgs)
-            downs.append(LevelSpec(L, cliques, pairs_of, smsgs, 1))
+            downs.append(LevelSpec(L, *split(L, cliques, pairs_of, smsgs), 1))
         # ---- Gibbs sweeps over the frontals with every factor and message of the clique (roots after the up pass, the others after
         #      their outward down solve): colour classes of the clique's own graph
         def sweeps(lvl, roots, iters):
             if iters <= 0:
                 return None
-            L = FactorGraph(fg.N)
+            L = LevelGraph(self.universe)
             cliques, pairs_of, smsgs = [], {}, []
             for cid in lvl:
                 c = t.cliques[cid]
@@ -601,74 +480,36 @@ class TreeSolver:
                     cliques.append(([], [])); continue
                 pw, pri, srcs = down_parts[cid]
                 F = list(c.frontals)
-                nb = {v: set() for v in F}
-                for _, ls, _ in pw:
-                    for v in ls:
-                        if v in nb:
-                            nb[v].update(o for o in ls if o != v and o in nb)
-                col = _colour(F, nb.__getitem__)
+                col = _gibbs_colours(F, [ls for _, ls, _ in pw])
+                on = _factors_on(pw)
                 for v in F:
-                    self._need(L, v, fg.variables[v])
-                    rows = []
-                    for fid, ls, f in pw:
-                        if v in ls:
-                            for o in ls:
-                                self._need(L, o, fg.variables[o])
-                            rows.append(self._lift(L, fid, cid, "*" + v + ":", list(ls), f))
-                    rows += [self._lift(L, fl, cid, "*", [v], f) for fl, pv, f in pri if pv == v]
-                    for src, sv in srcs:
-                        if sv == v:
-                            self._need(L, src, fg.variables[v]); smsgs.append((src, v))
-                    pairs_of[v] = rows
+                    self._rows(L, pairs_of, smsgs, cid, v, home, "*", pw=on[v] if v in on else (), pri=pri, srcs=[src for src, sv in srcs if sv == v])
                 cliques.append((F, [col[v] for v in F]))
-            cliques, pairs_of, smsgs = self._split_products(L, cliques, pairs_of, smsgs)
-            return LevelSpec(L, cliques, pairs_of, smsgs, iters)
+            return LevelSpec(L, *split(L, cliques, pairs_of, smsgs), iters)
+
         def rel_sweeps(lvl):
             if self.relIters <= 0:
                 return None
-            L = FactorGraph(fg.N)
+            L = LevelGraph(self.universe)
             cliques, pairs_of = [], {}
             for cid in lvl:
                 if cid not in rel_parts:
                     cliques.append(([], [])); continue
                 pw, reached, anc = rel_parts[cid]
-                lab = lambda v: "%s@%d" % (v, cid)
                 known = reached | {anc}
+                lab = {v: "%s@%d" % (v, cid) for v in known}
                 T = [v for v in t.cliques[cid].frontals + t.cliques[cid].separators if v in reached]
-                nb = {v: set() for v in T}
                 use = [(fid, ls, f) for fid, ls, f in pw if all(o in known for o in ls)]
-                for _, ls, _ in use:
-                    for v in ls:
-                        if v in nb:
-                            nb[v].update(o for o in ls if o != v and o in nb)
-                col = _colour(T, nb.__getitem__)
-                for v in T:
-                    self._need(L, lab(v), fg.variables[v])
-                    rows = []
-                    for fid, ls, f in use:
-                        if v in ls:
-                            for o in ls:
-                                self._need(L, lab(o), fg.variables[o])
-                            rows.append(self._lift(L, fid, cid, "%" + v + ":", [lab(o) for o in ls], f))
-                    pairs_of[lab(v)] = rows
-                cliques.append(([lab(v) for v in T], [col[v] for v in T]))
-            cliques, pairs_of, sm = self._split_products(L, cliques, pairs_of, [])
-            return LevelSpec(L, cliques, pairs_of, sm, self.relIters)
+                col = _gibbs_colours(T, [ls for _, ls, _ in use])
+                on = _factors_on(use)
+                cliques.append(([self._rows(L, pairs_of, None, cid, v, lab, "%", pw=on[v] if v in on else (), key=v) for v in T], [col[v] for v in T]))
+            return LevelSpec(L, *split(L, cliques, pairs_of, []), self.relIters)
         self.rel_specs = [rel_sweeps(lvl) for lvl in t.levels]
         self.root_specs = [sweeps(lvl, True, self.rootIters) for lvl in t.levels]
         self.refine_specs = [sweeps(lvl, False, self.refineIters) for lvl in t.levels]
         return ups, downs
 
     # ---------------------------------------------------------------- the solve
-    def _run(self, plan, opts):
-        o = type(opts).from_buffer_copy(opts)
-        o.stream_offset = opts.stream_offset + (self.runs << 36)     # (it << 32) + family / product offsets stay below 2^36
-        if self.shard is not None:
-            self.shard.step(plan, o)
-        else:
-            plan.run(o)
-        self.runs += 1
-
     def upload(self, fg=None):
         """current beliefs of every variable (IIF: initAll! has run) -> home blocks"""
         self.store.upload(fg or self.fg)
@@ -702,10 +543,6 @@ class TreeSolver:
             self.up(opts)
             self.down(opts)
 
-    def download(self, fg=None):
-        """home blocks -> fg.vals (the posterior of every variable)"""
-        self.store.download(fg or self.fg, labels=list(self.fg.variables))
-
     def stats(self):
         w = [len(l) for l in self.tree.levels]
         steps = lambda specs: sum(len(set(s.groups)) * s.gibbs_iters for s in specs if s.order)
@@ -716,19 +553,6 @@ class TreeSolver:
                     blocks=len(self.universe.variables), unreached=len(getattr(self, "unreached", ())))
 
 
-class _ShardedPlans:
-    """backend view whose Plan() returns a FrontierShard level plan (share up-solve + exchange + scatter); block operations unchanged"""
-
-    def __init__(self, backend, make):
-        self.backend, self.make = backend, make
-
-    def Plan(self, store, spec):
-        return self.make(spec)
-
-    def BlockOp(self, store, op, entries):
-        return self.backend.BlockOp(store, op, entries)
-
-
 class DeviceBackend:
     """TreeSolver on the device: `clique.DeviceStore` over the lifted universe, `TreeLevelPlan` per level, `rome_blockop_plan`s."""
 
@@ -736,7 +560,6 @@ class DeviceBackend:
         self.ctx = ctx
 
     def Store(self, universe):
-        from .clique import DeviceStore
         return DeviceStore(universe, ctx=self.ctx, upload=False)
 
     def Plan(self, store, spec, share=None, mirror=None):
@@ -746,17 +569,15 @@ class DeviceBackend:
         return BlockOpPlan(store, op, entries)
 
 
-class BlockOpPlan:
+class BlockOpPlan(LibHandle):
     """block operations inside a DeviceStore (rome_blockop_plan), ONE launch per run:
     "copy" [(source, destination)], "anchor" [(belief, destination)], "relative" [(anchor block, separator block, destination)],
     "compose" [(a, b, destination, invert a, invert b)] (Pose2 or Pose3 blocks, one type per plan), "mix" [(pool, destination, p)],
     "anchor_mean" [(belief, destination)] (Pose3: mean translation and mean rotation; Pose2 / Point2: as "anchor")"""
     OPS = {"copy": 0, "anchor": 1, "relative": 2, "compose": 3, "mix": 4, "anchor_mean": 5}
+    _destroy = "rome_blockop_plan_destroy"
 
     def __init__(self, store, op, entries):
-        import ctypes as C
-        from . import _lib
-        from .clique import DeviceStore
         self.store, self.ctx, self._lib = store, store.ctx, _lib.load()
         U = store.fg
         prm = None
@@ -783,87 +604,14 @@ class BlockOpPlan:
         self.handle = h
 
     def run(self):
-        from . import _lib
         _lib.check(self._lib.rome_blockop_plan_run(self.handle), self.ctx.handle)
         self.store.touched.update(self.dst_labels)
 
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.rome_blockop_plan_destroy(self.handle); self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class TreeLevelPlan:
+class TreeLevelPlan(UpsolvePlan):
     """A LevelSpec bound to a DeviceStore: `rome_upsolve_plan` with explicit (factor, destination) rows, groups and store-resident
-    messages.  share: positions (within the level) of the cliques THIS plan updates -- Philox stream ids are positions in the WHOLE
-    level's tables, so the shares of a level together draw what the unsharded plan draws."""
+    messages.  share: positions (within the level) of the cliques THIS plan updates (clique.upsolve_share)."""
 
     def __init__(self, store, spec, share=None, mirror=None, outputs=False):
-        import ctypes as C
-        from . import _lib, api
-        from .clique import CliqueBatch, CliqueUpsolveHost
-        from .factors import Pose2, Point2, Pose3
-        self.store, self.spec, self.ctx, self._lib = store, spec, store.ctx, _lib.load()
-        L = spec.fg
-        full = CliqueBatch(L, spec.pairs, var_index=store.index)
-        sid = {pair: r for pair, (fam, r) in full.rows.items()}
-        pos_t, cnt = {}, {Pose2: 0, Point2: 0, Pose3: 0}
-        for l in spec.order:
-            vt = L.variables[l]; pos_t[l] = cnt[vt]; cnt[vt] += 1
-        mine = None if share is None else set(share)
-        keep = [k for k in range(len(spec.order)) if mine is None or spec.owner[k] in mine]
-        order = [spec.order[k] for k in keep]
-        oset = set(order)
-        self.order = order
-        self.batch = full if mine is None else CliqueBatch(L, [p for p in spec.pairs if p[1] in oset], var_index=store.index, stream_ids=sid)
-        for l in order:
-            if l not in self.batch.vidx:
-                self.batch.vidx[l] = store.index[l]
-        u = CliqueUpsolveHost()
-        kp = []
-        self.res = self.batch._fill_upsolve(u, kp, order, spec.gibbs_iters, 1, "sequential", None, [spec.groups[k] for k in keep],
-                                            up_stream=[pos_t[l] for l in order],
-                                            up_mirror=None if mirror is None else [mirror.get(l, -1) for l in order], outputs=outputs)
-        pos_of = {l: k for k, l in enumerate(order)}
-        for ti, (vt, nm) in enumerate(((Pose2, "pose2"), (Point2, "point2"), (Pose3, "pose3"))):
-            ms = [(store.index[s], pos_of[d]) for s, d in spec.smsgs if d in pos_of and L.variables[d] is vt]
-            setattr(u, "n_smsg_" + nm, len(ms))
-            if ms:
-                a = np.array(ms, dtype=np.int32)
-                src, up = np.ascontiguousarray(a[:, 0]), np.ascontiguousarray(a[:, 1])
-                kp += [src, up]
-                setattr(u, "smsg_%s_src" % nm, src.ctypes.data_as(C.c_void_p)); setattr(u, "smsg_%s_up" % nm, up.ctypes.data_as(C.c_void_p))
-        self.has_mirror = mirror is not None
-        o = api.make_opts(N=L.N)
-        o.layout = _lib.LAYOUT_SOA
-        h = C.c_void_p()
-        _lib.check(self._lib.rome_upsolve_plan_create(self.ctx.handle, store.handle, C.byref(o), C.byref(u), C.byref(h)), self.ctx.handle)
-        self.handle = h
-
-    def run(self, opts, mirror_out=None, mirror_stride=0):
-        import ctypes as C
-        from . import _lib
-        o = _lib.Opts.from_buffer_copy(opts)
-        o.layout = _lib.LAYOUT_SOA
-        if hasattr(mirror_out, "data_ptr"):
-            mirror_out = mirror_out.data_ptr()
-        _lib.check(self._lib.rome_upsolve_plan_run(self.handle, C.byref(o), C.c_void_p(mirror_out or 0), int(mirror_stride)), self.ctx.handle)
-        self.store.touched.update(self.order)
-        if self.res:
-            return {l: (new[k].copy(), bw[k].copy()) for vt, (ls, new, bw) in self.res.items() for k, l in enumerate(ls)}
-        return None
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self._lib.rome_upsolve_plan_destroy(self.handle); self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.spec = spec
+        self._create(store, spec.fg, plan_level(spec, share, store.index), mirror, outputs)

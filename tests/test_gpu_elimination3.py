@@ -147,7 +147,7 @@ def test_sampled_pose3pose3_rows_equal_the_oracle_convolution(N):
     for l in ("x", "z", "y", "w"):
         L.addVariable(l, R.Pose3)
     for fl, labels in (("f0", ["x", "y"]), ("f1", ["w", "x"])):      # y = x (+) z;  w = x (-) z
-        L.factors.append((fl, labels, SampledPose3Pose3("z"))); L._findex[fl] = L.factors[-1]
+        L.putFactor(fl, labels, SampledPose3Pose3("z"))
     spec = LevelSpec(L, [(["y"], [0]), (["w"], [0])], {"y": ["f0"], "w": ["f1"]}, [], 1)
     TreeLevelPlan(st, spec).run(R.make_opts(N=N, seed=5))
     out = np.stack([st.get("y"), st.get("w")])

@@ -282,3 +282,39 @@ def test_staged_products_agree_with_the_single_product_in_law():
         assert np.abs(m - truth[:2]).max() < 0.15 and abs(th - truth[2]) < 0.05, (mp_, m, th)      # 14 proposals of sigma ~0.25: posterior sigma ~0.07
         assert 0.02 < sd.max() < 0.3, (mp_, sd)
     assert np.abs(res[0][0] - res[8][0]).max() < 0.15
+
+
+def test_every_library_handle_closes_once_and_stays_closed():
+    """clique.LibHandle under DeviceStore, UpsolvePlan, TreeLevelPlan, BlockOpPlan, ScatterPlan: each object runs, close() twice leaves
+    handle None, and collecting the closed object raises nothing"""
+    import gc
+    import torch
+    from rome_jl_amd.clique import LibHandle, ScatterPlan, UpsolvePlan
+    from rome_jl_amd.tree import LevelSpec, TreeLevelPlan
+    N = 32
+    fg = R.initfg(N)
+    rng = np.random.default_rng(11)
+    for k in range(2):
+        fg.addVariable("x%d" % k, R.Pose2)
+        fg.initVariable("x%d" % k, np.array([[k], [0.0], [0.0]]) + 0.1 * rng.standard_normal((3, N)))
+    fl = fg.addFactor(["x0", "x1"], R.Pose2Pose2(R.MvNormal([1.0, 0.0, 0.0], np.diag([0.01, 0.01, 0.001]))))
+    o = R.make_opts(N=N, seed=3)
+    store = DeviceStore(fg)
+    up = UpsolvePlan(store, [["x1"]], gibbsIters=1)
+    lvl = TreeLevelPlan(store, LevelSpec(fg, [(["x1"], [0])], {"x1": [fl]}, [], 1))
+    cp = BlockOpPlan(store, "copy", [("x1", "x0")])
+    sc = ScatterPlan(store, ["x0"], [0], stride=N)
+    buf = torch.zeros(3 * N, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()                 # (the plans run on the context's own stream)
+    up.run(o); lvl.run(o); cp.run(); sc.run(buf)
+    store.ctx.synchronize()
+    assert np.array_equal(store.get("x0"), np.zeros((3, N))) and np.isfinite(store.get("x1")).all()
+    objs = [up, lvl, cp, sc, store]          # (plans before the store they were made over)
+    for x in objs:
+        assert isinstance(x, LibHandle) and x.handle
+        x.close(); x.close()
+        assert x.handle is None
+    del up, lvl, cp, sc, store
+    while objs:
+        objs.pop()
+    gc.collect()
