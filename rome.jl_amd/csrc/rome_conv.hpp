@@ -22,6 +22,7 @@
 // a contiguous range of the convolution table (neighbouring factors share variables).
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 // Floating-point contraction by SOURCE EXPRESSION (a*b + c written in one expression is one fma), not across statements at the
 // optimizer's discretion (hipcc's default, -ffp-contract=fast): the same inlined function then rounds identically in every kernel
 // instantiation it is inlined into -- the packed sweep, the wave-per-row kernel (lean or not) and the per-factor entry points agree
@@ -99,6 +100,16 @@ __device__ __forceinline__ void store_stream2(double* p, const double2& v) {
   typedef double dvec2 __attribute__((ext_vector_type(2)));
   const dvec2 vv = {v.x, v.y};
   __builtin_nontemporal_store(vv, reinterpret_cast<dvec2*>(p));
+}
+
+// base + idx · stride_bytes + off_bytes for a NON-NEGATIVE index (row, block and factor indices are, by the table's contract) and a
+// byte stride below 2^32: the product is one unsigned 32 x 32 -> 64 multiply-add (v_mad_u64_u32), exact for arrays of any size --
+// written on int / size_t the same expression is a signed 64 x 64 partial product (v_mad_u64_u32 + 2 v_mul_lo_u32 + v_add3_u32 +
+// v_ashrrev_i32 per site).  The packed sweep's launcher refuses strides that do not fit (launch_flat).
+template <class T>
+__device__ __forceinline__ T* row_ptr(T* base, int idx, uint32_t stride_bytes, uint32_t off_bytes = 0u) {
+  typedef typename std::conditional<std::is_const<T>::value, const char, char>::type B;
+  return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + ((uint64_t)(uint32_t)idx * stride_bytes + off_bytes));
 }
 
 // separator rows are duplicated into the exchange buffer: block m of mirror_out for row c with mirror_map[c] = m >= 0
@@ -387,6 +398,16 @@ template <class FP> struct FlatStage { static constexpr int kLanes = FP::NK <= 1
 #endif
 template <class FP, int SOLVER, bool VERIFY, bool VEC2, int PP>
 __device__ __forceinline__ void conv_flat_body(const ConvArgs& a, int H, int CPB, uint32_t magic, int blk, double* __restrict__ s_K);
+// entry q of factor f's staged constants [μ(DZ), L(NL)]: ONE address, selected between the two arrays before the entry offset is added
+// (L is entered DZ entries before its start, so that q indexes both).  Integer arithmetic -- the address DZ entries before L is never
+// formed as a pointer -- and an explicit global-memory load
+template <class FP>
+__device__ __forceinline__ double flat_stage_entry(const ConvArgs& a, int f, int q) {
+  typedef const double __attribute__((address_space(1))) * GlobalPtr;
+  const uint64_t pm = reinterpret_cast<uint64_t>(a.mu) + (uint64_t)(uint32_t)f * (8u * FP::DZ);
+  const uint64_t pl = reinterpret_cast<uint64_t>(a.L) + (uint64_t)(uint32_t)f * (8u * FP::NL) - 8u * FP::DZ;
+  return *reinterpret_cast<GlobalPtr>((q < FP::DZ ? pm : pl) + 8u * (uint32_t)q);
+}
 #ifndef ROME_FLAT_PP
 #define ROME_FLAT_PP 1   // neighbouring particle pairs per thread of the packed sweep (Pose2 / Point2 factors).  Measured: 2 pairs per
                           // thread (fewer, fatter waves, one generation) need 96 VGPRs + spills and run 21.8 µs against 8.0 µs: one pair it is
@@ -425,52 +446,51 @@ __device__ __forceinline__ void conv_flat_body(const ConvArgs& a, int H, int CPB
   const bool live = lc_raw < CPB && c0 + lc_raw < a.n_conv;
   const int lc = lc_raw < CPB ? lc_raw : CPB - 1;
   const int c = min(c0 + lc, a.n_conv - 1);
-  const int4 row = *reinterpret_cast<const int4*>(a.rows4 + 4 * (size_t)c);
+  const int4 row = *row_ptr(reinterpret_cast<const int4*>(a.rows4), c, 16u);
   const int dr = (FP::kHypoDir < 0 || FP::kHypoDir == 2) ? row.y : a.dir_all;
   const int i0 = NP * j;                      // particles i0 .. i0 + NP - 1 (the tail of a row may be shorter)
+  const uint32_t sN = 8u * (uint32_t)N;       // byte strides: one coordinate, one block of the fixed / the target belief (uniform)
+  const uint32_t sF = (uint32_t)FP::DF * sN, sT = (uint32_t)FP::DT * sN;
   // ---- per-factor constants -> LDS: the first threads of every row load one entry each of THEIR OWN row's factor (the factor
   //      index arrives with the row they need anyway: the load is issued beside the belief loads, nothing waits for it here;
   //      branch-free: every thread loads SOME valid entry, only the first NK of a row publish theirs)
-  constexpr int KP = (FP::NK + 7) / 8;   // passes (H >= 8 threads per row)
-  double kst[KP];
-#pragma unroll
-  for (int e = 0; e < KP; ++e) {
-    const int q = min(j + e * H, FP::NK - 1);
-    const double* src = q < FP::DZ ? a.mu + (size_t)FP::DZ * row.x + q : a.L + (size_t)FP::NL * row.x + (q - FP::DZ);
-    kst[e] = *src;
-  }
-  const double* __restrict__ fb = a.bel_fixed + (size_t)row.z * FP::DF * N;
+  constexpr int KP = (FP::NK + 7) / 8;   // passes (H >= 8 threads per row); pass e serves entries [e·H, (e + 1)·H): with H >= NK / e
+  double kst[KP];                         // it has none, and the whole block skips it (H is uniform; the first pass always runs)
+  kst[0] = flat_stage_entry<FP>(a, row.x, min(j, FP::NK - 1));
+  // the fixed belief's block, entered at this thread's first particle (idle threads shadow particle 0): coordinate d lies d·N doubles on
   double fx[NP][FP::DF];
   [[maybe_unused]] double t0[NP][FP::DT];   // GAUSS_NEWTON: the start points u0 (the target's current belief): +24 B per Pose2 particle
 #pragma unroll
   for (int p = 0; p < PP; ++p) {
     const int ip = i0 + 2 * p;
+    const uint32_t o0 = 8u * (uint32_t)(ip < N ? ip : 0), o1 = 8u * (uint32_t)(ip + 1 < N ? ip + 1 : 0);
     if (VEC2) {   // (N even: a pair is inside the row or entirely beyond it)
-      const int ii = ip < N ? ip : 0;
+      const double* __restrict__ fb = row_ptr(a.bel_fixed, row.z, sF, o0);
 #pragma unroll
       for (int d = 0; d < FP::DF; ++d) {
-        const double2 v = *reinterpret_cast<const double2*>(fb + (size_t)d * N + ii);
+        const double2 v = *reinterpret_cast<const double2*>(fb + (size_t)d * N);
         fx[2 * p][d] = v.x; fx[2 * p + 1][d] = v.y;
       }
     } else {
+      const double* __restrict__ fb0 = row_ptr(a.bel_fixed, row.z, sF, o0);
+      const double* __restrict__ fb1 = row_ptr(a.bel_fixed, row.z, sF, o1);
 #pragma unroll
-      for (int d = 0; d < FP::DF; ++d) {
-        fx[2 * p][d] = fb[(size_t)d * N + (ip < N ? ip : 0)]; fx[2 * p + 1][d] = fb[(size_t)d * N + (ip + 1 < N ? ip + 1 : 0)];
-      }
+      for (int d = 0; d < FP::DF; ++d) { fx[2 * p][d] = fb0[(size_t)d * N]; fx[2 * p + 1][d] = fb1[(size_t)d * N]; }
     }
     if constexpr (SOLVER == kSolverGaussNewton) {
-      const double* __restrict__ tb = a.bel_target + (size_t)row.w * FP::DT * N;
+      const double* __restrict__ tb0 = row_ptr(a.bel_target, row.w, sT, o0);
+      const double* __restrict__ tb1 = row_ptr(a.bel_target, row.w, sT, o1);
 #pragma unroll
-      for (int d = 0; d < FP::DT; ++d) {
-        t0[2 * p][d] = tb[(size_t)d * N + (ip < N ? ip : 0)]; t0[2 * p + 1][d] = tb[(size_t)d * N + (ip + 1 < N ? ip + 1 : 0)];
-      }
+      for (int d = 0; d < FP::DT; ++d) { t0[2 * p][d] = tb0[(size_t)d * N]; t0[2 * p + 1][d] = tb1[(size_t)d * N]; }
     }
   }
+#pragma unroll
+  for (int e = 1; e < KP; ++e) kst[e] = e * H < FP::NK ? flat_stage_entry<FP>(a, row.x, min(j + e * H, FP::NK - 1)) : 0.0;   // (behind the belief loads: the branch splits no load group)
   // ---- measurement noise (depends on the row id only).  The two compiler fences keep the order {loads issued} -> {Philox /
   //      Box-Muller} -> {first use of a loaded value}, so that the generator runs under the load latency (left alone, the
   //      compiler sinks the generator below the LDS write and its s_waitcnt vmcnt(0))
   asm volatile("" ::: "memory");
-  const uint64_t stream = a.stream_offset + (uint64_t)c;
+  const uint64_t stream = a.stream_offset + (uint64_t)(uint32_t)c;   // (c >= 0: zero extension, the same counter)
   double xi[NP][FP::DZ];
 #pragma unroll
   for (int p = 0; p < PP; ++p) rng_normals_pair<FP::DZ>(a.seed, stream, (uint32_t)(i0 + 2 * p), xi[2 * p], xi[2 * p + 1]);
@@ -482,6 +502,7 @@ __device__ __forceinline__ void conv_flat_body(const ConvArgs& a, int H, int CPB
 #pragma unroll
   for (int e = 0; e < KP; ++e) {
     const int q = j + e * H;
+    if (e > 0 && e * H >= FP::NK) continue;
     if (lc_raw < CPB && q < FP::NK) s_K[lc * SLP + q] = kst[e];
   }
   __syncthreads();
@@ -515,32 +536,32 @@ __device__ __forceinline__ void conv_flat_body(const ConvArgs& a, int H, int CPB
   const uint64_t trace_t1 = wall_clock64();
 #endif
   if (!live) return;
-  double* __restrict__ ob = a.out + (size_t)c * FP::DT * N;
   const int mslot = (a.n_mirror > 0 || a.mirror_map) ? mirror_slot(a, c) : -1;
-  double* mb = mslot >= 0 ? a.mirror_out + (size_t)mslot * FP::DT * N : nullptr;
 #pragma unroll
   for (int p = 0; p < PP; ++p) {
     const int ip = i0 + 2 * p;
     if (ip >= N) continue;
     const bool act1 = ip + 1 < N;               // (odd N: the last pair is a single particle)
+    double* __restrict__ ob = row_ptr(a.out, c, sT, 8u * (uint32_t)ip);
+    double* mb = mslot >= 0 ? row_ptr(a.mirror_out, mslot, sT, 8u * (uint32_t)ip) : nullptr;
     if (VEC2) {
 #pragma unroll
       for (int d = 0; d < FP::DT; ++d) {
         const double2 v = {t[2 * p][d], t[2 * p + 1][d]};
         // streaming stores: the proposals are not read again by this launch; written through, they are not left dirty in the L2
         // for the end-of-kernel write-back (measured: 9.1 -> 7.8 µs per Manhattan sweep)
-        store_stream2(ob + (size_t)d * N + ip, v);
-        if (mb) store_stream2(mb + (size_t)d * N + ip, v);
+        store_stream2(ob + (size_t)d * N, v);
+        if (mb) store_stream2(mb + (size_t)d * N, v);
       }
     } else {
 #pragma unroll
       for (int d = 0; d < FP::DT; ++d) {
-        store_stream(ob + (size_t)d * N + ip, t[2 * p][d]); if (act1) store_stream(ob + (size_t)d * N + ip + 1, t[2 * p + 1][d]);
-        if (mb) { store_stream(mb + (size_t)d * N + ip, t[2 * p][d]); if (act1) store_stream(mb + (size_t)d * N + ip + 1, t[2 * p + 1][d]); }
+        store_stream(ob + (size_t)d * N, t[2 * p][d]); if (act1) store_stream(ob + (size_t)d * N + 1, t[2 * p + 1][d]);
+        if (mb) { store_stream(mb + (size_t)d * N, t[2 * p][d]); if (act1) store_stream(mb + (size_t)d * N + 1, t[2 * p + 1][d]); }
       }
     }
 #ifndef ROME_FLAT_TRACE
-    if (a.status) { a.status[(size_t)c * N + ip] = st[2 * p]; if (act1) a.status[(size_t)c * N + ip + 1] = st[2 * p + 1]; }
+    if (a.status) { int* sb = row_ptr(a.status, c, 4u * (uint32_t)N, 4u * (uint32_t)ip); sb[0] = st[2 * p]; if (act1) sb[1] = st[2 * p + 1]; }
 #endif
   }
 #ifdef ROME_FLAT_TRACE
@@ -705,6 +726,9 @@ static hipError_t launch_flat(const ConvArgs& a, hipStream_t s) {
   for (int t = 0; t < kFlatThreads; ++t) if ((int)(((uint32_t)t * magic) >> 16) != t / H) return hipErrorInvalidValue;
   const int nb = (a.n_conv + CPB - 1) / CPB;
   if (nb == 0) return hipSuccess;
+  // the kernel forms a row's address as index x byte stride in 32 x 32 -> 64 bits (row_ptr): one block of either belief has to span
+  // less than 2^32 bytes (always, at the N <= 512 this launch is reached with)
+  if ((uint64_t)(FP::DF > FP::DT ? FP::DF : FP::DT) * 8u * (uint64_t)a.N > 0xFFFFFFFFull) return hipErrorInvalidValue;
   // 16-byte accesses need an even N (row starts stay 16-byte aligned) and 16-byte aligned arrays
   const bool vec2 = (a.N % 2 == 0) && (((uintptr_t)a.bel_fixed | (uintptr_t)a.out | (uintptr_t)a.mirror_out) % 16 == 0);
   // (the functor evaluation is a separate instantiation: compiled into the plain sweep it would pin its register allocation)

@@ -170,21 +170,29 @@ __device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1
 
 enum : uint32_t { kDomainNoise = 1u, kDomainEntropy = 2u };
 
+// The correctly rounded single-precision square root for NORMAL, FINITE x >= 2^-96: the hardware estimate v_sqrt_f32 (within 1 ulp)
+// and the residual test against its two neighbours -- s_down·s >= x takes the lower one, s_up·s < x the upper one (each residual one
+// fma, exact in sign).  The same bits as __builtin_sqrtf on that whole range (tests/test_gpu_sqrt32.py compares every float of it),
+// without what the general expansion adds around this sequence: the 2^32 scaling of inputs below 2^-96 and its unscale, and the
+// pass-through of 0 and inf -- seven instructions per call.  NOT valid for zero, denormal, tiny, infinite or NaN arguments.
+__device__ __forceinline__ float sqrt32_rn_normal(float x) {
+#pragma clang fp contract(off)
+  const float s = __builtin_amdgcn_sqrtf(x);
+  const float s_down = __uint_as_float(__float_as_uint(s) - 1u), s_up = __uint_as_float(__float_as_uint(s) + 1u);
+  const float r_down = __builtin_fmaf(-s_down, s, x), r_up = __builtin_fmaf(-s_up, s, x);
+  float r = r_down <= 0.0f ? s_down : s;
+  r = r_up > 0.0f ? s_up : r;
+  return r;
+}
+
 __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {  // (0,1]
   const uint64_t x = ((uint64_t)hi << 32) | lo;
   return (double)((x >> 11) + 1) * (1.0 / 9007199254740992.0);
 }
 
-// One Box-Muller pair from two Philox words.  The transform is defined in IEEE single-precision operations (explicit fmaf
-// only, contraction off) -- the same function, bit for bit, as ro_box_muller in oracle/rome_oracle.c:
-//   radius  u1 = x·2^-32, x = float(wa) + 1 in [1, 2^32]: -ln u1 = (32 - e) ln2 - ln m, x = m·2^e, ln m a degree-7 polynomial
-//           in m - 1.5 (|error| <= 2.7e-7; no division, no library log);
-//   angle   a = (π/4)·int32(wb << 2)·2^-31 in [-π/4, π/4): the direction (cos a - sin a, cos a + sin a)/√2 is the angle π/4 + a,
-//           uniform on the first quadrant; bits 31 / 30 of wb mirror it into the other three (no range reduction at all);
-//   n0 = ±√(-ln u1)·(c - s), n1 = ±√(-ln u1)·(c + s).
-// ≈ 50 VALU instructions per pair, none in double precision but the final conversions (the FP64 log / sqrt / sincos form it
-// replaces: ≈ 135); draws carry 24-bit mantissas.
-__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, double* n0, double* n1) {
+// The radius argument h = -ln u1 of box_muller (below) for the radius word wa; its own function so that tests/hip/sqrt32_check.hip can
+// walk every wa.
+__device__ __forceinline__ float box_muller_h(uint32_t wa) {
 #pragma clang fp contract(off)
   const float x = (float)wa + 1.0f;
   const uint32_t xb = __float_as_uint(x);
@@ -198,8 +206,25 @@ __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, double* n0,
   p = __builtin_fmaf(p, t, -0x1.c72898p-3f);
   p = __builtin_fmaf(p, t, 0x1.555544p-1f);
   p = __builtin_fmaf(p, t, 0x1.9f324cp-2f);
-  const float h = __builtin_fmaf(ke, 0x1.62e43p-1f, -p);
-  const float rr = h > 0.0f ? __builtin_sqrtf(h) : 0.0f;   // IEEE single-precision square root (correctly rounded expansion)
+  return __builtin_fmaf(ke, 0x1.62e43p-1f, -p);
+}
+
+// One Box-Muller pair from two Philox words.  The transform is defined in IEEE single-precision operations (explicit fmaf
+// only, contraction off) -- the same function, bit for bit, as ro_box_muller in oracle/rome_oracle.c:
+//   radius  u1 = x·2^-32, x = float(wa) + 1 in [1, 2^32]: -ln u1 = (32 - e) ln2 - ln m, x = m·2^e, ln m a degree-7 polynomial
+//           in m - 1.5 (|error| <= 2.7e-7; no division, no library log);
+//   angle   a = (π/4)·int32(wb << 2)·2^-31 in [-π/4, π/4): the direction (cos a - sin a, cos a + sin a)/√2 is the angle π/4 + a,
+//           uniform on the first quadrant; bits 31 / 30 of wb mirror it into the other three (no range reduction at all);
+//   n0 = ±√(-ln u1)·(c - s), n1 = ±√(-ln u1)·(c + s).
+// ≈ 50 VALU instructions per pair, none in double precision but the final conversions (the FP64 log / sqrt / sincos form it
+// replaces: ≈ 135); draws carry 24-bit mantissas.
+__device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, double* n0, double* n1) {
+#pragma clang fp contract(off)
+  const float h = box_muller_h(wa);
+  // IEEE single-precision square root, correctly rounded.  h = (32 - e) ln2 - ln m is 0, negative (the top ~900 radius words, x within
+  // 2.7e-7 of 2^32: the polynomial's error) or at least 2^-47 (ke·ln2 and p are multiples of 2^-47): where the select takes the root
+  // its argument is normal, far above 2^-96 (the second pass of tests/hip/sqrt32_check.hip runs every radius word through this h)
+  const float rr = h > 0.0f ? sqrt32_rn_normal(h) : 0.0f;
   const float a = (float)(int32_t)(wb << 2) * 0x1.921fb6p-32f;
   const float z = a * a;
   float sp = __builtin_fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f);
