@@ -143,7 +143,10 @@ __device__ __forceinline__ void lcv_g64(const double (&x)[2], const bool (&act)[
   // exponent a·d²·log2(e) is formed in double and rounded once to single precision (absolute error <= 2e-6 for every weight that
   // matters, i.e. a relative error of ~1e-6 in w_ij, random over the pairs), which moves the Newton step by ~1e-8 h -- two orders
   // below the 2e-6 at which the reference's stored heading bandwidths are reproduced -- at a third of the cost of a double-precision
-  // exponential per ordered pair (0.28 -> 0.13 ms of the 1.5 ms of a Manhattan sweep of proposals).
+  // exponential per ordered pair (0.28 -> 0.13 ms of the 1.5 ms of a Manhattan sweep of proposals).  Measured against an independent
+  // double-precision root of g (tests/test_gpu_kde_shapes.py, every launch shape, Euclidean, concentrated and wrapped circular data):
+  // the returned bandwidth lies within 0.6e-8 .. 3.9e-8 h of the root, the largest at B = 13 -- the weight rounding AND what one
+  // Newton step leaves of a secant result that is 1e-4 off.
   const double a = -0.5 / (h * h) * 1.4426950408889634074;
   double S[2] = {0.0, 0.0}, T[2] = {0.0, 0.0}, Q[2] = {0.0, 0.0};
   for (int j = 0; j < N; ++j) {
