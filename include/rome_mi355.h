@@ -10,6 +10,8 @@
  *     Point2Point2Range          src/factors/Range2D.jl:8-17
  *     Pose2Point2Range           src/factors/Range2D.jl:40-54        (partial = (1, 2) on the pose)
  *     Pose2Point2Bearing         src/factors/Bearing2D.jl:10-32
+ *     Pose3Pose3XYYaw            src/factors/PartialPose3.jl:101-136  (partial = (1, 2, 6))
+ *     PriorPose3ZRP              src/factors/PartialPose3.jl:12-46    (partial = (3, 4, 5))
  * (paths relative to the RoME.jl v0.24.6 checkout).  Each entry point names the reference
  * interface it replaces.  Plain pointers and sizes only; no exceptions cross the ABI; the library
  * never retains caller pointers past a call.  There is NO CPU fallback: without a HIP device
@@ -42,7 +44,7 @@
 extern "C" {
 #endif
 
-#define ROME_MI355_VERSION 122 /* 0.1.22 (appended since, the number unchanged: ROME_BLOCKOP_COMPOSE on Pose3 blocks, ROME_BLOCKOP_ANCHOR_MEAN, p3p3_meas at the end of rome_clique_host -- solveTree as variable elimination on Pose3 graphs): ROME_BLOCKOP_COMPOSE / MIX, rome_blockop_plan_create_ex (round 6: solveTree as variable elimination in relative-factor algebra); rome_ctx_set_stream orders streams by event.  0.1.21: store-resident messages (smsg_*) in rome_clique_upsolve_host (a tree level reads its children's separator beliefs from HBM); multihypo / nullhypo / stream-id columns in rome_clique_host; rome_store + rome_upsolve_plan
+#define ROME_MI355_VERSION 122 /* 0.1.22 (appended since, the number unchanged: the partial Pose3 entries rome_*_pose3pose3xyyaw* / rome_conv_priorpose3zrp*;ROME_BLOCKOP_COMPOSE on Pose3 blocks, ROME_BLOCKOP_ANCHOR_MEAN, p3p3_meas at the end of rome_clique_host -- solveTree as variable elimination on Pose3 graphs): ROME_BLOCKOP_COMPOSE / MIX, rome_blockop_plan_create_ex (round 6: solveTree as variable elimination in relative-factor algebra); rome_ctx_set_stream orders streams by event.  0.1.21: store-resident messages (smsg_*) in rome_clique_upsolve_host (a tree level reads its children's separator beliefs from HBM); multihypo / nullhypo / stream-id columns in rome_clique_host; rome_store + rome_upsolve_plan
                                  * (device-resident clique up-solves: beliefs stay in HBM across frontiers) */
 
 enum {
@@ -270,6 +272,42 @@ int rome_conv_pose2point2bearing(rome_ctx*, const rome_opts*, int32_t C, int32_t
                                  const double* mu /*C*/, const double* sigma /*C*/,
                                  const double* fixed, const double* noise /*C*N*1 or NULL*/,
                                  double* target_inout, int32_t* status);
+/* Partial Pose3 factors (src/factors/PartialPose3.jl; IIF is not vendored: these are the readings this library pins).
+ * The partial rule of Pose2Point2Range on a Pose3 target: the spread over the whole variable (all six tangent coordinates), entropy and
+ * solve on the partial coordinates only, every other coordinate of every particle returned BIT FOR BIT in the coordinate layouts.
+ * The entropy is ADDITIVE on the partial coordinates, c[k] += spread (u[k] − ½) with u the d = 6 entropy draw (three of the six used):
+ * the compose form u0 ∘ exp(e) of Pose3Pose3 would move the other coordinates as soon as the pose is tilted.
+ * nullhypo (opts->nullhypo) is honoured: null particles keep every coordinate and receive spread_nh entropy on the partial coordinates
+ * only.  Multihypo is not supported (ROME_ERR_INVALID_ARG from the _dev entries when alt_var / hypo_w is set).
+ *
+ * Yaw of a Pose3: ψ(R) = atan2(R21, R11), from the first column of R (:120-128 normalises that column, which does not change the
+ *   atan2); the x-axis vertical (R11 = R21 = 0): ψ = 0, the library's atan2(0, 0).
+ * Pose3Pose3XYYaw(Z) over [p, q], partial = (1, 2, 6) (:101-136), dz = dr = 3: with p₂ = (p.t_xy, ψ(R_p)), q₂ likewise, the residual is the
+ *   Pose2Pose2 residual of (z, p₂, q₂) (the same device function).  rome_residual_pose3pose3xyyaw: rows of coordinates; _pt: p, q as
+ *   native points (n*12).
+ *   Convolution: dir[c] 0 solves q from p, 1 solves p from q (NULL: all 0); mu [C][3], cov [C][9], z = μ + Lξ (the d = 3 normal rule of
+ *   Pose2Pose2); noise [C][N][3].  Unknowns: the target's (x, y, ω_z).  (ψ*, t*) = what the factor predicts for the target:
+ *     dir 0: ψ* = ψ_p + z_θ, t* = p.t_xy + R₂(ψ_p) z_xy;   dir 1: ψ* = ψ_q − z_θ, t* = q.t_xy − R₂(ψ_p) z_xy, ψ_p the yaw of the returned p.
+ *   xy is that closed form; ω_z = s solves g(s) = wrap(ψ(Exp(ω_x, ω_y, s)) − ψ*) = 0 by Newton's rule, ∂ψ/∂s from dR = R hat(J_r(ω) e₃) ds.
+ *   CLOSED_FORM / NEWTON: from s₀ = wrap_π(ψ*), the principal branch (exact in one evaluation on an upright pose), at most max_iters steps
+ *     to |g| <= tol; the start points' ω_z is not read.  NEWTON with a status array: the functor at the returned point, 0 iff max|r| <= tol.
+ *   GAUSS_NEWTON: the same iteration from the start particle's own ω_z, the functor at every iterate (xy by the closed form); one pass,
+ *     status 1 at the cap.  It lands on the principal-branch root when the start lies within π of it, else on the neighbouring branch
+ *     (the same rotation where the pose is upright; documented behaviour).
+ *   NELDER_MEAD: nelder_mead<3> on Σr² over (x, y, ω_z), inflate_cycles x {entropy, minimise}: the only solver that cycles.
+ * PriorPose3ZRP(z, rp), partial = (3, 4, 5) (:12-46), dz = 3: mu [C][3] = (μ_z, μ_roll, μ_pitch), sigma_z [C], cov_rp [C][4].  Per
+ *   particle z_s = μ_z + σ_z ξ₀, (r, p) = μ_rp + L_rp (ξ₁, ξ₂), R = R_y(p) R_x(r) (RotYX(p, r), :32), ω = Log R; the sample is
+ *   (z_s, ω_x, ω_y) -- ω_z is dropped (:41-45); under ROME_NOISE_MEASUREMENTS the noise rows [C][N][3] are those three coordinates.
+ *   The proposal is the target's OWN particle with coordinates 3, 4, 5 replaced: a prior row that reads the target belief.  No
+ *   iteration, no cycles: every solver returns the same thing; no status.                                                          */
+int rome_residual_pose3pose3xyyaw(rome_ctx*, int32_t n, const double* z /*n*3*/, const double* p /*n*6*/, const double* q /*n*6*/, double* r /*n*3*/);
+int rome_residual_pose3pose3xyyaw_pt(rome_ctx*, int32_t n, const double* z /*n*3*/, const double* p_pt /*n*12*/, const double* q_pt /*n*12*/, double* r /*n*3*/);
+int rome_conv_pose3pose3xyyaw(rome_ctx*, const rome_opts*, int32_t C, const int32_t* dir /*[C] or NULL*/,
+                              const double* mu /*C*3*/, const double* cov /*C*9*/,
+                              const double* fixed /*C*N*6*/, const double* noise /*C*N*3 or NULL*/,
+                              double* target_inout /*C*N*6*/, int32_t* status);
+int rome_conv_priorpose3zrp(rome_ctx*, const rome_opts*, int32_t C, const double* mu /*C*3*/, const double* sigma_z /*C*/,
+                            const double* cov_rp /*C*4*/, const double* noise /*C*N*3 or NULL*/, double* target_inout /*C*N*6*/);
 /* Prior "convolution" = N samples of the prior as points: IIF samplePoint on PriorPose2.Z / PriorPose3.Z
  * (src/factors/PriorPose2.jl:13-17, src/factors/Pose3D.jl:8-12).                                 */
 int rome_sample_priorpose2(rome_ctx*, const rome_opts*, int32_t C, const double* mu /*C*3*/, const double* cov /*C*9*/,
@@ -547,6 +585,12 @@ int rome_conv_point2point2range_dev(rome_ctx*, const rome_opts*, const rome_conv
 int rome_conv_pose2point2range_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 /* bearing-only factor on device tables: L = [F][1] sigma; dir_all (0 landmark, 1 pose), dir must be NULL; no multihypo */
 int rome_conv_pose2point2bearing_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
+/* partial Pose3 factors on device tables; no multihypo (alt_var / hypo_w -> INVALID_ARG).  pose3pose3xyyaw: mu [F][3], L = [F][6] packed
+ * Cholesky, the row direction from rows4 / dir / dir_all (0 or 1).  priorpose3zrp: mu [F][3], L = [F][4] = (σ_z, packed 2x2 Cholesky of the
+ * roll / pitch covariance); rows (factor, 0, var, var): bel_target is READ (the proposal is the target's own particle with coordinates
+ * 3, 4, 5 replaced), bel_fixed may be NULL; status, when given, receives zeros */
+int rome_conv_pose3pose3xyyaw_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
+int rome_conv_priorpose3zrp_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 /* The whole convolution sweep of a Pose2 / Point2 graph (odometry + bearing-range sightings: MIT.g2o with landmarks, the beehive) in ONE
  * call: the Pose2Pose2 (+ PriorPose2 rows) table, the bearing-range -> pose table (dir_all = 1) and the bearing-range -> landmark table
  * (dir_all = 0); any of them may be NULL.  Philox stream of row r of family k = opts->stream_offset + family_stream_offset[k] + r

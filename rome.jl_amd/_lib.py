@@ -86,7 +86,13 @@ SIGNATURES = {
     "rome_residual_pose2point2bearing_pt": (C.c_int, [_CTX, C.c_int32, _PD, _PD, _PD, _PD]),
     "rome_conv_pose2point2bearing": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PI]),
     "rome_conv_pose2point2bearing_dev": (C.c_int, [_CTX, _PO, _PT]),
-    "rome_conv_pose2pose2_mh": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI]),
+    "rome_residual_pose3pose3xyyaw": (C.c_int, [_CTX, C.c_int32, _PD, _PD, _PD, _PD]),
+    "rome_residual_pose3pose3xyyaw_pt": (C.c_int, [_CTX, C.c_int32, _PD, _PD, _PD, _PD]),
+    "rome_conv_pose3pose3xyyaw": (C.c_int, [_CTX, _PO, C.c_int32, _PI, _PD, _PD, _PD, _PD, _PD, _PI]),
+    "rome_conv_priorpose3zrp": (C.c_int, [_CTX, _PO, C.c_int32, _PD, _PD, _PD, _PD, _PD]),
+    "rome_conv_pose3pose3xyyaw_dev": (C.c_int, [_CTX, _PO, _PT]),
+    "rome_conv_priorpose3zrp_dev": (C.c_int, [_CTX, _PO, _PT]),
+    "rome_conv_pose2pose2_mh":(C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI]),
     "rome_conv_pose3pose3": (C.c_int, [_CTX, _PO, C.c_int32, _PI, _PD, _PD, _PD, _PD, _PD, _PI]),
     "rome_sample_priorpose2": (C.c_int, [_CTX, _PO, C.c_int32, _PD, _PD, _PD, _PD]),
     "rome_sample_priorpose3": (C.c_int, [_CTX, _PO, C.c_int32, _PD, _PD, _PD, _PD]),

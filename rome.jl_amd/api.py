@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3,
-                      PriorPose3, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, getCoordinates)
+                      PriorPose3, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, getCoordinates)
 
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
@@ -105,10 +105,21 @@ def residual_pose2point2bearing_pt(z, p_pt, l, ctx=None):
     return _rows(_lib.load().rome_residual_pose2point2bearing_pt, ctx, (z, p_pt, l), (1, 6, 2), 1)[:, 0]
 
 
+def residual_pose3pose3xyyaw(z, p, q, ctx=None):
+    """the Pose2Pose2 residual of the SE(2) projections (t_xy, yaw) of p and q per row (PartialPose3.jl:116-136): z (n, 3) = (x, y, θ),
+    p / q (n, 6) Pose3 coordinates -> (n, 3)"""
+    return _rows(_lib.load().rome_residual_pose3pose3xyyaw, ctx, (z, p, q), (3, 6, 6), 3)
+
+
+def residual_pose3pose3xyyaw_pt(z, p_pt, q_pt, ctx=None):
+    """the same with the poses as native points (n, 12)"""
+    return _rows(_lib.load().rome_residual_pose3pose3xyyaw_pt, ctx, (z, p_pt, q_pt), (3, 12, 12), 3)
+
+
 def _meas_coords(factor, meas):
     """Accepts the reference's tangent containers (hat form) or plain coordinates."""
     m = np.asarray(meas, dtype=np.float64).ravel()
-    if isinstance(factor, (Pose2Pose2, PriorPose2)):
+    if isinstance(factor, (Pose2Pose2, PriorPose2, Pose3Pose3XYYaw)):   # (XYYaw: an SE(2) tangent, getManifold PartialPose3.jl:112)
         if m.size == 3:
             return m
         if m.size == 6:  # ((x,y), [0 -θ; θ 0]) column-major
@@ -159,6 +170,10 @@ def calcFactorResidualTemporary(factor, vartypes, meas, points, ctx=None):
         if pts[0].size == 6:
             return residual_pose2point2bearing_pt(z, [pts[0]], [pts[1]], ctx)[0]
         return residual_pose2point2bearing(z, [pts[0]], [pts[1]], ctx)[0]
+    if isinstance(factor, Pose3Pose3XYYaw):
+        if pts[0].size == 12:
+            return residual_pose3pose3xyyaw_pt([z], [pts[0]], [pts[1]], ctx)[0]
+        return residual_pose3pose3xyyaw([z], [pts[0]], [pts[1]], ctx)[0]
     if isinstance(factor, Pose3Pose3):
         if pts[0].size == 12:
             return residual_pose3pose3_pt([z], [pts[0]], [pts[1]], ctx)[0]
@@ -445,6 +460,48 @@ def conv_pose3pose3(opts, mu, cov, fixed, target, dirs=None, noise=None, want_st
     _lib.check(_lib.load().rome_conv_pose3pose3(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(cov), _p(fixed),
                                                _p(noise), _p(out), _pi(st)), ctx.handle)
     return (out, st) if want_status else out
+
+
+def _with_nullhypo(opts, nullhypo):
+    if nullhypo is None:
+        return opts
+    o = _lib.Opts.from_buffer_copy(opts)
+    o.nullhypo = float(nullhypo)
+    return o
+
+
+def conv_pose3pose3xyyaw(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None):
+    """C Pose3Pose3XYYaw convolutions (PartialPose3.jl:101-136): mu (C, 3), cov (C, 3, 3), dirs (C,) or None (0: solve q from p, 1: solve p
+    from q), fixed / target C Pose3 blocks, noise C blocks of three standard normals per particle (or the (x, y, θ) samples themselves under
+    presampled=NOISE_MEASUREMENTS).  Solves the target's (x, y, ω_z); every particle's z, ω_x, ω_y is returned unchanged (bit for bit
+    in the coordinate layouts).  nullhypo: the fraction of particles the factor does not apply to (opts.nullhypo when None)."""
+    ctx = ctx or default_context()
+    opts = _with_nullhypo(_with_layout(opts, layout), nullhypo)
+    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
+    mu = _d(mu, (C_, 3)); cov = _d(cov, (C_, 3, 3))
+    fixed = _blocks(fixed, C_, N, 6, opts.layout)
+    out = _blocks(target, C_, N, 6, opts.layout).copy()
+    noise = None if noise is None else _blocks(noise, C_, N, 3, opts.layout, points_ok=False)
+    dirs = None if dirs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dirs, dtype=np.int32), (C_,)))
+    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
+    _lib.check(_lib.load().rome_conv_pose3pose3xyyaw(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(cov), _p(fixed),
+                                                    _p(noise), _p(out), _pi(st)), ctx.handle)
+    return (out, st) if want_status else out
+
+
+def conv_priorpose3zrp(opts, mu, sigma_z, cov_rp, target, noise=None, ctx=None, layout=None, nullhypo=None):
+    """C PriorPose3ZRP rows (PartialPose3.jl:12-46): mu (C, 3) = (μ_z, μ_roll, μ_pitch), sigma_z (C,), cov_rp (C, 2, 2), target C Pose3
+    blocks -> the same blocks with coordinates 3, 4, 5 (z, ω_x, ω_y) replaced by the samples; x, y, ω_z unchanged (bit for bit in the
+    coordinate layouts).  noise: C blocks of three standard normals per particle (or the three sample coordinates themselves under
+    presampled=NOISE_MEASUREMENTS)."""
+    ctx = ctx or default_context()
+    opts = _with_nullhypo(_with_layout(opts, layout), nullhypo)
+    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
+    mu = _d(mu, (C_, 3)); sigma_z = _d(np.atleast_1d(_d(sigma_z)).ravel(), (C_,)); cov_rp = _d(cov_rp, (C_, 2, 2))
+    out = _blocks(target, C_, N, 6, opts.layout).copy()
+    noise = None if noise is None else _blocks(noise, C_, N, 3, opts.layout, points_ok=False)
+    _lib.check(_lib.load().rome_conv_priorpose3zrp(ctx.handle, C.byref(opts), C_, _p(mu), _p(sigma_z), _p(cov_rp), _p(noise), _p(out)), ctx.handle)
+    return out
 
 
 def _sample_prior(fn, d, opts, mu, cov, noise, ctx):

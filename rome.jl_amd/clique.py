@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib, api
 from .device import DeviceGraph
 from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2,
-                      refuse_range, refuse_bearing)
+                      refuse_range, refuse_bearing, refuse_partial3)
 
 # Philox offsets of the families of rome_clique_proposals: DeviceGraph's ("prpt2" is this layer's name for its priorpt2)
 FAMILY_STREAM = {"p2p2": DeviceGraph.STREAM_P2P2, "br1": DeviceGraph.STREAM_BR1, "br0": DeviceGraph.STREAM_BR0, "p3p3": DeviceGraph.STREAM_P3P3,
@@ -85,6 +85,7 @@ class CliqueBatch:
     def __init__(self, fg, pairs, var_index=None, stream_ids=None):
         refuse_range([fg.getFactor(fl)[2] for fl, _ in pairs], "CliqueBatch")
         refuse_bearing([fg.getFactor(fl)[2] for fl, _ in pairs], "CliqueBatch")
+        refuse_partial3([fg.getFactor(fl)[2] for fl, _ in pairs], "CliqueBatch")
         self.fg, self.N = fg, fg.N
         self.vars = {Pose2: [], Point2: [], Pose3: []}
         self.vidx = {}
@@ -345,6 +346,7 @@ class DeviceStore(LibHandle):
     def __init__(self, fg, ctx=None, wrap=None, upload=True):
         refuse_range([f for _, _, f in fg.factors], "DeviceStore")
         refuse_bearing([f for _, _, f in fg.factors], "DeviceStore")
+        refuse_partial3([f for _, _, f in fg.factors], "DeviceStore")
         self.ctx = ctx or api.default_context()
         self._lib = _lib.load()
         self.fg, self.N = fg, fg.N

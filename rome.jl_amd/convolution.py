@@ -3,7 +3,7 @@ test/testBasicPose2Conv.jl:25, test/TestPoseAndPoint2Constraints.jl:36,97)."""
 import numpy as np
 
 from . import _lib, api
-from .factors import Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing
+from .factors import Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP
 
 
 def approxConv(fg, flabel, target, solver=_lib.SOLVER_NEWTON, seed=None, ctx=None, **optkw):
@@ -19,6 +19,9 @@ def approxConv(fg, flabel, target, solver=_lib.SOLVER_NEWTON, seed=None, ctx=Non
         return api.sample_priorpose3(opts, [f.Z.mu], [f.Z.cov], ctx=ctx)[0]
     if isinstance(f, PriorPoint2):
         return api.sample_priorpoint2(opts, [f.Z.mu], [f.Z.cov], ctx=ctx)[0]
+    if isinstance(f, PriorPose3ZRP):   # a partial prior: the target's own belief with z, ω_x, ω_y replaced (zeros before it has one)
+        u0 = fg.getVal(target)[None] if fg.isInitialized(target) else np.zeros((1, 6, fg.N))
+        return api.conv_priorpose3zrp(opts, [[f.z.mu, f.rp.mu[0], f.rp.mu[1]]], [f.z.sigma], [f.rp.cov], u0, ctx=ctx)[0]
     mh = fg.multihypo.get(flabel)
     if mh is not None and isinstance(f, Pose2Pose2):   # Pose2Pose2 over [a, b1, b2]
         a, b1, b2 = labels
@@ -49,6 +52,8 @@ def approxConv(fg, flabel, target, solver=_lib.SOLVER_NEWTON, seed=None, ctx=Non
         return api.conv_pose2pose2(opts, [f.Z.mu], [f.Z.cov], fixed, u0, dirs=[direction], ctx=ctx)[0]
     if isinstance(f, Pose3Pose3):
         return api.conv_pose3pose3(opts, [f.Z.mu], [f.Z.cov], fixed, u0, dirs=[direction], ctx=ctx)[0]
+    if isinstance(f, Pose3Pose3XYYaw):
+        return api.conv_pose3pose3xyyaw(opts, [f.Z.mu], [f.Z.cov], fixed, u0, dirs=[direction], ctx=ctx)[0]
     if isinstance(f, Pose2Point2BearingRange):
         return api.conv_pose2point2br(opts, direction, [[f.bearing.mu, f.range.mu]], [[f.bearing.sigma, f.range.sigma]],
                                       fixed, u0, ctx=ctx)[0]

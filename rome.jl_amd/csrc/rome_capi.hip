@@ -157,7 +157,7 @@ int cholesky_one(int d, const double* cov, double* Lp) {
   return ROME_OK;
 }
 
-enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2, kP2R, kPPR, kPB };
+enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2, kP2R, kPPR, kPB, kP3XYY, kP3ZRP };
 
 // common host-pointer path: stage -> launch -> fetch
 int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const int32_t* dir, int dir_all,
@@ -243,6 +243,8 @@ int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const i
     case kP2R: e = launch_conv_point2point2range(a, o->solver, s); break;
     case kPPR: e = launch_conv_pose2point2range(a, o->solver, s); break;
     case kPB: e = launch_conv_pose2point2bearing(a, o->solver, s); break;
+    case kP3XYY: e = launch_conv_pose3pose3xyyaw(a, o->solver, s); break;
+    case kP3ZRP: e = launch_conv_priorpose3zrp(a, s); break;
   }
   ROME_HIP(ctx, e);
   if (status) ROME_HIP(ctx, hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)C * N, hipMemcpyDeviceToHost, s));
@@ -415,6 +417,16 @@ int rome_residual_pose3pose3_pt(rome_ctx* c, int32_t n, const double* z, const d
   return host_rows(c, n, in, 3, r, 6, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
     return launch_residual_pose3pose3(n, a, b, d, 1, o, s); });
 }
+int rome_residual_pose3pose3xyyaw(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
+  RowBuf in[3] = {{z, 3}, {p, 6}, {q, 6}};
+  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
+    return launch_residual_pose3pose3xyyaw(n, a, b, d, 0, o, s); });
+}
+int rome_residual_pose3pose3xyyaw_pt(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
+  RowBuf in[3] = {{z, 3}, {p, 12}, {q, 12}};
+  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
+    return launch_residual_pose3pose3xyyaw(n, a, b, d, 1, o, s); });
+}
 int rome_residual_priorpose3(rome_ctx* c, int32_t n, const double* m, const double* p, double* r) {
   RowBuf in[2] = {{m, 6}, {p, 6}};
   return host_rows(c, n, in, 2, r, 6, [&](const double* a, const double* b, const double*, double* o, hipStream_t s) {
@@ -514,6 +526,30 @@ int rome_conv_pose2point2bearing(rome_ctx* c, const rome_opts* o, int32_t C, int
   for (int i = 0; i < C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;  /* sigma < 0 encodes Uniform(mu ± |sigma|) */
   return host_conv(c, o, kPB, C, nullptr, dir, 1, dir == 0 ? 3 : 2, dir == 0 ? 2 : 3, mu, sigma, 1, fixed, noise, target_inout, status);
 }
+int rome_conv_pose3pose3xyyaw(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* cov,
+                              const double* fixed, const double* noise, double* target_inout, int32_t* status) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || C < 0 || (C > 0 && (!mu || !cov || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
+  if (C == 0) return ROME_OK;
+  if (dir) for (int i = 0; i < C; ++i) if (dir[i] != 0 && dir[i] != 1) return ROME_ERR_INVALID_ARG;
+  std::vector<double> L((size_t)C * 6);
+  if ((rc = rome_cholesky_lower(3, C, cov, L.data()))) return rc;
+  return host_conv(c, o, kP3XYY, C, dir, 0, 3, 6, 6, mu, L.data(), 6, fixed, noise, target_inout, status);
+}
+int rome_conv_priorpose3zrp(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* sigma_z, const double* cov_rp,
+                            const double* noise, double* target_inout) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || C < 0 || (C > 0 && (!mu || !sigma_z || !cov_rp || !target_inout))) return ROME_ERR_INVALID_ARG;
+  if (C == 0) return ROME_OK;
+  std::vector<double> L((size_t)C * 4);   // [σ_z, packed 2x2 Cholesky of the roll / pitch covariance]
+  for (int i = 0; i < C; ++i) {
+    if (!(sigma_z[i] >= 0.0)) return ROME_ERR_NOT_POSDEF;
+    L[4 * (size_t)i] = sigma_z[i];
+    if ((rc = rome_cholesky_lower(2, 1, cov_rp + 4 * (size_t)i, L.data() + 4 * (size_t)i + 1))) return rc;
+  }
+  // a prior row that reads the target belief: the table's fixed block IS the target block (staged once more; the kernel does not read it)
+  return host_conv(c, o, kP3ZRP, C, nullptr, 0, 3, 6, 6, mu, L.data(), 4, target_inout, noise, target_inout, nullptr);
+}
 int rome_sample_priorpose2(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* cov, const double* noise, double* out) {
   int rc = check_opts(o); if (rc) return rc;
   if (!c || C < 0 || (C > 0 && (!mu || !cov || !out))) return ROME_ERR_INVALID_ARG;
@@ -581,6 +617,20 @@ int rome_conv_pose2point2bearing_dev(rome_ctx* c, const rome_opts* o, const rome
 }
 int rome_conv_pose3pose3_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
   return dev_launch(c, o, t, true, launch_conv_pose3pose3);
+}
+int rome_conv_pose3pose3xyyaw_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
+  if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;   // no multihypo on the partial Pose3 factors
+  if (t && !t->dir && !t->rows4 && t->dir_all != 0 && t->dir_all != 1) return ROME_ERR_INVALID_ARG;
+  return dev_launch(c, o, t, true, launch_conv_pose3pose3xyyaw);
+}
+int rome_conv_priorpose3zrp_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
+  if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;
+  int rc = dev_common(c, o, t, false); if (rc) return rc;
+  if (t->n_conv > 0 && !t->bel_target) return ROME_ERR_INVALID_ARG;   // the target belief is read: the proposal is its own particle, partly replaced
+  ConvArgs a; args_from_dev(a, o, t);
+  a.bel_fixed = a.bel_target;   // (fixed = target in every row; the block is not read)
+  ROME_HIP(c, launch_conv_priorpose3zrp(a, c->stream));
+  return ROME_OK;
 }
 int rome_sample_priorpose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
   return dev_launch(c, o, t, false, [](const ConvArgs& a, int, hipStream_t s) { return launch_sample_priorpose2(a, s); });

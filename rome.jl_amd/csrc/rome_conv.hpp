@@ -1,5 +1,5 @@
 // rome_conv.hpp -- batched factor-convolution kernels for gfx950 (MI355X): the kernel bodies and launch templates that every factor
-// family shares.  A family's unit (rome_conv_pose2.hip, rome_conv_range.hip, rome_conv_pose3.hip) defines its policies, includes this
+// family shares.  A family's unit (rome_conv_pose2.hip, rome_conv_range.hip, rome_conv_pose3.hip, rome_conv_pose3_partial.hip) defines its policies, includes this
 // header and instantiates the kernels through launch_solver<FP>.
 //
 // One convolution = approxConvBelief for one (factor, direction): N particle root-finds

@@ -595,6 +595,44 @@ __device__ __forceinline__ void residual_priorpose3(const Se3& m, const Se3& p, 
   r[0] = m.t[0] - p.t[0]; r[1] = m.t[1] - p.t[1]; r[2] = m.t[2] - p.t[2];
   so3_log(U, &r[3]);
 }
+// ---- yaw of a Pose3 and the Pose3Pose3XYYaw residual (src/factors/PartialPose3.jl:116-136).
+// ψ(R) = atan2(R21, R11), from the first column of R; R11 = R21 = 0 (the x-axis is vertical): ψ = 0, the atan2(0, 0) of the bearing factor.
+// First column c = (R11, R21, R31) of Exp(ω) (Rodrigues, as so3_exp) and u = J_l(ω) e3, the world-frame angular velocity of a unit rate of
+// ω_z:  d/dω_z Exp(ω) = hat(u) Exp(ω) = Exp(ω) hat(J_r(ω) e3).  a = sin θ/θ, b = (1 − cos θ)/θ², k = (θ − sin θ)/θ³, by their series below
+// θ² = 1e-2 (truncation < 3e-17 / 5e-15 / 2.5e-16 there; k has no stable closed form at small θ).
+__device__ __forceinline__ void so3_col1_dz(double x, double y, double z, double (&c)[3], double (&u)[3]) {
+  const double th2 = x * x + y * y + z * z;
+  const bool big = th2 >= 1e-2;
+  const double ith = fast_rsqrt(big ? th2 : 1.0);
+  const double th = th2 * ith;
+  double sn, cs; fast_sincos(big ? th : 0.0, &sn, &cs);
+  const double ith2 = ith * ith;
+  const double a = big ? sn * ith : fma(th2, fma(th2, fma(th2, fma(th2, 1.0 / 362880.0, -1.0 / 5040.0), 1.0 / 120.0), -1.0 / 6.0), 1.0);
+  const double b = big ? (1.0 - cs) * ith2 : fma(th2, fma(th2, fma(th2, -1.0 / 40320.0, 1.0 / 720.0), -1.0 / 24.0), 0.5);
+  const double k = big ? (th - sn) * ith2 * ith : fma(th2, fma(th2, fma(th2, -1.0 / 362880.0, 1.0 / 5040.0), -1.0 / 120.0), 1.0 / 6.0);
+  c[0] = 1.0 + b * (x * x - th2); c[1] = a * z + b * x * y; c[2] = -a * y + b * x * z;
+  u[0] = b * y + k * x * z; u[1] = -b * x + k * y * z; u[2] = 1.0 - k * (x * x + y * y);
+}
+__device__ __forceinline__ double yaw_of_col1(double r11, double r21) {
+  return (r11 != 0.0 || r21 != 0.0) ? fast_atan2(r21, r11) : 0.0;
+}
+// ∂ψ/∂ω_z = u_z − R31 (u_x R11 + u_y R21)/(R11² + R21²)   (from dR = hat(u) R on the first column; 1 on an upright pose)
+__device__ __forceinline__ double yaw_rate(const double (&c)[3], const double (&u)[3]) {
+  const double n2 = c[0] * c[0] + c[1] * c[1];
+  return n2 > 0.0 ? u[2] - c[2] * (u[0] * c[0] + u[1] * c[1]) * fast_rcp(n2) : 1.0;
+}
+// the SE(2) projection of a Pose3: (t_x, t_y, ψ(R)) with (cos ψ, sin ψ) = the normalised (R11, R21) (PartialPose3.jl:120-128)
+__device__ __forceinline__ Se2 se2_of_pose3(double x, double y, double r11, double r21) {
+  const double n2 = r11 * r11 + r21 * r21;
+  const bool ok = n2 > 0.0;
+  const double in = fast_rsqrt(ok ? n2 : 1.0);
+  Se2 p; p.x = x; p.y = y; p.c = ok ? r11 * in : 1.0; p.s = ok ? r21 * in : 0.0;
+  return p;
+}
+// Pose3Pose3XYYaw: the Pose2Pose2 residual of the two projections (the same device function: residual_pose2pose2)
+__device__ __forceinline__ void residual_pose3pose3xyyaw(double zx, double zy, double cz, double sz, const Se2& p2, const Se2& q2, double (&r)[3]) {
+  residual_pose2pose2(zx, zy, cz, sz, p2, q2, r);
+}
 __device__ __forceinline__ void se3_add_entropy(Se3& T, double spread, const double (&u)[6]) {
   double e[6];
 #pragma unroll

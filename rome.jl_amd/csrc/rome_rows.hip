@@ -102,6 +102,24 @@ __global__ void k_residual_pose3pose3(int n, const double* z, const double* p, c
 #pragma unroll
   for (int k = 0; k < 6; ++k) r[6 * i + k] = rr[k];
 }
+// Pose3Pose3XYYaw (PartialPose3.jl:116-136): z rows (x, y, θ); p, q rows as k_residual_pose3pose3 (only t_x, t_y and R's first column are read)
+__global__ void k_residual_pose3pose3xyyaw(int n, const double* z, const double* p, const double* q, int pts, double* r) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  Se2 P, Q;
+  if (pts) {
+    P = se2_of_pose3(p[12 * i], p[12 * i + 1], p[12 * i + 3], p[12 * i + 4]);
+    Q = se2_of_pose3(q[12 * i], q[12 * i + 1], q[12 * i + 3], q[12 * i + 4]);
+  } else {
+    double c[3], u[3];
+    so3_col1_dz(p[6 * i + 3], p[6 * i + 4], p[6 * i + 5], c, u); P = se2_of_pose3(p[6 * i], p[6 * i + 1], c[0], c[1]);
+    so3_col1_dz(q[6 * i + 3], q[6 * i + 4], q[6 * i + 5], c, u); Q = se2_of_pose3(q[6 * i], q[6 * i + 1], c[0], c[1]);
+  }
+  double sz, cz; fast_sincos(z[3 * i + 2], &sz, &cz);
+  double rr[3];
+  residual_pose3pose3xyyaw(z[3 * i], z[3 * i + 1], cz, sz, P, Q, rr);
+  r[3 * i] = rr[0]; r[3 * i + 1] = rr[1]; r[3 * i + 2] = rr[2];
+}
 __global__ void k_residual_priorpose3(int n, const double* m, const double* p, double* r) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -188,6 +206,9 @@ hipError_t launch_residual_bearingrange(int n, const double* z, const double* p,
 }
 hipError_t launch_residual_pose3pose3(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s) {
   return launch_rows(k_residual_pose3pose3, n, s, z, p, q, pts, r);
+}
+hipError_t launch_residual_pose3pose3xyyaw(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s) {
+  return launch_rows(k_residual_pose3pose3xyyaw, n, s, z, p, q, pts, r);
 }
 hipError_t launch_residual_priorpose3(int n, const double* m, const double* p, double* r, hipStream_t s) {
   return launch_rows(k_residual_priorpose3, n, s, m, p, r);

@@ -165,6 +165,22 @@ class DeviceGraph:
             self.tab["pbear"] = dict(F=F)
         sampler("prior2", "rome_sample_priorpose2_dev", Pose2, None, pk.prior2)
         sampler("prior3", "rome_sample_priorpose3_dev", Pose3, None, pk.prior3)
+        # partial Pose3 factors (PartialPose3.jl): the last two families, their proposal rows behind every other Pose3 row.  p3xyy: both
+        # directions in one table (L = [F][6] packed Cholesky); zrp3: prior rows that READ the target belief (fixed = target,
+        # L = [F][4] = (σ_z, packed 2x2 Cholesky of the roll / pitch covariance))
+        xy = getattr(pk, "p3xyy", None)
+        if xy is not None and xy["F"]:
+            factor, dr, fixed, target = PackedGraph.conv_table(xy)
+            add("p3xyy", "rome_conv_pose3pose3xyyaw_dev", Pose3, Pose3, 0, self.STREAM_P3XYY, target, t(xy["mu"], f64), t(cholesky_lower(xy["cov"]), f64),
+                rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(xy["nh"], 2)))
+            self.tab["p3xyy"] = dict(F=xy["F"], C=2 * xy["F"])
+        zr = getattr(pk, "zrp3", None)
+        if zr is not None and zr["F"]:
+            F = zr["F"]
+            L = np.concatenate([zr["sigma_z"].reshape(F, 1), cholesky_lower(zr["cov_rp"]).reshape(F, 3)], axis=1)
+            add("zrp3", "rome_conv_priorpose3zrp_dev", Pose3, Pose3, 0, self.STREAM_ZRP3, zr["var"], t(zr["mu"], f64), t(L, f64),
+                rows4=np.stack([np.arange(F, dtype=np.int32), col(0, F), zr["var"], zr["var"]], axis=1), nh=nh_or_none(zr["nh"]))
+            self.tab["zrp3"] = dict(F=F)
 
         # one conv_step: the fused Pose2 / Point2 call for its three records when all three have rows, then every other record that
         # owns proposal rows, in list order
@@ -320,6 +336,12 @@ class DeviceGraph:
     STREAM_P2RNG, STREAM_PPRNG1, STREAM_PPRNG0 = 8 << 28, 9 << 28, 10 << 28   # range factors (Point2Point2Range, Pose2Point2Range dir 1 / 0)
 
     STREAM_PB1, STREAM_PB0 = 11 << 28, 12 << 28   # bearing-only factor (Pose2Point2Bearing dir 1 / 0)
+
+    STREAM_P3XYY, STREAM_ZRP3 = 13 << 28, 14 << 28   # partial Pose3 factors (Pose3Pose3XYYaw both directions, PriorPose3ZRP)
+
+    def has_partial3(self):
+        """does the graph hold partial Pose3 factors (served by conv_step / solve only: not by the multi-rank drivers)"""
+        return "p3xyy" in self.tab or "zrp3" in self.tab
 
     def has_bearing(self):
         """does the graph hold bearing-only factors (served by conv_step / solve only: not by the multi-rank drivers)"""
@@ -525,6 +547,14 @@ class DeviceGraph:
         """direction 0: poses -> landmark proposals [F, 2, N] (on the sighting rays); 1: landmarks -> pose proposals [F, 3, N]
         (translations kept, headings turned to the bearing)."""
         return self._sweep(self.fams["pb0" if direction == 0 else "pb1"], opts, out, noise, status)
+
+    def sweep_pose3pose3xyyaw(self, opts, out=None, noise=None, status=None):
+        """Pose3Pose3XYYaw rows, both directions interleaved -> proposals [2F, 6, N] ((x, y, ω_z) solved, z, ω_x, ω_y kept)."""
+        return self._sweep(self.fams["p3xyy"], opts, out, noise, status)
+
+    def sweep_priorpose3zrp(self, opts, out=None, noise=None):
+        """PriorPose3ZRP rows -> proposals [F, 6, N]: the variables' own particles with z, ω_x, ω_y replaced by the samples."""
+        return self._sweep(self.fams["zrp3"], opts, out, noise)
 
     def sample_priors(self, opts, kind="prior2", out=None, noise=None):
         return self._sweep(self.fams[kind], opts, out, noise)

@@ -8,6 +8,7 @@ Same names and argument meaning as the reference (paths relative to the RoME.jl 
   Pose3Pose3(Z), PriorPose3(Z)                               src/factors/Pose3Pose3.jl:9-11, Pose3D.jl:8-10
   Point2Point2Range(Z), Pose2Point2Range(Z)                 src/factors/Range2D.jl:8-17, 40-54
   Pose2Point2Bearing(Z)                                      src/factors/Bearing2D.jl:10-32
+  Pose3Pose3XYYaw(Z), PriorPose3ZRP(z, rp)                   src/factors/PartialPose3.jl:101-136, 12-46
   getMeasurementParametric(::Pose2Point2BearingRange)        src/factors/BearingRange2D.jl:30-37
   Packed* <-> factor converters                              src/factors/Pose2D.jl:76-84 etc.
 These objects only hold the measurement model; all arithmetic is done by the HIP library.
@@ -205,7 +206,41 @@ class Pose2Point2Bearing(_RelativeFactor):
         self.Z = Z
 
 
+class Pose3Pose3XYYaw(_RelativeFactor):
+    """Planar odometry with heading between two `Pose3` variables (src/factors/PartialPose3.jl:101-136), partial = (1, 2, 6): the
+    Pose2Pose2 residual of the two poses' SE(2) projections (t_xy, yaw).  Solving a pose moves its (x, y, ω_z) only; every particle's
+    z, ω_x, ω_y pass through unchanged."""
+    variable_types = (Pose3, Pose3)
+    partial = (1, 2, 6)
+
+    def __init__(self, Z):
+        if not isinstance(Z, MvNormal):
+            raise TypeError("Pose3Pose3XYYaw: this build supports an MvNormal belief, got %s" % type(Z).__name__)
+        if Z.mu.size != 3:
+            raise ValueError("Pose3Pose3XYYaw needs a 3-dimensional belief (x, y, yaw)")
+        self.Z = Z
+
+
+class PriorPose3ZRP(_PriorFactor):
+    """Partial prior on z, roll and pitch of a `Pose3` (src/factors/PartialPose3.jl:12-46), partial = (3, 4, 5): z a `Normal`, rp a
+    2-dimensional `MvNormal` of (roll, pitch).  The proposal is the variable's own belief with coordinates 3, 4, 5 replaced by the
+    samples (z, and ω_x, ω_y of Log(R_y(pitch) R_x(roll))); x, y, ω_z pass through unchanged."""
+    variable_types = (Pose3,)
+    partial = (3, 4, 5)
+
+    def __init__(self, z, rp):
+        if not isinstance(z, Normal):
+            raise TypeError("PriorPose3ZRP: this build supports a Normal z belief, got %s" % type(z).__name__)
+        if not isinstance(rp, MvNormal):
+            raise TypeError("PriorPose3ZRP: this build supports an MvNormal roll / pitch belief, got %s" % type(rp).__name__)
+        if rp.mu.size != 2:
+            raise ValueError("PriorPose3ZRP needs a 2-dimensional roll / pitch belief")
+        self.z = z
+        self.rp = rp
+
+
 RANGE_FACTORS = (Point2Point2Range, Pose2Point2Range)
+PARTIAL3_FACTORS = (Pose3Pose3XYYaw, PriorPose3ZRP)
 
 
 def refuse_range(factors, where):
@@ -222,6 +257,14 @@ def refuse_bearing(factors, where):
         if isinstance(f, Pose2Point2Bearing):
             raise TypeError("%s: Pose2Point2Bearing factors are not supported here (solveGraph / approxConv / solveGraphParametric "
                             "serve bearing-only factors)" % where)
+
+
+def refuse_partial3(factors, where):
+    """TypeError naming the first partial Pose3 factor in `factors` (the paths that refuse range factors refuse these too)."""
+    for f in factors:
+        if isinstance(f, PARTIAL3_FACTORS):
+            raise TypeError("%s: %s factors are not supported here (solveGraph / approxConv serve the partial Pose3 factors)"
+                            % (where, type(f).__name__))
 
 
 def getMeasurementParametric(f):
@@ -259,6 +302,8 @@ def pack_factor(f):
     name = type(f).__name__
     if isinstance(f, Pose2Point2BearingRange):  # PackedPose2Point2BearingRange: bearstr, rangstr (BearingRange2D.jl:76-79)
         return {"fnctype": name, "bearstr": _pack_belief(f.bearing), "rangstr": _pack_belief(f.range)}
+    if isinstance(f, PriorPose3ZRP):  # PackedPriorPose3ZRP: zdata, rpdata (PartialPose3.jl:54-57)
+        return {"fnctype": name, "zdata": _pack_belief(f.z), "rpdata": _pack_belief(f.rp)}
     return {"fnctype": name, "Z": _pack_belief(f.Z)}
 
 
@@ -266,9 +311,12 @@ def unpack_factor(d):
     t = d["fnctype"]
     if t == "Pose2Point2BearingRange":
         return Pose2Point2BearingRange(_unpack_belief(d["bearstr"]), _unpack_belief(d["rangstr"]))
+    if t == "PriorPose3ZRP":
+        return PriorPose3ZRP(_unpack_belief(d["zdata"]), _unpack_belief(d["rpdata"]))
     cls = {"Pose2Pose2": Pose2Pose2, "PriorPose2": PriorPose2, "Pose3Pose3": Pose3Pose3, "PriorPose3": PriorPose3,
            "PriorPoint2": PriorPoint2, "Point2Point2Range": Point2Point2Range, "Pose2Point2Range": Pose2Point2Range,
-           "Pose2Point2Bearing": Pose2Point2Bearing}[t]   # PackedPose2Point2Bearing: Z (Bearing2D.jl:36-45)
+           "Pose2Point2Bearing": Pose2Point2Bearing,    # PackedPose2Point2Bearing: Z (Bearing2D.jl:36-45)
+           "Pose3Pose3XYYaw": Pose3Pose3XYYaw}[t]       # PackedPose3Pose3XYYaw: Z (PartialPose3.jl:172-174)
     return cls(_unpack_belief(d["Z"]))
 
 

@@ -222,6 +222,53 @@ function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:
   return manikde!(M3, pts)
 end
 
+# ---- partial Pose3 factors (src/factors/PartialPose3.jl): Pose3Pose3XYYaw over [p, q], partial = (1, 2, 6) -- solving a pose moves its
+# (x, y, ω_z) only --, and PriorPose3ZRP, partial = (3, 4, 5) -- the variable's own points with (z, ω_x, ω_y) replaced by the samples ------
+function conv_pose3pose3xyyaw(fg, f::Pose3Pose3XYYaw{<:MvNormal}, fixedpts, u0pts, dir::Integer; solver=1)
+  o = default_opts(fg; solver)
+  μ = collect(Float64, mean(f.Z)); Σ = collect(Float64, cov(f.Z))'
+  fixed = coords(Pose3, fixedpts); target = coords(Pose3, u0pts)
+  d = Int32[dir]
+  GC.@preserve μ Σ fixed target d begin
+    check(ccall((:rome_conv_pose3pose3xyyaw, LIB), Cint,
+      (Ptr{Cvoid}, Ref{RomeOpts}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+      ctx().h, o, 1, d, μ, Σ, fixed, C_NULL, target, C_NULL))
+  end
+  points(Pose3, target)
+end
+
+function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:Pose3Pose3XYYaw{<:MvNormal}}}, target::Symbol,
+                          measurement::AbstractVector=Tuple[]; solveKey::Symbol=:default, kw...)
+  vars = getVariableOrder(fc)
+  dir = vars[2] == target ? 0 : 1
+  other = dir == 0 ? vars[1] : vars[2]
+  pts = conv_pose3pose3xyyaw(dfg, getFactorType(fc), getVal(dfg, other; solveKey), getVal(dfg, target; solveKey), dir)
+  return manikde!(M3, pts)
+end
+
+function conv_priorpose3zrp(fg, f::PriorPose3ZRP{<:Normal,<:MvNormal}, u0pts)
+  o = default_opts(fg)
+  μ = Float64[mean(f.z), mean(f.rp)[1], mean(f.rp)[2]]; σz = Float64[std(f.z)]; Σ = collect(Float64, cov(f.rp))'
+  target = coords(Pose3, u0pts)
+  GC.@preserve μ σz Σ target begin
+    check(ccall((:rome_conv_priorpose3zrp, LIB), Cint,
+      (Ptr{Cvoid}, Ref{RomeOpts}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+      ctx().h, o, 1, μ, σz, Σ, C_NULL, target))
+  end
+  points(Pose3, target)
+end
+
+function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:PriorPose3ZRP{<:Normal,<:MvNormal}}}, target::Symbol,
+                          measurement::AbstractVector=Tuple[]; solveKey::Symbol=:default, kw...)
+  return manikde!(M3, conv_priorpose3zrp(dfg, getFactorType(fc), getVal(dfg, target; solveKey)))
+end
+
+# the device-table twins: `tab` points to a rome_conv_dev laid out as in include/rome_mi355.h (device pointers; the caller owns it)
+conv_pose3pose3xyyaw_dev(o::RomeOpts, tab::Ptr{Cvoid}) =
+  check(ccall((:rome_conv_pose3pose3xyyaw_dev, LIB), Cint, (Ptr{Cvoid}, Ref{RomeOpts}, Ptr{Cvoid}), ctx().h, o, tab))
+conv_priorpose3zrp_dev(o::RomeOpts, tab::Ptr{Cvoid}) =
+  check(ccall((:rome_conv_priorpose3zrp_dev, LIB), Cint, (Ptr{Cvoid}, Ref{RomeOpts}, Ptr{Cvoid}), ctx().h, o, tab))
+
 # ---- priors: N samples of the prior as points (IIF samplePoint) ------------------------------------------------
 function sample_prior(fg, f::Union{PriorPose2,PriorPose3})
   T, sym, d = f isa PriorPose2 ? (Pose2, :rome_sample_priorpose2, 3) : (Pose3, :rome_sample_priorpose3, 6)
@@ -647,6 +694,18 @@ function residual_pose2point2bearing(z::AbstractVector, p::AbstractMatrix, l::Ab
   r = similar(z)
   check(ccall((:rome_residual_pose2point2bearing, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
               ctx().h, length(z), z, p, l, r))
+  r
+end
+function residual_pose3pose3xyyaw(z::AbstractMatrix, p::AbstractMatrix, q::AbstractMatrix)   # 3 x n measurements (x, y, θ), 6 x n pose coordinates
+  r = similar(z)
+  check(ccall((:rome_residual_pose3pose3xyyaw, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              ctx().h, size(z, 2), z, p, q, r))
+  r
+end
+function residual_pose3pose3xyyaw_pt(z::AbstractMatrix, p::AbstractMatrix, q::AbstractMatrix)   # the poses as native points, 12 x n
+  r = similar(z)
+  check(ccall((:rome_residual_pose3pose3xyyaw_pt, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              ctx().h, size(z, 2), z, p, q, r))
   r
 end
 

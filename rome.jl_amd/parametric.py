@@ -366,8 +366,9 @@ def solveGraphParametric(fg, init=None, max_iters=100, tol=1e-4, ctx=None, retur
     The host arithmetic of the whole solve runs with the BLAS pools limited to one thread: every BLAS call
     of this loop is small -- SuperLU supernodes, 12 x 12 block products -- and the worker threads of a 64-thread OpenBLAS pool on a
     16-CPU quota spin after each of them while the sequential parts of the factorisation want the cores: 10k helix 6.1 -> 2.4 s"""
-    from .factors import refuse_range
+    from .factors import refuse_range, refuse_partial3
     refuse_range([f for _, _, f in fg.factors], "solveGraphParametric")
+    refuse_partial3([f for _, _, f in fg.factors], "solveGraphParametric")
     if shard is not None:   # the row-sharded linearisation goes through rome_linearize_dev, which serves kinds 0..5
         from .factors import refuse_bearing
         refuse_bearing([f for _, _, f in fg.factors], "solveGraphParametric(shard=...)")

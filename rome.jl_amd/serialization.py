@@ -28,13 +28,13 @@ import numpy as np
 
 from .factors import (MvNormal, Normal, Uniform, Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3,
                       PriorPose3, PriorPoint2, Point2Point2,
-                      Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing)
+                      Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP)
 from .graph import FactorGraph
 
 _VERSION = "0.25.1"
 _VARTYPES = {"Pose2": Pose2, "Point2": Point2, "Pose3": Pose3}
 _FACTORS = {c.__name__: c for c in (Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2,
-                                     Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing)}
+                                     Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP)}
 
 
 # ---------------------------------------------------------------- Packed beliefs (IIF PackedSamplableBelief JSON forms)
@@ -71,6 +71,8 @@ def packFactor(f):
     """factor -> the field dict of its Packed<F> struct."""
     if isinstance(f, Pose2Point2BearingRange):
         return {"bearstr": packBelief(f.bearing), "rangstr": packBelief(f.range)}
+    if isinstance(f, PriorPose3ZRP):   # PackedPriorPose3ZRP (PartialPose3.jl:54-57)
+        return {"zdata": packBelief(f.z), "rpdata": packBelief(f.rp)}
     return {"Z": packBelief(f.Z)}
 
 
@@ -82,6 +84,8 @@ def unpackFactor(fnctype, fnc):
         raise ValueError("factor type %s is not on the supported path" % fnctype)
     if name == "Pose2Point2BearingRange":
         return Pose2Point2BearingRange(unpackBelief(fnc["bearstr"]), unpackBelief(fnc["rangstr"]))
+    if name == "PriorPose3ZRP":
+        return PriorPose3ZRP(unpackBelief(fnc["zdata"]), unpackBelief(fnc["rpdata"]))
     return _FACTORS[name](unpackBelief(fnc["Z"]))
 
 

@@ -8,7 +8,7 @@ on a whole-graph Jacobi schedule instead of the Bayes tree --, 
 import numpy as np
 
 from .convolution import approxConv
-from .factors import _PriorFactor, refuse_range, refuse_bearing
+from .factors import _PriorFactor, refuse_range, refuse_bearing, refuse_partial3
 
 
 def initAll(fg, seed=1, solver=None):
@@ -23,6 +23,8 @@ def initAll(fg, seed=1, solver=None):
         changed = False
         for flabel, labels, f in fg.factors:
             if isinstance(f, _PriorFactor):
+                if getattr(f, "partial", None) is not None:   # a partial prior replaces coordinates of an existing belief: it starts none
+                    continue
                 if not fg.isInitialized(labels[0]):
                     fg.initVariable(labels[0], approxConv(fg, flabel, labels[0], seed=seed + k, **kw)); k += 1; changed = True
                 continue
@@ -45,6 +47,7 @@ def initAllOrdered(fg, seed=1, ctx=None, sweeps=0, kind="colour", solver=None):
     -> the OrderedSolve (its store keeps the beliefs on the device for further sweeps)."""
     refuse_range([f for _, _, f in fg.factors], "initAllOrdered")
     refuse_bearing([f for _, _, f in fg.factors], "initAllOrdered")
+    refuse_partial3([f for _, _, f in fg.factors], "initAllOrdered")
     from .api import make_opts
     from .clique import DeviceStore
     from .schedule import OrderedSolve
@@ -109,6 +112,7 @@ def solveTree(fg, tree=None, messages="auto", passes=1, seed=0x524F4D45, ctx=Non
     -> the TreeSolver (its store keeps the beliefs on the device; pass it back as `tree=` after adding nothing to the graph)."""
     refuse_range([f for _, _, f in fg.factors], "solveTree")
     refuse_bearing([f for _, _, f in fg.factors], "solveTree")
+    refuse_partial3([f for _, _, f in fg.factors], "solveTree")
     from .api import make_opts
     from .canonical import setPPE
     from .tree import TreeSolver

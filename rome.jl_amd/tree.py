@@ -33,7 +33,7 @@ import numpy as np
 
 from . import _lib
 from .clique import DeviceStore, LibHandle, UpsolvePlan, plan_level
-from .factors import refuse_range, refuse_bearing
+from .factors import refuse_range, refuse_bearing, refuse_partial3
 from .levels import ZERO, LevelSpec, LevelGraph, LevelSolver, split_products   # noqa: F401  (ZERO, LevelSpec: importable from here as before)
 
 
@@ -244,6 +244,7 @@ class TreeSolver(LevelSolver):
         operations between levels run on every rank (each holds the whole store)."""
         refuse_range([f for _, _, f in fg.factors], "TreeSolver")
         refuse_bearing([f for _, _, f in fg.factors], "TreeSolver")
+        refuse_partial3([f for _, _, f in fg.factors], "TreeSolver")
         if messages not in ("relative", "marginal"):
             raise ValueError("messages must be 'relative' or 'marginal'")
         if message_tree not in ("hop", "star"):
