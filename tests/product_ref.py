@@ -1,4 +1,4 @@
-"""References for the importance product (k_product<D,S>, k_product_se3<S>) and the belief statistics (k_belief_stats<D>, block_stats) of
+"""References for the importance product (k_product<M,S>: Flat<2>, Flat<3>, Se3M) and the belief statistics (k_belief_stats<D>, block_stats) of
 rome.jl_amd/csrc/rome_product.hip: what rome_product_dev / rome_product_bw_dev / rome_belief_stats* must return for every particle.
 
 Three sides, none of which is the kernel:

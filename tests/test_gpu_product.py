@@ -1,9 +1,16 @@
-"""The importance product (rome_product_dev / rome_product_bw_dev: k_product<D,S>, k_product_se3<S>) and the belief statistics
-(rome_belief_stats*: k_belief_stats<D>) against the references of tests/product_ref.py: EVERY particle of every table is decided -- the
-pick recovered from the output equals the reference's, the output lies within 64 ulp of Pb[pick] ⊕ h_p⊙ξ at the variable's scale, K = 0 / 1
-blocks are bit copies.  The rule, the bounds and the CPU conditions that make it total are stated in product_ref's docstring and checked
-in tests/test_product_ref_host.py; nothing here comes from a GPU run."""
+"""The importance product (rome_product_dev / rome_product_bw_dev: k_product<M,S> over the manifolds Flat<2>, Flat<3>, Se3M) and the
+belief statistics (rome_belief_stats*: k_belief_stats<D>) against the references of tests/product_ref.py: EVERY particle of every table is
+decided -- the pick recovered from the output equals the reference's, the output lies within 64 ulp of Pb[pick] ⊕ h_p⊙ξ at the variable's
+scale, K = 0 / 1 blocks are bit copies.  The rule, the bounds and the CPU conditions that make it total are stated in product_ref's
+docstring and checked in tests/test_product_ref_host.py; nothing in those tests comes from a GPU run.
+
+tests/golden/product_bits.json holds the sha256 of the output bytes of every one of these tables and of the statistics at every (D, N),
+written by scripts/product_bits.py from the two-kernel source (k_product<D,S> and k_product_se3<S>) that the one-body kernel replaced:
+the outputs are bit-for-bit what they were then."""
 import ctypes as C
+import importlib.util
+import json
+import os
 
 import numpy as np
 import pytest
@@ -147,3 +154,16 @@ def test_device_graph_product_step_against_np_product(bandwidth):
         assert all(eq or g >= PR.GAP_FACTOR * PR.ULP64 * D for g, eq in ref.lnh)
         fig, bad = ref.check(dg.bel[vt].cpu().numpy())
         assert not bad, (bandwidth, vt, bad)
+
+
+def test_output_bits_are_the_recorded_ones():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("product_bits", os.path.join(root, "scripts", "product_bits.py"))
+    bits = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bits)
+    with open(os.path.join(root, "tests", "golden", "product_bits.json")) as f:
+        want = json.load(f)["sha256"]
+    got = bits.hashes(lambda name, make: PR.reference(name).table)           # the tables the tests above ran, not rebuilt
+    assert sorted(got) == sorted(want) and len(got) == len(TABLES) + sum(len(PR.SHAPE_N[D]) for D in PR.DIMS)
+    diff = [k for k in got if got[k] != want[k]]
+    assert not diff, diff
