@@ -1517,7 +1517,7 @@ static int msg_node(const msg_tree* T, int l, int z, double* mean, double* var, 
 static inline uint32_t msg_xorshift(uint32_t r) { r ^= r << 13; r ^= r >> 17; r ^= r << 5; return r; }
 /* Candidate arithmetic: IEEE single precision, every operation written out (this file is compiled with -ffp-contract=off; fmaf is
  * the correctly rounded fused operation).  The device evaluates two candidates per lane with packed instructions: same values
- * (its opt-in ROME_GIBBS_HWTRANS build takes msg_exp32 / msg_ln32 from the hardware transcendentals, within an ulp of these). */
+ * (taking msg_exp32 / msg_ln32 from the hardware transcendentals, within an ulp of these, was measured there and rejected for parity). */
 #define MSG_ABSENT (-3.0e38f)   /* log p of "no candidate"; also the initial running maximum */
 static inline float msg_f32_from_bits(uint32_t b) { float f; memcpy(&f, &b, 4); return f; }
 static inline uint32_t msg_bits_from_f32(float f) { uint32_t b; memcpy(&b, &f, 4); return b; }

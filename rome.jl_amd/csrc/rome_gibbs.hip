@@ -8,19 +8,24 @@
 //
 // Mapping on gfx950: three kernels.
 //   build   k_gibbs_trees: one wavefront per proposal (four per block) writes the proposal's ball tree (6.9 kB for Pose2) to a
-//           workspace in HBM -- every proposal feeds exactly one product.  A tree is built top-down by sorting:
-//           at level l every node re-sorts its index range along its widest coordinate -- ONE 128-key bitonic sort of the whole
-//           wavefront per level with the key (node, coordinate, id): sorting by node first keeps every point inside its node's
-//           range, so the nodes of a level are sorted simultaneously (segment extents by LDS integer min/max atomics).
+//           workspace in HBM -- every proposal feeds exactly one product.  A tree is built top-down by ordering:
+//           at level l every node orders its index range along its widest coordinate (the extents of all nodes of the level at
+//           once, by LDS integer min/max atomics).  The positions of a node are already its own, because the level above ordered
+//           by node, so a point's place is the node's first position + its RANK in the node: the number of the node's points with
+//           a smaller (key along that coordinate, id), counted against the node's keys in LDS -- all nodes of a level at the
+//           same time, 2N compare steps per point over the whole tree, no sort.
 //           Node statistics bottom-up by Chan's pairwise update with the children fetched by lane shuffles (same arithmetic
 //           order as the oracle), stored in single precision as offsets from the proposal's point 0, [coordinate][node].
 //   order   k_gibbs_order: the variables by descending number of proposals (one block, counting sort) -- the dispatch order of
-//   sample  k_product_gibbs: one block per variable, lane = output sample (128 threads for N <= 128, 256 up to N = 256).  The current level of every tree
-//           of the variable is staged in LDS (2.8 kB per tree; the whole trees would pin 81 kB for a hub variable with 11
-//           proposals); every categorical draw walks the candidates of a level two at a time with WAVE-UNIFORM node statistics
-//           (8-byte LDS broadcasts) against the lane's own point / product Gaussian: no divergence; one-pass reservoir selection
-//           (running max of log p, rescaled total) driven by a xorshift32 stream seeded from one Philox word.  The candidate
-//           arithmetic is an exact single-precision specification shared with the oracle (below).
+//           the blocks of the sampling kernel, longest first.
+//   sample  k_product_gibbs: one block per variable, lane = output sample (128 threads for N <= 128, 256 up to N = 256).  The
+//           current level of every tree of the variable is staged in LDS (2.8 kB per tree; the whole trees would pin 81 kB for a
+//           hub variable with 11 proposals); every categorical draw walks the candidates of a level two at a time with
+//           WAVE-UNIFORM node statistics (8-byte LDS broadcasts) against the lane's own point / product Gaussian: no divergence;
+//           one-pass reservoir selection (running max of log p, rescaled total) driven by a xorshift32 stream seeded from one
+//           Philox word.  The candidate arithmetic is an exact single-precision specification shared with the oracle (below).
+//           Per level: (a) a point from the product Gaussian of the selected nodes (fuse), (c) every density's label given the
+//           point, (d) Gibbs sweeps: a density's label given the product Gaussian of the others (fuse again, to_chart).
 #include "rome_device_math.hpp"
 #include "rome_kernels.h"
 
@@ -302,8 +307,7 @@ __global__ void __launch_bounds__(256) k_gibbs_trees(const GibbsArgs a) {
 }
 
 // ---- candidate arithmetic: IEEE single precision, every operation spelled out (explicit fma, contraction off), so that the
-// oracle (msg_exp32 / msg_ln32 / msg_wrap32 / msg_res_pair in oracle/rome_oracle.c) reproduces it bit for bit (an opt-in build takes exp and log from the
-// hardware instead: ROME_GIBBS_HWTRANS below).  Written on
+// oracle (msg_exp32 / msg_ln32 / msg_wrap32 / msg_res_pair in oracle/rome_oracle.c) reproduces it bit for bit.  Written on
 // f32x2 = two CANDIDATES of the same lane (nodes z, z + 1: their statistics are one 8-byte LDS broadcast), which the compiler maps to
 // the packed v_pk_{add,mul,fma}_f32 instructions: half the VALU issue slots of the one-candidate-at-a-time form.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -313,24 +317,12 @@ constexpr float kAbsent = -3.0e38f;   // log p of "no candidate" (odd N at the l
 
 __device__ __forceinline__ f32x2 splat(float v) { return f32x2{v, v}; }
 // exp(max(x, -80)), x <= 0 (never 0: e^-80 = 1.8e-35 is below every acceptance threshold and every total); k = rint(x log2 e), Cody-Waite r = x - k ln2, Cephes expf polynomial, scaled by 2^k on the exponent field
-// ROME_GIBBS_HWTRANS (default 0; 1 is an opt-in build): exp and log of the candidate arithmetic on the hardware transcendentals
-// (v_exp_f32 / v_log_f32, within 1 ulp of the specified polynomials below, which the oracle evaluates: msg_exp32 / msg_ln32).  13 %
-// faster (1.20 -> 1.02 ms per Manhattan sweep: the two polynomial exponentials are 65 of ~300 issue cycles of a candidate pair) and
-// 50 784 of 50 784 product samples of the unit problems identical (scripts/gibbs_identical.py) -- but a categorical draw differs
-// whenever a uniform lands within an ulp of a cumulative boundary, and over the 8e9 draws of two Manhattan-3500 solve iterations
-// that happens: one of the 3500 pose means moved by 1.7e-3 against the oracle loop (north_star's bar is 1e-3).  Parity first: the
-// shipped build evaluates the specified polynomials, bit for bit the oracle's.
-#ifndef ROME_GIBBS_HWTRANS
-#define ROME_GIBBS_HWTRANS 0
-#endif
+// (Taking exp and log from the hardware transcendentals instead -- v_exp_f32 / v_log_f32, within 1 ulp of the polynomials below -- was
+// measured and rejected: 13 % faster per Manhattan sweep, but a categorical draw differs whenever a uniform lands within an ulp of a
+// cumulative boundary, and over the 8e9 draws of two Manhattan-3500 solve iterations one pose mean moved by 1.7e-3 against the oracle
+// loop, past north_star's 1e-3 bar: docs/EXPERIMENTS.md.  Parity first: the specified polynomials, bit for bit the oracle's.)
 __device__ __forceinline__ f32x2 exp32_neg(f32x2 x) {
 #pragma clang fp contract(off)
-#if ROME_GIBBS_HWTRANS
-  {
-    const f32x2 t = __builtin_elementwise_max(x, splat(-80.0f)) * 1.44269504f;
-    return f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-  }
-#endif
   const f32x2 xc = __builtin_elementwise_max(x, splat(-80.0f));
   const f32x2 k = __builtin_elementwise_rint(xc * 1.44269504f);
   f32x2 r = __builtin_elementwise_fma(k, splat(-0.693359375f), xc);
@@ -351,9 +343,6 @@ __device__ __forceinline__ f32x2 exp32_neg(f32x2 x) {
 // second, discarded element (round 6; the same IEEE operations in the same order: the same bits)
 __device__ __forceinline__ float exp32_neg(float x) {
 #pragma clang fp contract(off)
-#if ROME_GIBBS_HWTRANS
-  return __builtin_amdgcn_exp2f(fmaxf(x, -80.0f) * 1.44269504f);
-#endif
   const float xc = fmaxf(x, -80.0f);
   const float k = __builtin_rintf(xc * 1.44269504f);
   float r = __builtin_fmaf(k, -0.693359375f, xc);
@@ -370,9 +359,6 @@ __device__ __forceinline__ float exp32_neg(float x) {
 // ln(v), v > 0 normal: v = m 2^e, ln m the degree-7 polynomial in m - 1.5 of the Box-Muller radius (rome_device_math.hpp)
 __device__ __forceinline__ f32x2 ln32_pos(f32x2 v) {
 #pragma clang fp contract(off)
-#if ROME_GIBBS_HWTRANS
-  return f32x2{__builtin_amdgcn_logf(v.x), __builtin_amdgcn_logf(v.y)} * 0.693147181f;
-#endif
   const u32x2 xb = (u32x2)v;
   const i32x2 e = (i32x2)(xb >> 23) - 127;
   const f32x2 ke = __builtin_convertvector(e, f32x2);
@@ -434,10 +420,9 @@ __device__ __forceinline__ void ratio_group(const f32x2* s, const f32x2* v, f32x
 // Candidate scan with the statistics of the NEXT pair of candidates loaded while the current pair is evaluated: the LDS broadcasts of
 // pair z + 2 are in flight during the ~80 dependent instructions of pair z (left to itself the compiler issues a pair's loads at the head
 // of its own iteration and waits for them three instructions later).  Two register sets in ping-pong (no copies); the candidates are
-// visited in the same order, so every draw is the one the plain loop makes.
-#ifndef ROME_GIBBS_PREFETCH
-#define ROME_GIBBS_PREFETCH 1   // 0: the plain loops (A/B on one box, scripts/gibbs_time.py: 2.545 -> 2.512 ms per bandwidth + tree + product pass,
-#endif                          // i.e. -33 us = 2.8 % of the product kernel; asking for five waves per SIMD (94 VGPRs) on top: no gain)
+// visited in the same order, so every draw is the one the plain loop makes.  (Against the plain loops, A/B on one box with
+// scripts/gibbs_time.py: 2.545 -> 2.512 ms per bandwidth + tree + product pass, i.e. -33 us = 2.8 % of the product kernel; asking for
+// five waves per SIMD (94 VGPRs) on top: no gain.)
 template <class S, bool PREFETCH, class Load, class Body>
 __device__ __forceinline__ void scan_pairs(int n, Load&& load, Body&& body) {
   if constexpr (!PREFETCH) {   // (Pose3: six coordinates -- the second register set would cost an occupancy step, 162 -> 170 VGPRs)
@@ -596,212 +581,197 @@ __global__ void __launch_bounds__(NM) k_product_gibbs(const GibbsArgs a) {
   for (int j = 0; j < K; ++j) selbuf[j * NM + tid] = 0;
   stage(0);
   GTRACE(3);   // labels, level 0
-  double x[D];
-  [[maybe_unused]] double xq[4] = {1.0, 0.0, 0.0, 0.0};   // D = 6: rotation of the current point
-  constexpr int DE = D == 6 ? 3 : D;                      // coordinates handled one by one (Euclidean / circular)
-  for (int l = 1; l <= L + 1; ++l) {
-    // (a) a point from the product of the selected nodes of level l - 1 (its image is the one in LDS).  Deviations are taken
-    //     from density 0's node; rotations: Log(Q_0* ⊗ Q_j) with Q_j = q0_j ⊗ Exp(mean_ω) the node's absolute rotation.
-    //     Labels of level L are sorted positions.
+  constexpr int DE = D == 6 ? 3 : D;   // coordinates handled one by one (Euclidean / circular); D = 6: 3..5 are the rotation
+  // The product Gaussian of the selected nodes of every density but `skip` (-1: none is left out).  src(i, d, sz, &mean, &ivar) gives
+  // coordinate d of density i's selected node sz, the mean in density i's chart (in_chart) or absolute.  Deviations are taken from the
+  // first density that takes part; rotations: Log(B* ⊗ Q_i) with B that density's node and Q_i = q0_i ⊗ Exp(mean_ω) the absolute
+  // rotation of node i.  Flat coordinates: mean mu0 + num / prec, precision prec; D = 6: the rotation B ⊗ Exp(num / prec [3..5]).
+  struct Fusion { double mu0[DE], num[D], prec[D], B[4]; };
+  auto fuse = [&](int skip, bool in_chart, auto&& src) -> Fusion {
+    Fusion F;
 #pragma unroll
     for (int d = 0; d < DE; ++d) {
-      double prec = 0.0, num = 0.0, mu0 = 0.0;
-      for (int j = 0; j < K; ++j) {
-        const GibbsConst<D>& c = cst[j];
-        const int sz = selbuf[j * NM + tid];
-        double mabs, iv;
-        if (l - 1 == L) {   // the selected kernel itself: the particle at full precision, its bandwidth in double
-          mabs = a.prop[(size_t)c.row * D * N + (size_t)d * N + W[c.row].perm[sz]];
-          iv = 1.0 / (c.h[d] * c.h[d]);
-        } else { mabs = c.ref[d] + (double)node_mean(l - 1, j, d, sz); iv = (double)node_ivar(l - 1, j, d, sz); }
-        if (j == 0) mu0 = mabs;
+      double prec = 0.0, num = 0.0, mu0 = 0.0; bool first = true;
+      for (int i = 0; i < K; ++i) {
+        if (i == skip) continue;
+        const int sz = selbuf[i * NM + tid];
+        double mean, iv;
+        src(i, d, sz, &mean, &iv);
+        const double mabs = in_chart ? cst[i].ref[d] + mean : mean;
+        if (first) { mu0 = mabs; first = false; }
         double dev = mabs - mu0;
         if (circ_bit(d)) dev = gwrap(dev);
         prec += iv; num += iv * dev;
       }
-      const double xi = normal();
-      x[d] = mu0 + num * fast_rcp(prec) + xi * fast_rsqrt(prec);   // (reciprocals by hardware seed + Newton: an ulp from the oracle's divisions)
+      F.mu0[d] = mu0; F.num[d] = num; F.prec[d] = prec;
     }
     if constexpr (D == 6) {
-      double B[4] = {1.0, 0.0, 0.0, 0.0}, prec[3] = {0.0, 0.0, 0.0}, num[3] = {0.0, 0.0, 0.0};
-      for (int j = 0; j < K; ++j) {
-        const GibbsConst<D>& c = cst[j];
-        const int sz = selbuf[j * NM + tid];
-        double Q[4], iv[3];
-        if (l - 1 == L) {
-          const int pi = W[c.row].perm[sz];
-          const double* pp = a.prop + (size_t)c.row * D * N + pi;
-          const double w[3] = {pp[3 * (size_t)N], pp[4 * (size_t)N], pp[5 * (size_t)N]};
-          quat_exp(w, Q);
+      double B[4] = {1.0, 0.0, 0.0, 0.0}, prec[3] = {0.0, 0.0, 0.0}, num[3] = {0.0, 0.0, 0.0}; bool first = true;
+      for (int i = 0; i < K; ++i) {
+        if (i == skip) continue;
+        const int sz = selbuf[i * NM + tid];
+        double m[3], iv[3];
 #pragma unroll
-          for (int k = 0; k < 3; ++k) iv[k] = 1.0 / (c.h[3 + k] * c.h[3 + k]);
-        } else {
-          const double m[3] = {(double)node_mean(l - 1, j, 3, sz), (double)node_mean(l - 1, j, 4, sz), (double)node_mean(l - 1, j, 5, sz)};
-          double E[4]; quat_exp(m, E); quat_mul(c.q0, E, Q);
-#pragma unroll
-          for (int k = 0; k < 3; ++k) iv[k] = (double)node_ivar(l - 1, j, 3 + k, sz);
-        }
-        double dev[3] = {0.0, 0.0, 0.0};
-        if (j == 0) { B[0] = Q[0]; B[1] = Q[1]; B[2] = Q[2]; B[3] = Q[3]; }
+        for (int k = 0; k < 3; ++k) src(i, 3 + k, sz, &m[k], &iv[k]);
+        double Q[4], dev[3] = {0.0, 0.0, 0.0};
+        if (in_chart) { double E[4]; quat_exp(m, E); quat_mul(cst[i].q0, E, Q); }
+        else quat_exp(m, Q);
+        if (first) { B[0] = Q[0]; B[1] = Q[1]; B[2] = Q[2]; B[3] = Q[3]; first = false; }
         else { double e[4]; quat_cmul(B, Q, e); quat_log(e, dev); }
 #pragma unroll
         for (int k = 0; k < 3; ++k) { prec[k] += iv[k]; num[k] += iv[k] * dev[k]; }
       }
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { F.num[3 + k] = num[k]; F.prec[3 + k] = prec[k]; }
+      F.B[0] = B[0]; F.B[1] = B[1]; F.B[2] = B[2]; F.B[3] = B[3];
+    }
+    return F;
+  };
+  // The mean of a fusion or, with `draw`, a sample of it (normals: flat coordinates first, then the three of the rotation): flat
+  // coordinates p; D = 6: rotation q.  var (may be null): 1 / prec per coordinate.  (Reciprocals by hardware seed + Newton: an ulp
+  // from the oracle's divisions.)
+  auto fused_point = [&](const Fusion& F, bool draw, double* p, [[maybe_unused]] double (&q)[4], float* var) {
+#pragma unroll
+    for (int d = 0; d < DE; ++d) {
+      const double ip = fast_rcp(F.prec[d]);
+      p[d] = F.mu0[d] + F.num[d] * ip;
+      if (draw) p[d] = p[d] + normal() * fast_rsqrt(F.prec[d]);
+      if (var) var[d] = (float)ip;
+    }
+    if constexpr (D == 6) {
       double e[3], E[4];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) { const double xi = normal(); e[k] = num[k] * fast_rcp(prec[k]) + xi * fast_rsqrt(prec[k]); }
-      quat_exp(e, E); quat_mul(B, E, xq);
+      for (int k = 0; k < 3; ++k) {
+        const double ip = fast_rcp(F.prec[3 + k]);
+        e[k] = F.num[3 + k] * ip;
+        if (draw) e[k] = e[k] + normal() * fast_rsqrt(F.prec[3 + k]);
+        if (var) var[3 + k] = (float)ip;
+      }
+      quat_exp(e, E); quat_mul(F.B, E, q);
+    }
+  };
+  // a point (flat coordinates p; D = 6: rotation q) in the chart of density c, Euclidean there, rounded to single precision
+  auto to_chart = [&](const GibbsConst<D>& c, const double* p, [[maybe_unused]] const double (&q)[4], float* e) {
+    double ed[D];
+#pragma unroll
+    for (int d = 0; d < DE; ++d) { ed[d] = p[d] - c.ref[d]; if (circ_bit(d)) ed[d] = gwrap(ed[d]); }
+    if constexpr (D == 6) { double r[4]; quat_cmul(c.q0, q, r); quat_log(r, ed + 3); }
+#pragma unroll
+    for (int d = 0; d < D; ++d) e[d] = (float)ed[d];
+  };
+  // the candidate scans, one per kind of level.  An inner level: wave-uniform candidates, the node statistics are LDS broadcasts --
+  // the means with one of (ivar, var) and one of (cz, lnc); the arithmetic of a pair is the caller's `body`.
+  constexpr bool kPrefetch = D <= 3;   // (Pose3: the second register set of six coordinates would cost an occupancy step)
+  auto scan_inner = [&](const GibbsLevel<D, NM>& G, const float (*sv)[NM / 2], const float* cw, int nz, auto&& body) {
+    scan_pairs<PairIn<D>, kPrefetch>(nz,
+      [&](int z, PairIn<D>& P) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) { P.m[d] = *reinterpret_cast<const f32x2*>(&G.in.mean[d][z]); P.v[d] = *reinterpret_cast<const f32x2*>(&sv[d][z]); }
+        P.c = *reinterpret_cast<const f32x2*>(&cw[z]);
+      },
+      body);
+  };
+  // The leaf level: single points against a Gaussian with centre ctr and inverse variances iv (both in the density's chart).  Every
+  // candidate has the same variance and the weight 1/N: the constants of the draw drop out.
+  auto draw_leaf = [&](const GibbsLevel<D, NM>& G, const float* ctr, const float* iv, Reservoir& R) {
+    scan_pairs<PairLeaf<D>, kPrefetch>(N,
+      [&](int p, PairLeaf<D>& P) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) P.y[d] = *reinterpret_cast<const f32x2*>(&G.ys[d][p]);
+      },
+      [&](int p, const PairLeaf<D>& P) {
+        f32x2 q = splat(0.0f);
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+          f32x2 e = P.y[d] - splat(ctr[d]);
+          if (circ_bit(d)) e = wrap32(e);
+          q = __builtin_elementwise_fma(e * e, splat(iv[d]), q);
+        }
+        f32x2 lp = q * -0.5f;
+        if (p + 1 >= N) lp.y = kAbsent;
+        R.add2(p, p + 1, lp);
+      });
+  };
+  double x[D];
+  [[maybe_unused]] double xq[4] = {1.0, 0.0, 0.0, 0.0};   // D = 6: rotation of the current point
+  for (int l = 1; l <= L + 1; ++l) {
+    // (a) a point from the product of the selected nodes of level l - 1 (its image is the one in LDS); labels of level L are sorted
+    //     positions, and there the selected kernel itself takes part: the particle at full precision, its bandwidth in double
+    {
+      const bool leaf = l - 1 == L;
+      const Fusion F = fuse(-1, !leaf, [&](int i, int d, int sz, double* mean, double* iv) {
+        const GibbsConst<D>& c = cst[i];
+        if (leaf) {
+          *mean = a.prop[(size_t)c.row * D * N + (size_t)d * N + W[c.row].perm[sz]];
+          *iv = 1.0 / (c.h[d] * c.h[d]);
+        } else { *mean = (double)node_mean(l - 1, i, d, sz); *iv = (double)node_ivar(l - 1, i, d, sz); }
+      });
+      fused_point(F, true, x, xq, nullptr);
     }
     GTRACE(4);   // (a) the point of level l - 1
     if (l == L + 1) break;
     stage(l);
     GTRACE(5);   // staging level l
     const int nz = 1 << l;
-    // (c) labels of level l given the point, which is expressed ONCE in the density's own chart (Euclidean there) and rounded
+    // (c) labels of level l given the point, which is expressed ONCE in the density's own chart
     for (int j = 0; j < K; ++j) {
       const GibbsConst<D>& c = cst[j];
       const GibbsLevel<D, NM>& G = image(l, j);
       Reservoir R; R.init(uniform_word());
       float e0[D];
-      {
-        double e0d[D];
+      to_chart(c, x, xq, e0);
+      if (l < L) {   // point against node
+        scan_inner(G, G.in.ivar, G.in.cz, nz, [&](int z, const PairIn<D>& P) {
+          f32x2 q = splat(0.0f);
 #pragma unroll
-        for (int d = 0; d < DE; ++d) { e0d[d] = x[d] - c.ref[d]; if (circ_bit(d)) e0d[d] = gwrap(e0d[d]); }
-        if constexpr (D == 6) { double e[4]; quat_cmul(c.q0, xq, e); quat_log(e, e0d + 3); }
-#pragma unroll
-        for (int d = 0; d < D; ++d) e0[d] = (float)e0d[d];
-      }
-      if (l < L) {   // wave-uniform candidates: node statistics are LDS broadcasts
-        scan_pairs<PairIn<D>, (D <= 3 && ROME_GIBBS_PREFETCH)>(nz,
-          [&](int z, PairIn<D>& P) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) { P.m[d] = *reinterpret_cast<const f32x2*>(&G.in.mean[d][z]); P.v[d] = *reinterpret_cast<const f32x2*>(&G.in.ivar[d][z]); }
-            P.c = *reinterpret_cast<const f32x2*>(&G.in.cz[z]);
-          },
-          [&](int z, const PairIn<D>& P) {
-            f32x2 q = splat(0.0f);
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-              f32x2 e = splat(e0[d]) - P.m[d];
-              if (circ_bit(d)) e = wrap32(e);
-              q = __builtin_elementwise_fma(e * e, P.v[d], q);
-            }
-            R.add2(z, z + 1, __builtin_elementwise_fma(splat(-0.5f), q, P.c));
-          });
-      } else {   // single points: every candidate has the kernel's variance and the weight 1/N: constants of the draw drop out
-        scan_pairs<PairLeaf<D>, (D <= 3 && ROME_GIBBS_PREFETCH)>(N,
-          [&](int p, PairLeaf<D>& P) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) P.y[d] = *reinterpret_cast<const f32x2*>(&G.ys[d][p]);
-          },
-          [&](int p, const PairLeaf<D>& P) {
-            f32x2 q = splat(0.0f);
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-              f32x2 e = splat(e0[d]) - P.y[d];
-              if (circ_bit(d)) e = wrap32(e);
-              q = __builtin_elementwise_fma(e * e, splat(c.livar[d]), q);
-            }
-            f32x2 lp = q * -0.5f;
-            if (p + 1 >= N) lp.y = kAbsent;
-            R.add2(p, p + 1, lp);
-          });
-      }
+          for (int d = 0; d < D; ++d) {
+            f32x2 e = splat(e0[d]) - P.m[d];
+            if (circ_bit(d)) e = wrap32(e);
+            q = __builtin_elementwise_fma(e * e, P.v[d], q);
+          }
+          R.add2(z, z + 1, __builtin_elementwise_fma(splat(-0.5f), q, P.c));
+        });
+      } else draw_leaf(G, e0, c.livar, R);   // the kernel's own variance
       selbuf[j * NM + tid] = (uint8_t)R.sel;
     }
     GTRACE(6);   // (c) labels given the point
-    // (d) Gibbs sweeps over the labels
+    // (d) Gibbs sweeps over the labels: density j's label given the product Gaussian of the other selected nodes (mean mx in
+    //     density j's chart, variances cx)
     for (int it = 0; it < a.iters; ++it)
       for (int j = 0; j < K; ++j) {
         const GibbsConst<D>& c = cst[j];
-        double Mx[D], Cx[D];   // product Gaussian of the other selected nodes, its mean in density j's chart
-#pragma unroll
-        for (int d = 0; d < DE; ++d) {
-          double prec = 0.0, num = 0.0, mu0 = 0.0; bool first = true;
-          for (int i = 0; i < K; ++i) {
-            if (i == j) continue;
-            const int sz = selbuf[i * NM + tid];
-            double mean, iv;
-            mean = (double)node_mean(l, i, d, sz); iv = (double)node_ivar(l, i, d, sz);
-            const double mabs = cst[i].ref[d] + mean;
-            if (first) { mu0 = mabs; first = false; }
-            double dev = mabs - mu0;
-            if (circ_bit(d)) dev = gwrap(dev);
-            prec += iv; num += iv * dev;
-          }
-          const double ip = fast_rcp(prec);
-          Mx[d] = mu0 + num * ip - c.ref[d]; Cx[d] = ip;
-          if (circ_bit(d)) Mx[d] = gwrap(Mx[d]);
-        }
-        if constexpr (D == 6) {
-          double B[4] = {1.0, 0.0, 0.0, 0.0}, prec[3] = {0.0, 0.0, 0.0}, num[3] = {0.0, 0.0, 0.0}; bool first = true;
-          for (int i = 0; i < K; ++i) {
-            if (i == j) continue;
-            const int sz = selbuf[i * NM + tid];
-            double m[3], iv[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { m[k] = (double)node_mean(l, i, 3 + k, sz); iv[k] = (double)node_ivar(l, i, 3 + k, sz); }
-            double E[4], Q[4], dev[3] = {0.0, 0.0, 0.0};
-            quat_exp(m, E); quat_mul(cst[i].q0, E, Q);
-            if (first) { B[0] = Q[0]; B[1] = Q[1]; B[2] = Q[2]; B[3] = Q[3]; first = false; }
-            else { double e[4]; quat_cmul(B, Q, e); quat_log(e, dev); }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { prec[k] += iv[k]; num[k] += iv[k] * dev[k]; }
-          }
-          double e[3], E[4], QM[4], r[4];
-#pragma unroll
-          for (int k = 0; k < 3; ++k) { const double ip = fast_rcp(prec[k]); e[k] = num[k] * ip; Cx[3 + k] = ip; }
-          quat_exp(e, E); quat_mul(B, E, QM); quat_cmul(c.q0, QM, r); quat_log(r, Mx + 3);
-        }
+        const Fusion F = fuse(j, true, [&](int i, int d, int sz, double* mean, double* iv) {
+          *mean = (double)node_mean(l, i, d, sz); *iv = (double)node_ivar(l, i, d, sz);
+        });
+        double pm[DE];
+        [[maybe_unused]] double pq[4] = {1.0, 0.0, 0.0, 0.0};
         float mx[D], cx[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) { mx[d] = (float)Mx[d]; cx[d] = (float)Cx[d]; }
+        fused_point(F, false, pm, pq, cx);
+        to_chart(c, pm, pq, mx);
         const GibbsLevel<D, NM>& G = image(l, j);
         Reservoir R; R.init(uniform_word());
-        if (l < L) {
-          scan_pairs<PairIn<D>, (D <= 3 && ROME_GIBBS_PREFETCH)>(nz,
-            [&](int z, PairIn<D>& P) {
+        if (l < L) {   // Gaussian against node
+          scan_inner(G, G.in.var, G.in.lnc, nz, [&](int z, const PairIn<D>& P) {
+            f32x2 sq[D], vv[D];
 #pragma unroll
-              for (int d = 0; d < D; ++d) { P.m[d] = *reinterpret_cast<const f32x2*>(&G.in.mean[d][z]); P.v[d] = *reinterpret_cast<const f32x2*>(&G.in.var[d][z]); }
-              P.c = *reinterpret_cast<const f32x2*>(&G.in.lnc[z]);
-            },
-            [&](int z, const PairIn<D>& P) {
-              f32x2 sq[D], vv[D];
-#pragma unroll
-              for (int d = 0; d < D; ++d) {
-                f32x2 e = P.m[d] - splat(mx[d]);
-                if (circ_bit(d)) e = wrap32(e);
-                sq[d] = e * e;
-                vv[d] = P.v[d] + splat(cx[d]);
-              }
-              // Σ_d e_d² / v_d + Σ_d log v_d with one division and one logarithm per group of <= 3 coordinates
-              f32x2 q, pv;
-              ratio_group<(D == 2 ? 2 : 3)>(sq, vv, &q, &pv);
-              f32x2 t = q + ln32_pos(pv);
-              if constexpr (D == 6) { ratio_group<3>(sq + 3, vv + 3, &q, &pv); t = t + (q + ln32_pos(pv)); }
-              R.add2(z, z + 1, __builtin_elementwise_fma(splat(-0.5f), t, P.c));
-            });
-        } else {   // single points: every candidate has the variance h² + C and the weight 1/N
+            for (int d = 0; d < D; ++d) {
+              f32x2 e = P.m[d] - splat(mx[d]);
+              if (circ_bit(d)) e = wrap32(e);
+              sq[d] = e * e;
+              vv[d] = P.v[d] + splat(cx[d]);
+            }
+            // Σ_d e_d² / v_d + Σ_d log v_d with one division and one logarithm per group of <= 3 coordinates
+            f32x2 q, pv;
+            ratio_group<(D == 2 ? 2 : 3)>(sq, vv, &q, &pv);
+            f32x2 t = q + ln32_pos(pv);
+            if constexpr (D == 6) { ratio_group<3>(sq + 3, vv + 3, &q, &pv); t = t + (q + ln32_pos(pv)); }
+            R.add2(z, z + 1, __builtin_elementwise_fma(splat(-0.5f), t, P.c));
+          });
+        } else {   // the variance h² + C
           float ivv[D];
 #pragma unroll
           for (int d = 0; d < D; ++d) ivv[d] = 1.0f / (c.lvar[d] + cx[d]);
-          scan_pairs<PairLeaf<D>, (D <= 3 && ROME_GIBBS_PREFETCH)>(N,
-            [&](int p, PairLeaf<D>& P) {
-#pragma unroll
-              for (int d = 0; d < D; ++d) P.y[d] = *reinterpret_cast<const f32x2*>(&G.ys[d][p]);
-            },
-            [&](int p, const PairLeaf<D>& P) {
-              f32x2 q = splat(0.0f);
-#pragma unroll
-              for (int d = 0; d < D; ++d) {
-                f32x2 e = P.y[d] - splat(mx[d]);
-                if (circ_bit(d)) e = wrap32(e);
-                q = __builtin_elementwise_fma(e * e, splat(ivv[d]), q);
-              }
-              f32x2 lp = q * -0.5f;
-              if (p + 1 >= N) lp.y = kAbsent;
-              R.add2(p, p + 1, lp);
-            });
+          draw_leaf(G, mx, ivv, R);
         }
         selbuf[j * NM + tid] = (uint8_t)R.sel;
       }
@@ -825,13 +795,19 @@ extern "C" int rome_debug_gibbs_trace(unsigned long long* out16) {
 }
 namespace rome {
 #endif
-static size_t tree_bytes(int dim, int n_rows, int N) {
-  const size_t one = N <= 128 ? (dim == 2 ? sizeof(GibbsTree<2, 128>) : (dim == 3 ? sizeof(GibbsTree<3, 128>) : sizeof(GibbsTree<6, 128>)))
-                              : (dim == 2 ? sizeof(GibbsTree<2, 256>) : (dim == 3 ? sizeof(GibbsTree<3, 256>) : sizeof(GibbsTree<6, 256>)));
-  return one * (size_t)(n_rows > 0 ? n_rows : 1);
+// dim, N -> the types: f(D, NM) as integral constants, the only place where the host decides them.  N <= 128: the 128-thread /
+// two-slot instantiation (what every measured number of the solve loop is quoted on); above: 256.
+template <class F>
+static auto with_gibbs_types(int dim, int N, F&& f) {
+  auto of = [&](auto d) { return N <= 128 ? f(d, std::integral_constant<int, 128>{}) : f(d, std::integral_constant<int, 256>{}); };
+  return dim == 2 ? of(std::integral_constant<int, 2>{}) : (dim == 3 ? of(std::integral_constant<int, 3>{}) : of(std::integral_constant<int, 6>{}));
 }
+template <int D, int NM>
+static size_t tree_bytes(int n_rows) { return sizeof(GibbsTree<D, NM>) * (size_t)(n_rows > 0 ? n_rows : 1); }
 // workspace: one tree per proposal row | the variables ordered by their number of proposals
-size_t gibbs_workspace_bytes(int dim, int n_rows, int V, int N) { return tree_bytes(dim, n_rows, N) + sizeof(int32_t) * (size_t)(V > 0 ? V : 1); }
+size_t gibbs_workspace_bytes(int dim, int n_rows, int V, int N) {
+  return with_gibbs_types(dim, N, [&](auto d, auto nm) { return tree_bytes<d(), nm()>(n_rows); }) + sizeof(int32_t) * (size_t)(V > 0 ? V : 1);
+}
 
 // Variables in descending order of their number of proposals (counting sort, one block): the blocks of the sampling kernel are
 // dispatched in this order, i.e. longest first (a block's run time is proportional to its variable's proposal count, 2 .. 11 on
@@ -849,21 +825,18 @@ __global__ void __launch_bounds__(1024) k_gibbs_order(int V, const int32_t* __re
   for (int v = threadIdx.x; v < V; v += 1024) { const int K = prop_ptr[v + 1] - prop_ptr[v]; order[atomicAdd(&start[K < 64 ? K : 64], 1)] = v; }
 }
 
-template <int NM>
-static hipError_t launch_product_gibbs_nm(GibbsArgs& a, int dim, int V, int N, int n_rows, uint32_t circ, int max_k, hipStream_t s) {
-  int32_t* order = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(a.trees) + tree_bytes(dim, n_rows, N));
+template <int D, int NM>
+static hipError_t launch_product_gibbs_of(GibbsArgs& a, hipStream_t s) {
+  const int V = a.V, n_rows = a.n_rows, max_k = a.max_k;
+  int32_t* order = reinterpret_cast<int32_t*>(reinterpret_cast<unsigned char*>(a.trees) + tree_bytes<D, NM>(n_rows));
   a.order = order;
   hipLaunchKernelGGL(k_gibbs_order, dim3(1), dim3(1024), 0, s, V, a.prop_ptr, order);
-  if (n_rows > 0 && max_k > 1) {   // (no variable has two proposals: every product is a copy, no tree is read)
-    if (dim == 2) hipLaunchKernelGGL((k_gibbs_trees<2, NM>), dim3((n_rows + 3) / 4), dim3(256), 0, s, a);
-    else if (dim == 3) hipLaunchKernelGGL((k_gibbs_trees<3, NM>), dim3((n_rows + 3) / 4), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_gibbs_trees<6, NM>), dim3((n_rows + 3) / 4), dim3(256), 0, s, a);
-  }
+  // (max_k <= 1: no variable has two proposals, every product is a copy, no tree is read)
+  if (n_rows > 0 && max_k > 1) hipLaunchKernelGGL((k_gibbs_trees<D, NM>), dim3((n_rows + 3) / 4), dim3(256), 0, s, a);
   // LDS of a block: kGibbsResident level images (variables with more proposals stream theirs through slot 0) + constants and labels
   // for the variable with the most proposals
   constexpr int kGibbsResident = 4;
-  const size_t img = dim == 2 ? sizeof(GibbsLevel<2, NM>) : (dim == 3 ? sizeof(GibbsLevel<3, NM>) : sizeof(GibbsLevel<6, NM>));
-  const size_t per = (dim == 2 ? sizeof(GibbsConst<2>) : (dim == 3 ? sizeof(GibbsConst<3>) : sizeof(GibbsConst<6>))) + NM;
+  constexpr size_t img = sizeof(GibbsLevel<D, NM>), per = sizeof(GibbsConst<D>) + NM;
   a.k_lds = max_k < kGibbsResident ? max_k : kGibbsResident;
   // A launch that cannot fill the chip anyway (a clique, a small frontier: at most two blocks per CU) has no occupancy to protect: every
   // level image resident, as far as 64 kB of LDS go -- the streaming path re-stages an image before every categorical draw, and a
@@ -883,9 +856,10 @@ static hipError_t launch_product_gibbs_nm(GibbsArgs& a, int dim, int V, int N, i
     hipLaunchKernelGGL(kernel, dim3(V), dim3(NM), bytes, s, a);
     return hipGetLastError();
   };
-  if (dim == 2) return circ == 0 ? launch(k_product_gibbs<2, 0, NM>) : launch(k_product_gibbs<2, -1, NM>);
-  if (dim == 3) return circ == 4u ? launch(k_product_gibbs<3, 4, NM>) : (circ == 0 ? launch(k_product_gibbs<3, 0, NM>) : launch(k_product_gibbs<3, -1, NM>));
-  return circ == 0 ? launch(k_product_gibbs<6, 0, NM>) : launch(k_product_gibbs<6, -1, NM>);
+  // the circular mask at compile time for the masks of the variable types (none; Pose2's heading), any other read at run time
+  if (a.circ == 0) return launch(k_product_gibbs<D, 0, NM>);
+  if constexpr (D == 3) if (a.circ == 4u) return launch(k_product_gibbs<3, 4, NM>);
+  return launch(k_product_gibbs<D, -1, NM>);
 }
 
 hipError_t launch_product_gibbs(int dim, int V, int N, int n_rows, const int32_t* prop_ptr, const int32_t* prop_rows, const double* prop,
@@ -901,8 +875,7 @@ hipError_t launch_product_gibbs(int dim, int V, int N, int n_rows, const int32_t
   a.seed = seed; a.stream_offset = stream_offset;
   a.place = place ? *place : GibbsPlace{nullptr, nullptr, nullptr, nullptr, 0};
   if (!a.place.mirror_out) a.place.mirror_slot = nullptr;
-  // N <= 128: the 128-thread / two-slot instantiation (what every measured number of the solve loop is quoted on); above: 256
-  return N <= 128 ? launch_product_gibbs_nm<128>(a, dim, V, N, n_rows, circ, max_k, s) : launch_product_gibbs_nm<256>(a, dim, V, N, n_rows, circ, max_k, s);
+  return with_gibbs_types(dim, N, [&](auto d, auto nm) { return launch_product_gibbs_of<d(), nm()>(a, s); });
 }
 
 }  // namespace rome

@@ -24,3 +24,8 @@ for s in range(5):
     dg.conv_step(o, s); dg.product_step(o, s, "lcv", "gibbs")
 torch.cuda.synchronize()
 print("Pose3 helix: iteration with manikde! bandwidths + Gibbs product on SE(3)  %.3f ms" % ((time.perf_counter() - t) / 5 * 1e3))
+t = time.perf_counter()
+for s in range(5):
+    dg.product_step(o, s, "lcv", "gibbs")
+torch.cuda.synchronize()
+print("Pose3 helix: product_step with manikde! bandwidths + Gibbs product on SE(3)  %.3f ms" % ((time.perf_counter() - t) / 5 * 1e3))
