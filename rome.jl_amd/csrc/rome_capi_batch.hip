@@ -96,7 +96,7 @@ int rome_kde_bandwidth_dev(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const
   int rc = check_kde(c, dim, V, N, bel, bw); if (rc) return rc;
   ROME_BIND(c);
   ROME_HIP(c, launch_kde_bandwidth(dim, V, N, bel, circular_mask, tol_euclid > 0 ? tol_euclid : 1e-2,
-                                         tol_circular > 0 ? tol_circular : 1e-6, bw, nullptr, c->stream));
+                                         tol_circular > 0 ? tol_circular : 1e-6, bw, c->stream));
   return ROME_OK;
 }
 int rome_kde_bandwidth(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, uint32_t circular_mask,
@@ -110,7 +110,7 @@ int rome_kde_bandwidth(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const dou
   if ((rc = ensure(c, 1, nh, &d_h))) return rc;
   ROME_HIP(c, hipMemcpyAsync(d_b, bel, nb, hipMemcpyHostToDevice, c->stream));
   ROME_HIP(c, launch_kde_bandwidth(dim, V, N, (const double*)d_b, circular_mask, tol_euclid > 0 ? tol_euclid : 1e-2,
-                                         tol_circular > 0 ? tol_circular : 1e-6, (double*)d_h, nullptr, c->stream));
+                                         tol_circular > 0 ? tol_circular : 1e-6, (double*)d_h, c->stream));
   ROME_HIP(c, hipMemcpyAsync(bw, d_h, nh, hipMemcpyDeviceToHost, c->stream));
   ROME_HIP(c, hipStreamSynchronize(c->stream));
   return ROME_OK;

@@ -349,7 +349,7 @@ int plan_build(rome_ctx* c, rome_store* st, const rome_opts* o, const rome_cliqu
       double* mb = P->d_prop[t] + (size_t)msg_base[t] * kVdim[t] * N;
       if ((rc = stage_blocks(c, o->layout, n_msg[t], kVdim[t], N, msg_host[t], mb))) return rc;
       ROME_HIP(c, launch_kde_bandwidth(kVdim[t], n_msg[t], N, mb, kCircBw[t], 1e-2, 1e-6,
-                                             P->d_pbw[t] + (size_t)msg_base[t] * kVdim[t], nullptr, s));
+                                             P->d_pbw[t] + (size_t)msg_base[t] * kVdim[t], s));
     }
     P->tree_off[t] = t == 0 ? 0 : P->tree_need;
     if (t == 0) P->tree_need = 0;
@@ -411,7 +411,7 @@ int plan_run(rome_upsolve_plan* P, const rome_opts* o, double* mirror_out, int64
     if (P->n_smsg[t] > 0 && P->gi > 0) {
       ROME_HIP(c, launch_scatter_blocks(P->n_smsg[t], N, P->d_smsg_ent[t], P->d_prop[t], (int64_t)kVdim[t] * N, st->bel[0], st->bel[1], st->bel[2], s, /*to_store=*/0));
       ROME_HIP(c, launch_kde_bandwidth(kVdim[t], P->n_smsg[t], N, P->d_prop[t] + (size_t)P->smsg_base[t] * kVdim[t] * N, kCircBw[t], 1e-2, 1e-6,
-                                             P->d_pbw[t] + (size_t)P->smsg_base[t] * kVdim[t], nullptr, s));
+                                             P->d_pbw[t] + (size_t)P->smsg_base[t] * kVdim[t], s));
     }
   for (int it = 0; it < P->gi; ++it) {
     const uint64_t base = o->stream_offset + ((uint64_t)it << 32);
@@ -435,7 +435,7 @@ int plan_run(rome_upsolve_plan* P, const rome_opts* o, double* mirror_out, int64
         double* out = P->d_prop[f.vt] + (size_t)(f.base + lo) * f.dt * N;
         ROME_HIP(c, launch_fam(f, P->fd[k4], o, base, lo, hi, st->bel[f.vf], st->bel[f.vt], out, sx, st->bel[f.vmeas()]));
         if (P->max_k[f.vt] > 1)   // (a plan whose destinations take ONE proposal each -- sampling a graph's measurements, transporting a belief -- multiplies nothing: no manikde!)
-          ROME_HIP(c, launch_kde_bandwidth(f.dt, hi - lo, N, out, kCircBw[f.vt], 1e-2, 1e-6, P->d_pbw[f.vt] + (size_t)(f.base + lo) * f.dt, nullptr, sx));
+          ROME_HIP(c, launch_kde_bandwidth(f.dt, hi - lo, N, out, kCircBw[f.vt], 1e-2, 1e-6, P->d_pbw[f.vt] + (size_t)(f.base + lo) * f.dt, sx));
         return ROME_OK;
       });
       if (rc) return rc;
@@ -473,7 +473,7 @@ int plan_run(rome_upsolve_plan* P, const rome_opts* o, double* mirror_out, int64
     const int nu = P->n_upt[t];
     if (nu == 0) continue;
     if (P->bw_host[t]) {
-      ROME_HIP(c, launch_kde_bandwidth(kVdim[t], nu, N, st->bel[t], kCircBw[t], 1e-2, 1e-6, P->d_bwout[t], nullptr, s, P->d_upblock[t]));
+      ROME_HIP(c, launch_kde_bandwidth(kVdim[t], nu, N, st->bel[t], kCircBw[t], 1e-2, 1e-6, P->d_bwout[t], s, P->d_upblock[t]));
       ROME_HIP(c, hipMemcpyAsync(P->bw_host[t], P->d_bwout[t], (size_t)nu * kVdim[t] * 8, hipMemcpyDeviceToHost, s));
       sync = true;
     }

@@ -18,6 +18,7 @@
 namespace rome {
 
 constexpr int kKdeWaves = 4;
+template <int V> using Int = std::integral_constant<int, V>;   // a compile-time int as a function argument
 
 __device__ __forceinline__ double lcv_wrap(double d) { return d - 6.283185307179586476925287 * rint(d * 0.15915494309189533576888); }
 
@@ -73,10 +74,43 @@ __device__ __forceinline__ double lcv_negll(const double (&x)[S], const bool (&a
   return -(ll - (double)N * fast_log((double)(N - 1) * h * 2.50662827463100050241576528));
 }
 
+// The golden-section search (Numerical-Recipes form; oracle: ro_kde_bandwidth_lcv), shared by both kernels.  The fast kernel keeps
+// its search state in scalar registers across the unrolled block body: UNIFORM sends every update through readfirstlane
+// (uniform_f64: the value is unchanged); the slow kernel does not need it.
+__device__ __forceinline__ double uniform_f64(double v) {
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+template <bool UNIFORM>
+__device__ __forceinline__ double lcv_u(double v) { return UNIFORM ? uniform_f64(v) : v; }
+
+constexpr double kCg = 0.38196601125010515180, kRg = 0.61803398874989484820;
+struct Bracket {
+  double x0, x1, x2, x3;   // x0 < x1 < x2 < x3; x1, x2: the interior points
+  __device__ __forceinline__ bool wider_than(double tol) const { return fabs(x3 - x0) > tol * (fabs(x1) + fabs(x2)); }
+};
+// smallest pair distance mn and extent [ylo, yhi] about particle 0 -> the initial bracket and its two interior points
+template <bool UNIFORM>
+__device__ __forceinline__ Bracket lcv_bracket(double mn, double ylo, double yhi, int N) {
+  const double minm = fmax(mn, 1e-6), maxm = fmax(yhi - ylo, minm);
+  const double ax = lcv_u<UNIFORM>(2.0 * minm / (double)(N - 1)), bx = lcv_u<UNIFORM>(0.5 * (minm + maxm)), cx = lcv_u<UNIFORM>(2.0 * maxm);
+  Bracket b; b.x0 = ax; b.x3 = cx;
+  if (fabs(cx - bx) > fabs(bx - ax)) { b.x1 = bx; b.x2 = lcv_u<UNIFORM>(bx + kCg * (cx - bx)); }
+  else { b.x2 = bx; b.x1 = lcv_u<UNIFORM>(bx - kCg * (bx - ax)); }
+  return b;
+}
+// one golden-section step: the bracket closes on the side of the lower interior point (lower2: f(x2) < f(x1)); returns the new
+// interior point, x2 if lower2, else x1 -- the abscissa to evaluate next.  Rg·x + Cg·y is spelled as the contraction the recorded
+// bits were computed with, fma(Rg, x, Cg·y) with Cg·y rounded: left to the compiler, WHICH product is fused depends on the code around.
+template <bool UNIFORM>
+__device__ __forceinline__ double golden_advance(Bracket& b, bool lower2) {
+  if (lower2) { b.x0 = b.x1; b.x1 = b.x2; b.x2 = lcv_u<UNIFORM>(fma(kRg, b.x1, kCg * b.x3)); return b.x2; }
+  b.x3 = b.x2; b.x2 = b.x1; b.x1 = lcv_u<UNIFORM>(fma(kRg, b.x2, kCg * b.x0)); return b.x1;
+}
+
 template <int S, bool CIRC>
 __device__ __forceinline__ double lcv_golden(const double (&x)[S], const bool (&act)[S], const double* __restrict__ pts,
-                                             double* __restrict__ wbuf, int N, int lane, double tol, int* n_evals) {
-  // bracket: smallest pair distance and extent about particle 0 (oracle: ro_kde_bandwidth_lcv)
+                                             double* __restrict__ wbuf, int N, int lane, double tol) {
+  // smallest pair distance and extent about particle 0
   const double x0v = pts[0];
   double mn = __builtin_inf(), ylo = 0.0, yhi = 0.0;
 #pragma unroll
@@ -94,22 +128,13 @@ __device__ __forceinline__ double lcv_golden(const double (&x)[S], const bool (&
       if (act[s] && lane + 64 * s != j) mn = fmin(mn, fabs(d));
     }
   }
-  mn = wave_min(mn); ylo = wave_min(ylo); yhi = -wave_min(-yhi);
-  const double minm = fmax(mn, 1e-6), maxm = fmax(yhi - ylo, minm);
-  const double ax = 2.0 * minm / (double)(N - 1), bx = 0.5 * (minm + maxm), cx = 2.0 * maxm;
-  constexpr double Cg = 0.38196601125010515180, Rg = 0.61803398874989484820;
-  double x0 = ax, x3 = cx, x1, x2;
-  if (fabs(cx - bx) > fabs(bx - ax)) { x1 = bx; x2 = bx + Cg * (cx - bx); }
-  else { x2 = bx; x1 = bx - Cg * (bx - ax); }
-  double f1 = lcv_negll<S, CIRC>(x, act, pts, wbuf, N, lane, x1), f2 = lcv_negll<S, CIRC>(x, act, pts, wbuf, N, lane, x2);
-  int ne = 2;
-  while (fabs(x3 - x0) > tol * (fabs(x1) + fabs(x2)) && ne < 200) {
-    if (f2 < f1) { x0 = x1; x1 = x2; x2 = Rg * x1 + Cg * x3; f1 = f2; f2 = lcv_negll<S, CIRC>(x, act, pts, wbuf, N, lane, x2); }
-    else         { x3 = x2; x2 = x1; x1 = Rg * x2 + Cg * x0; f2 = f1; f1 = lcv_negll<S, CIRC>(x, act, pts, wbuf, N, lane, x1); }
-    ++ne;
+  Bracket b = lcv_bracket<false>(wave_min(mn), wave_min(ylo), -wave_min(-yhi), N);
+  double f1 = lcv_negll<S, CIRC>(x, act, pts, wbuf, N, lane, b.x1), f2 = lcv_negll<S, CIRC>(x, act, pts, wbuf, N, lane, b.x2);
+  for (int ne = 2; b.wider_than(tol) && ne < 200; ++ne) {
+    if (f2 < f1) { f1 = f2; f2 = lcv_negll<S, CIRC>(x, act, pts, wbuf, N, lane, golden_advance<false>(b, true)); }
+    else         { f2 = f1; f1 = lcv_negll<S, CIRC>(x, act, pts, wbuf, N, lane, golden_advance<false>(b, false)); }
   }
-  *n_evals = ne;
-  return f1 < f2 ? x1 : x2;
+  return f1 < f2 ? b.x1 : b.x2;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -174,13 +199,13 @@ __device__ __forceinline__ void lcv_g64(const double (&x)[2], const bool (&act)[
 
 // ---- blocked SYMMETRIC evaluation of the row sums (fast path, 8 <= N <= 128) -----------------------------------------------------
 // The N particles are cut into nb <= 10 blocks of B (7 for N <= 70, 10 for N <= 100, else 13; the tail padded with far-away points of
-// weight 0) and
-// every lane owns ONE unordered pair of blocks (a <= b): nb(nb+1)/2 <= 55 lanes busy.  A lane evaluates its B x B weights once and
+// weight 0) and every lane owns ONE unordered pair of blocks (a <= b): nb(nb+1)/2 <= 55 lanes busy.  A lane evaluates its B x B weights once and
 // accumulates them both ways -- B row partials for block a, B column partials for block b -- in registers, with the 2B particle
 // values in registers too: per UNORDERED pair 3 VALU + v_exp_f32 + 2 accumulates = 21 issue cycles (the ring scheme before it: 20
-// per ORDERED pair).  Partials go to an nb x nb matrix of cells in LDS, cell (p, q) = the partial sums of the rows of block p
-// against block q; row i then sums the nb cells of its block row (B-term single-precision partials, single-precision sums of
-// <= 10 of them, converted once).  The derivative sums T_i go through the same cells after the row sums have been read.
+// per ORDERED pair).  Partials go to one row of cells per particle in LDS, cell (i, q) = the partial sum of particle i against
+// block q (lcv_tail); row i then sums its cells (B-term single-precision partials, single-precision sums of <= 10 of them,
+// converted once).  The derivative sums T_i go through the same cells after the row sums have been read.
+
 // 1 / v for a positive normal double: single-precision seed + two Newton steps (relative error ~1e-16; an IEEE division costs 5x)
 __device__ __forceinline__ double rcp_pos_f64(double v) {
   const int e = __builtin_amdgcn_frexp_exp(v);                 // the seed is taken on the mantissa: v may be outside the float range
@@ -206,16 +231,16 @@ __device__ __forceinline__ void wave_prod_frexp(double* mant, int* expo) {
     m *= __hiloint2double(hi, lo);
     e += __builtin_amdgcn_update_dpp(0, e, CTRL, MASK, 0xF, false);
   };
-  bcast(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xA>{});   // row_bcast:15 -> rows 1, 3
-  bcast(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xC>{});   // row_bcast:31 -> rows 2, 3
+  bcast(Int<0x142>{}, Int<0xA>{});   // row_bcast:15 -> rows 1, 3
+  bcast(Int<0x143>{}, Int<0xC>{});   // row_bcast:31 -> rows 2, 3
   *mant = readlane_f64(m, 63);
   *expo = __builtin_amdgcn_readlane(e, 63);
 }
-__device__ __forceinline__ double uniform_f64(double v) {
-  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
+constexpr int kKdeMaxBlocks = 10;  // nb <= 10: what the dispatch edges of launch_kde_bandwidth give (70 / 7, 100 / 10, 128 / 13 rounded up)
+constexpr int kKdeRowPitch = 12;   // floats per row of cells (10 used; 48 bytes: 16-byte aligned rows)
+static_assert(kKdeMaxBlocks <= kKdeRowPitch, "a row of cells holds one partial per block");
 template <int B>
-__host__ __device__ constexpr int kdeCells(int N) { const int nb = (N + B - 1) / B; return nb * B * 12 > nb * nb * B ? nb * B * 12 : nb * nb * B; }   // floats per wave (either cell layout)
+__host__ __device__ constexpr int kdeCells(int N) { return (N + B - 1) / B * B * kKdeRowPitch; }   // floats per wave: nb·B rows of cells
 template <int B>
 struct BlkPlan { int nb, a, b; bool ok, diag; };
 template <int B>
@@ -229,30 +254,22 @@ __device__ __forceinline__ BlkPlan<B> blk_plan(int N, int lane) {
   return p;
 }
 
-// The tail of one evaluation: partial sums -> LDS cells -> row sums -> -LL (and g).  Cell layout (ROME_KDE_ROWCELLS, default):
-// row-major, cell(i, q) = partial sum of particle i against block q at M[i * kKdeRowPitch + q] -- a row's <= 10 partials are 40
-// contiguous bytes, read back with three 16-byte LDS reads in flight (the block-major layout before it walked them with a loop of
-// dependent 4-byte reads: ten LDS round trips per evaluation on the critical path of a search that is sequential by nature).
-// Columns q >= nb are zeroed once per task (lcv_cells_init) and never written: the sums keep their order and their bits.
-#ifndef ROME_KDE_ROWCELLS
-#define ROME_KDE_ROWCELLS 1
-#endif
-constexpr int kKdeRowPitch = 12;   // floats per row of cells (10 used; 48 bytes: 16-byte aligned rows)
+// The tail of one evaluation: partial sums -> LDS cells -> row sums -> -LL (and g).  Cell layout: row-major, cell(i, q) = partial
+// sum of particle i against block q at M[i * kKdeRowPitch + q] -- a row's <= 10 partials are 40 contiguous bytes, read back with
+// three 16-byte LDS reads in flight.  Columns q >= nb are zeroed once per task (lcv_cells_init) and never written: the sums keep
+// their order and their bits.
+// (rejected: block-major cells, an nb x nb matrix of B partials walked with a loop of dependent 4-byte reads -- ten LDS round trips
+// per evaluation on the critical path of a search that is sequential by nature: 1.338 ms against 1.295, profiles/r03_kde_experiments.txt)
 template <int B>
 __device__ __forceinline__ void lcv_cells_init(float* __restrict__ M, int N, int lane) {
-#if ROME_KDE_ROWCELLS
-  const int nb = (N + B - 1) / B;
-  for (int q = lane; q < nb * B * kKdeRowPitch; q += 64) M[q] = 0.0f;
+  for (int q = lane; q < kdeCells<B>(N); q += 64) M[q] = 0.0f;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-#endif
 }
 template <bool WITH_T, int B, bool FOLD64 = WITH_T>
 __device__ __forceinline__ void lcv_tail(const BlkPlan<B>& pl, const float (&r)[B], const float (&c)[B], const float (&tr)[B], const float (&tc)[B],
                                          float* __restrict__ M, int N, int lane, double h, double tscale, double* negll, double* g) {
-  const int nb = pl.nb;
   const int i0 = lane, i1 = lane + 64;
   const bool act0 = i0 < N, act1 = i1 < N;
-#if ROME_KDE_ROWCELLS
   float* cr = M + (pl.a * B) * kKdeRowPitch + pl.b;
   float* cc = M + (pl.b * B) * kKdeRowPitch + pl.a;
   const float* row0 = M + i0 * kKdeRowPitch;
@@ -267,9 +284,9 @@ __device__ __forceinline__ void lcv_tail(const BlkPlan<B>& pl, const float (&r)[
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    float v0[12], v1[12];
+    float v0[kKdeRowPitch], v1[kKdeRowPitch];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
+    for (int q = 0; q < kKdeRowPitch / 4; ++q) {
       const float4 a = *reinterpret_cast<const float4*>(row0 + 4 * q), b = *reinterpret_cast<const float4*>(row1 + 4 * q);
       v0[4 * q] = a.x; v0[4 * q + 1] = a.y; v0[4 * q + 2] = a.z; v0[4 * q + 3] = a.w;
       v1[4 * q] = b.x; v1[4 * q + 1] = b.y; v1[4 * q + 2] = b.z; v1[4 * q + 3] = b.w;
@@ -277,44 +294,16 @@ __device__ __forceinline__ void lcv_tail(const BlkPlan<B>& pl, const float (&r)[
     if (FOLD64) {   // the derivative finish resolves 1e-6: the <= 10 partials of a row are folded in double (as the ring scheme did)
       double s0 = 0.0, s1 = 0.0;
 #pragma unroll
-      for (int k = 0; k < 10; ++k) { s0 += (double)v0[k]; s1 += (double)v1[k]; }
+      for (int k = 0; k < kKdeMaxBlocks; ++k) { s0 += (double)v0[k]; s1 += (double)v1[k]; }
       *o0 = s0; *o1 = s1;
     } else {
       float s0 = 0.0f, s1 = 0.0f;
 #pragma unroll
-      for (int k = 0; k < 10; ++k) { s0 += v0[k]; s1 += v1[k]; }
+      for (int k = 0; k < kKdeMaxBlocks; ++k) { s0 += v0[k]; s1 += v1[k]; }
       *o0 = (double)s0; *o1 = (double)s1;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();   // the cells are rewritten next
   };
-#else
-  float* cr = M + (pl.a * nb + pl.b) * B;
-  float* cc = M + (pl.b * nb + pl.a) * B;
-  const int b0 = i0 / B, b1 = (act1 ? i1 : 0) / B;
-  const float* row0 = M + b0 * nb * B + (i0 - b0 * B);
-  const float* row1 = M + b1 * nb * B + ((act1 ? i1 : 0) - b1 * B);
-  auto exchange = [&](const float (&pr)[B], const float (&pc)[B], double* o0, double* o1) {
-    if (pl.ok) {
-#pragma unroll
-      for (int u = 0; u < B; ++u) cr[u] = pr[u];
-      if (!pl.diag) {
-#pragma unroll
-        for (int u = 0; u < B; ++u) cc[u] = pc[u];
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-    if (FOLD64) {
-      double s0 = 0.0, s1 = 0.0;
-      for (int k = 0; k < nb; ++k) { s0 += (double)row0[k * B]; s1 += (double)row1[k * B]; }
-      *o0 = s0; *o1 = s1;
-    } else {
-      float s0 = 0.0f, s1 = 0.0f;
-      for (int k = 0; k < nb; ++k) { s0 += row0[k * B]; s1 += row1[k * B]; }
-      *o0 = (double)s0; *o1 = (double)s1;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();   // the cells are rewritten next
-  };
-#endif
   double S0, S1, T0 = 0.0, T1 = 0.0;
   exchange(r, c, &S0, &S1);
   if (WITH_T) exchange(tr, tc, &T0, &T1);
@@ -373,11 +362,17 @@ __device__ __forceinline__ void lcv_eval_blk(const BlkPlan<B>& pl, const float* 
   else { lcv_tail<true, B>(pl, r, c, tr, tc, M, N, lane, h, 1.0, negll, g); }
 }
 
+// The fast search is a small state machine around its evaluation site; the phase says what the evaluation asked for is: the
+// likelihood at x1, at the new interior point of a golden-section step, g at x1 and at x2 (`nowrap` only), g at a secant iterate
+enum class Phase { FirstPoint, Golden, DerivX1, DerivX2, Secant };
+struct LcvEval { double f, g; };     // -LL(h) and g(h) of one evaluation
+struct TiePair { double e1, e2; };   // the two likelihoods a golden-section decision compares
+
 template <bool CIRC, int B>
 __device__ __forceinline__ double lcv_golden_fast(const double (&x)[2], const bool (&act)[2], const double* __restrict__ pts,
                                                   float* __restrict__ xs, float* __restrict__ M, double* __restrict__ wbuf, int N, int lane,
-                                                  double tol, int* n_evals) {
-  // bracket: smallest pair distance and extent about particle 0 (oracle: ro_kde_bandwidth_lcv) -- in double, as the slow path
+                                                  double tol) {
+  // smallest pair distance and extent about particle 0 -- in double, as the slow path
   const double x0v = pts[0];
   double mn = __builtin_inf(), ylo = 0.0, yhi = 0.0;
   {
@@ -409,129 +404,137 @@ __device__ __forceinline__ double lcv_golden_fast(const double (&x)[2], const bo
     }
   }
   mn = uniform_f64(wave_min(mn)); ylo = uniform_f64(wave_min(ylo)); yhi = uniform_f64(-wave_min(-yhi));
-  // the search state is wave-uniform: every update goes through readfirstlane (U) so that it lives in scalar registers across the
-  // unrolled block body instead of being spilled around it
-#define U(v) uniform_f64(v)
-  const double minm = fmax(mn, 1e-6), maxm = fmax(yhi - ylo, minm);
-  const double ax = U(2.0 * minm / (double)(N - 1)), bx = U(0.5 * (minm + maxm)), cx = U(2.0 * maxm);
-  constexpr double Cg = 0.38196601125010515180, Rg = 0.61803398874989484820;
-  double x0 = ax, x3 = cx, x1, x2;
-  if (fabs(cx - bx) > fabs(bx - ax)) { x1 = bx; x2 = U(bx + Cg * (cx - bx)); }
-  else { x2 = bx; x1 = U(bx - Cg * (bx - ax)); }
+  // the search state is wave-uniform: every update goes through readfirstlane (lcv_u<true>, uniform_f64) so that it lives in scalar
+  // registers across the unrolled block body instead of being spilled around it
+  Bracket b = lcv_bracket<true>(mn, ylo, yhi, N);
   const bool finish = tol < 1e-2;          // finer than the golden section is run in single precision: finish on the derivative
   const bool nowrap = CIRC && (yhi - ylo) < 3.0;
   const double tol_gs = finish ? 1e-2 : tol;
-  // ONE evaluation site (the unrolled B x B body is a few kB of code per instantiation): a small state machine asks for the next h.
-  //   phase 0 / 1: the two interior points; 2: golden section (`upper`: the request replaces x2, else x1); 3: secant on g
-  double f1 = 0.0, f2 = 0.0, g1 = 0.0, g2 = 0.0, best = x1;
-  double ha = 0.0, ga = 0.0, hb = 0.0, gb = 0.0, lo = 0.0, hi = 0.0;
-  int ne = 0, phase = 0, it = 0;
-  bool upper = false;
-  double hq = x1;
+  double f1 = 0.0, f2 = 0.0, g1 = 0.0, g2 = 0.0, best = b.x1;
+  double ha = 0.0, ga = 0.0, hb = 0.0, gb = 0.0, lo = 0.0, hi = 0.0;   // the secant's two points and the interval it may not leave
+  int ne = 0, it = 0;
+  bool upper = false;                      // Golden: the evaluation asked for replaces x2 (else x1)
+  double hq = b.x1;                        // the abscissa asked for
+  Phase phase = Phase::FirstPoint;
+  // ONE evaluation site per instantiation (the unrolled B x B body is a few kB of code each): the loop below asks it for the next h
+  auto evaluate = [&](double h, Phase ph) {
+    LcvEval e;
+    if (!finish) lcv_eval_blk<CIRC, false, B>(pl, xs, M, N, lane, h, &e.f, &e.g);
+    else if (!(CIRC && nowrap)) lcv_eval_blk<CIRC, true, B>(pl, xs, M, N, lane, h, &e.f, &e.g);
+    // a circular coordinate whose particles all lie within 3 rad of each other: every staged difference has |d| < π, its wrap is
+    // the identity (rint(d / 2π) = 0, fma(-2π, 0, d) = d exactly) -- the Euclidean body evaluates the same bits with 3 of 12
+    // instructions per pair less (wave-uniform choice; headings of pose beliefs are almost always that concentrated)
+    // ... and its golden section needs likelihood VALUES only: the derivative sums T_i (3 of 9 instructions per pair, a second
+    // exchange, two reciprocals and a wave sum per evaluation) are left out of those ~17 evaluations -- same row sums, same double
+    // fold, same f bits -- and g is evaluated at the two interior points the secant starts from (DerivX1, DerivX2: two evaluations more)
+    else if (ph == Phase::FirstPoint || ph == Phase::Golden) lcv_eval_blk<false, false, B, true>(pl, xs, M, N, lane, h, &e.f, &e.g);
+    else lcv_eval_blk<false, true, B>(pl, xs, M, N, lane, h, &e.f, &e.g);
+    return e;
+  };
+  // the pair (e1, e2) a golden-section decision compares: the single-precision likelihoods at x1 and x2, or, when those are closer
+  // than kTieEps (wave-uniform), both re-evaluated in double precision
+  auto tie_decision = [&] {
+    TiePair c = {f1, f2};
+    if (!finish && fabs(f2 - f1) < kTieEps) {
+      c.e1 = lcv_negll<2, CIRC>(x, act, pts, wbuf, N, lane, b.x1); c.e2 = lcv_negll<2, CIRC>(x, act, pts, wbuf, N, lane, b.x2);
+    }
+    return c;
+  };
+  // (the steps stay written out in the loop, and in this form: the register allocation of these kernels sits at 128 VGPRs, and with
+  // the steps as lambdas, or the two Golden blocks below joined, spills move into the evaluations -- profiles/kde_one_body.md)
   for (;;) {
-    double fv, gv;
-    if (finish) {
-      // a circular coordinate whose particles all lie within 3 rad of each other: every staged difference has |d| < π, its wrap is
-      // the identity (rint(d / 2π) = 0, fma(-2π, 0, d) = d exactly) -- the Euclidean body evaluates the same bits with 3 of 12
-      // instructions per pair less (wave-uniform choice; headings of pose beliefs are almost always that concentrated)
-      // ... and its golden section needs likelihood VALUES only: the derivative sums T_i (3 of 9 instructions per pair, a second
-      // exchange, two reciprocals and a wave sum per evaluation) are left out of those ~17 evaluations -- same row sums, same double
-      // fold, same f bits -- and g is evaluated at the two interior points the secant starts from (phases 4, 5: two evaluations more)
-      if (CIRC && nowrap) {
-        if (phase <= 2) lcv_eval_blk<false, false, B, true>(pl, xs, M, N, lane, hq, &fv, &gv);
-        else lcv_eval_blk<false, true, B>(pl, xs, M, N, lane, hq, &fv, &gv);
-      } else lcv_eval_blk<CIRC, true, B>(pl, xs, M, N, lane, hq, &fv, &gv);
-    } else lcv_eval_blk<CIRC, false, B>(pl, xs, M, N, lane, hq, &fv, &gv);
+    const Phase ph = phase;   // what this evaluation is
+    const LcvEval e = evaluate(hq, phase);
+    const double fv = e.f, gv = e.g;
     ++ne;
-    if (phase == 0) { f1 = fv; g1 = gv; hq = x2; phase = 1; continue; }
-    if (phase == 1) { f2 = fv; g2 = gv; phase = 2; }
-    else if (phase == 2) { if (upper) { f2 = fv; g2 = gv; } else { f1 = fv; g1 = gv; } }
-    if (phase == 2) {
-      if (fabs(x3 - x0) > tol_gs * (fabs(x1) + fabs(x2)) && ne < 200) {
-        bool lower2 = f2 < f1;
-#ifndef ROME_KDE_EXPERIMENT_NO_TIES
-        if (!finish && fabs(f2 - f1) < kTieEps) {   // wave-uniform: decide in double precision
-          const double e1 = lcv_negll<2, CIRC>(x, act, pts, wbuf, N, lane, x1), e2 = lcv_negll<2, CIRC>(x, act, pts, wbuf, N, lane, x2);
-          lower2 = e2 < e1;
-        }
-#endif
-        if (lower2) { x0 = x1; x1 = x2; x2 = U(Rg * x1 + Cg * x3); f1 = f2; g1 = g2; hq = x2; upper = true; }
-        else        { x3 = x2; x2 = x1; x1 = U(Rg * x2 + Cg * x0); f2 = f1; g2 = g1; hq = x1; upper = false; }
+    // first points: f at x1 is in, x2 is asked for as a golden step's upper point
+    if (ph == Phase::FirstPoint) { f1 = fv; g1 = gv; hq = b.x2; phase = Phase::Golden; upper = true; continue; }
+    if (ph == Phase::Golden) { if (upper) { f2 = fv; g2 = gv; } else { f1 = fv; g1 = gv; } }
+    if (ph == Phase::Golden) {
+      if (b.wider_than(tol_gs) && ne < 200) {   // golden step: close the bracket on the lower side, ask for the new interior point
+        const TiePair c = tie_decision();
+        const bool lower2 = c.e2 < c.e1;
+        hq = golden_advance<true>(b, lower2);
+        if (lower2) { f1 = f2; g1 = g2; upper = true; }
+        else        { f2 = f1; g2 = g1; upper = false; }
         continue;
       }
-      best = f1 < f2 ? x1 : x2;
-      if (!finish) {
-#ifndef ROME_KDE_EXPERIMENT_NO_TIES
-        if (fabs(f2 - f1) < kTieEps) {
-          const double e1 = lcv_negll<2, CIRC>(x, act, pts, wbuf, N, lane, x1), e2 = lcv_negll<2, CIRC>(x, act, pts, wbuf, N, lane, x2);
-          best = e1 < e2 ? x1 : x2;
-        }
-#endif
-        break;
-      }
-      if (CIRC && nowrap) { hq = x1; phase = 4; continue; }   // (the derivative at x1, then at x2)
+      const TiePair c = tie_decision();         // final pick
+      best = c.e1 < c.e2 ? b.x1 : b.x2;
+      if (!finish) break;
+      if (CIRC && nowrap) { hq = b.x1; phase = Phase::DerivX1; continue; }   // derivative at the interior points: x1, then x2
     }
-    if (phase == 4) { g1 = gv; hq = x2; phase = 5; continue; }
-    if (phase == 2 || phase == 5) {
-      if (phase == 5) g2 = gv;
-      // secant steps on g from the two interior points; the iterate may leave the last bracket by its width (a near-tie decision
-      // of the single-precision golden section), never further (flat or noisy g: keep the golden-section answer)
-      const double wdt = x3 - x0;
-      lo = U(fmax(x0 - wdt, 0.5 * x0)); hi = U(x3 + wdt);
-      ha = x1; ga = g1; hb = x2; gb = g2;
-      phase = 3;
-    } else {   // phase 3: the evaluation at hq is in (fv, gv)
+    if (ph == Phase::DerivX1) { g1 = gv; hq = b.x2; phase = Phase::DerivX2; continue; }
+    if (ph == Phase::Golden || ph == Phase::DerivX2) {
+      // secant setup: from the two interior points and their g (a wrapped golden section accumulated g along with f); the iterate
+      // may leave the last bracket by its width (a near-tie decision of the single-precision golden section), never further
+      // (flat or noisy g: keep the golden-section answer)
+      if (ph == Phase::DerivX2) g2 = gv;
+      const double wdt = b.x3 - b.x0;
+      lo = uniform_f64(fmax(b.x0 - wdt, 0.5 * b.x0)); hi = uniform_f64(b.x3 + wdt);
+      ha = b.x1; ga = g1; hb = b.x2; gb = g2;
+      phase = Phase::Secant;
+    } else {   // secant step: g at the iterate hq is in
       const bool done = fabs(hq - hb) <= fmax(tol, 1e-4) * fabs(hq);   // (the double-precision Newton step below squares what is left)
       ha = hb; ga = gb; hb = hq; gb = gv;
       best = hq;
       if (done || ++it >= 5) break;
     }
-    const double den = gb - ga;
+    const double den = gb - ga;   // the next secant iterate, if there is one
     if (!(fabs(den) > 0.0)) break;
-    const double hc = U(hb - gb * (hb - ha) / den);
+    const double hc = uniform_f64(hb - gb * (hb - ha) / den);
     if (!(hc > lo && hc < hi)) break;
     hq = hc;
   }
-#ifndef ROME_KDE_EXPERIMENT_NO_G64
   if (finish && best == hb) {   // one Newton step in double precision (value and derivative of g)
     double g64, dg64;
     lcv_g64<CIRC>(x, act, pts, N, lane, hb, &g64, &dg64);
     const double hn = hb - g64 / dg64;
-    ++ne;
     if (dg64 < 0.0 && hn > lo && hn < hi && fabs(hn - hb) < 1e-2 * hb) best = hn;
   }
-#endif
-#undef U
-  *n_evals = ne;
   return best;
 }
+
+// One wave's (belief, coordinate) task, S particle slots per lane: which task, where its particles are, the lane's own particles in
+// registers and all N of them in the wave's LDS row; and the result write.
+template <int S>
+struct KdeTask {
+  int lane, wave, t;
+  bool circ;
+  double x[S];   // own particles l, l+64, ...; idle slots shadow particle 0
+  bool act[S];
+  // false: the wave has no task (wave-uniform; nothing after it synchronises across waves)
+  __device__ __forceinline__ bool stage(int T, int dim, int N, const double* __restrict__ bel, uint32_t circ_mask,
+                                        const int32_t* __restrict__ block_idx, double (&pts)[kKdeWaves][64 * S]) {
+    lane = threadIdx.x & 63; wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    t = blockIdx.x * kKdeWaves + wave;
+    if (t >= T) return false;
+    circ = (circ_mask >> (t % dim)) & 1u;
+    // (block_idx: belief t / dim lives in block block_idx[t / dim] of `bel` -- a scattered subset of a store; wave-uniform)
+    const double* __restrict__ P = bel + (block_idx ? (size_t)block_idx[t / dim] * dim + (size_t)(t % dim) : (size_t)t) * N;
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const int i = lane + 64 * s;
+      act[s] = i < N;
+      x[s] = P[act[s] ? i : 0];
+      if (act[s]) pts[wave][i] = x[s];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+    return true;
+  }
+  __device__ __forceinline__ void store(double* __restrict__ bw, double h) const { if (lane == 0) bw[t] = h; }
+};
 
 template <int S>
 __global__ void __launch_bounds__(64 * kKdeWaves) k_kde_bandwidth(int T, int dim, int N, const double* __restrict__ bel,
                                                                   uint32_t circ_mask, double tol_e, double tol_c,
-                                                                  double* __restrict__ bw, int32_t* __restrict__ evals, const int32_t* __restrict__ block_idx) {
+                                                                  double* __restrict__ bw, const int32_t* __restrict__ block_idx) {
   __shared__ double pts[kKdeWaves][64 * S];
   __shared__ double wex[kKdeWaves][64 * S];   // per-wave exchange row of the symmetric likelihood evaluation
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t = blockIdx.x * kKdeWaves + wave;
-  if (t >= T) return;   // wave-uniform; nothing below synchronises across waves
-  const bool circ = (circ_mask >> (t % dim)) & 1u;
-  // (block_idx: belief t / dim lives in block block_idx[t / dim] of `bel` -- a scattered subset of a store; wave-uniform)
-  const double* __restrict__ P = bel + (block_idx ? (size_t)block_idx[t / dim] * dim + (size_t)(t % dim) : (size_t)t) * N;
-  double x[S];
-  bool act[S];
-#pragma unroll
-  for (int s = 0; s < S; ++s) {
-    const int i = lane + 64 * s;
-    act[s] = i < N;
-    x[s] = P[act[s] ? i : 0];
-    if (act[s]) pts[wave][i] = x[s];
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-  int ne = 0;
-  const double h = circ ? lcv_golden<S, true>(x, act, pts[wave], wex[wave], N, lane, tol_c, &ne)
-                        : lcv_golden<S, false>(x, act, pts[wave], wex[wave], N, lane, tol_e, &ne);
-  if (lane == 0) { bw[t] = h; if (evals) evals[t] = ne; }
+  KdeTask<S> k;
+  if (!k.stage(T, dim, N, bel, circ_mask, block_idx, pts)) return;
+  k.store(bw, k.circ ? lcv_golden<S, true>(k.x, k.act, pts[k.wave], wex[k.wave], N, k.lane, tol_c)
+                     : lcv_golden<S, false>(k.x, k.act, pts[k.wave], wex[k.wave], N, k.lane, tol_e));
 }
 
 // the fast path as its own kernel per block size (register allocation is per kernel: the B = 13 bodies must not set the occupancy of
@@ -542,32 +545,16 @@ __global__ void __launch_bounds__(64 * kKdeWaves) k_kde_bandwidth(int T, int dim
 template <int B>
 __global__ void __launch_bounds__(64 * kKdeWaves) __attribute__((amdgpu_waves_per_eu(4, 8)))
 k_kde_bandwidth_fast(int T, int dim, int N, const double* __restrict__ bel, uint32_t circ_mask, double tol_e, double tol_c,
-                     double* __restrict__ bw, int32_t* __restrict__ evals, const int32_t* __restrict__ block_idx) {
+                     double* __restrict__ bw, const int32_t* __restrict__ block_idx) {
   __shared__ double pts[kKdeWaves][128];
   __shared__ double wex[kKdeWaves][128];   // exchange row of the double-precision evaluations (tie decisions)
   __shared__ float xsbuf[kKdeWaves][136];  // the particles as single-precision offsets from particle 0 (+ padding)
-  extern __shared__ float cellbuf[];       // per wave nb x nb cells of B partial sums (sized by the launcher)
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t = blockIdx.x * kKdeWaves + wave;
-  if (t >= T) return;   // wave-uniform; nothing below synchronises across waves
-  const bool circ = (circ_mask >> (t % dim)) & 1u;
-  // (block_idx: belief t / dim lives in block block_idx[t / dim] of `bel` -- a scattered subset of a store; wave-uniform)
-  const double* __restrict__ P = bel + (block_idx ? (size_t)block_idx[t / dim] * dim + (size_t)(t % dim) : (size_t)t) * N;
-  double x[2];
-  bool act[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    const int i = lane + 64 * s;
-    act[s] = i < N;
-    x[s] = P[act[s] ? i : 0];
-    if (act[s]) pts[wave][i] = x[s];
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-  int ne = 0;
-  float* M = cellbuf + wave * kdeCells<B>(N);
-  const double h = circ ? lcv_golden_fast<true, B>(x, act, pts[wave], xsbuf[wave], M, wex[wave], N, lane, tol_c, &ne)
-                        : lcv_golden_fast<false, B>(x, act, pts[wave], xsbuf[wave], M, wex[wave], N, lane, tol_e, &ne);
-  if (lane == 0) { bw[t] = h; if (evals) evals[t] = ne; }
+  extern __shared__ float cellbuf[];       // per wave nb·B rows of kKdeRowPitch cells (kdeCells<B>(N) floats; sized by the launcher)
+  KdeTask<2> k;
+  if (!k.stage(T, dim, N, bel, circ_mask, block_idx, pts)) return;
+  float* M = cellbuf + k.wave * kdeCells<B>(N);
+  k.store(bw, k.circ ? lcv_golden_fast<true, B>(k.x, k.act, pts[k.wave], xsbuf[k.wave], M, wex[k.wave], N, k.lane, tol_c)
+                     : lcv_golden_fast<false, B>(k.x, k.act, pts[k.wave], xsbuf[k.wave], M, wex[k.wave], N, k.lane, tol_e));
 }
 
 // ---- max-density point of a belief per coordinate (⚠IIF getKDEMax: PPE `max`, `suggested` heading) --------------------------
@@ -623,24 +610,24 @@ hipError_t launch_kde_max(int dim, int V, int N, int G, double extend, const dou
 }
 
 hipError_t launch_kde_bandwidth(int dim, int V, int N, const double* bel, uint32_t circ_mask, double tol_e, double tol_c,
-                                double* bw, int32_t* evals, hipStream_t s, const int32_t* block_idx) {
+                                double* bw, hipStream_t s, const int32_t* block_idx) {
   const int T = V * dim;
   if (T <= 0) return hipSuccess;
   const dim3 grid((T + kKdeWaves - 1) / kKdeWaves), block(64 * kKdeWaves);
-#define ROME_LAUNCH_KDE(SS) hipLaunchKernelGGL((k_kde_bandwidth<SS>), grid, block, 0, s, T, dim, N, bel, circ_mask, tol_e, tol_c, bw, evals, block_idx)
-  if (N < 8) ROME_LAUNCH_KDE(1);
-  else if (N <= 70)
-    hipLaunchKernelGGL((k_kde_bandwidth_fast<7>), grid, block, sizeof(float) * kKdeWaves * (size_t)kdeCells<7>(N), s, T, dim, N, bel, circ_mask,
-                       tol_e, tol_c, bw, evals, block_idx);
-  else if (N <= 100)
-    hipLaunchKernelGGL((k_kde_bandwidth_fast<10>), grid, block, sizeof(float) * kKdeWaves * (size_t)kdeCells<10>(N), s, T, dim, N, bel, circ_mask,
-                       tol_e, tol_c, bw, evals, block_idx);
-  else if (N <= 128)
-    hipLaunchKernelGGL((k_kde_bandwidth_fast<13>), grid, block, sizeof(float) * kKdeWaves * (size_t)kdeCells<13>(N), s, T, dim, N, bel, circ_mask,
-                       tol_e, tol_c, bw, evals, block_idx);
-  else if (N <= 256) ROME_LAUNCH_KDE(4);
-  else ROME_LAUNCH_KDE(8);
-#undef ROME_LAUNCH_KDE
+  auto slow = [&](auto S) {   // S slots per lane, N <= 64 S
+    hipLaunchKernelGGL((k_kde_bandwidth<decltype(S)::value>), grid, block, 0, s, T, dim, N, bel, circ_mask, tol_e, tol_c, bw, block_idx);
+  };
+  auto fast = [&](auto B) {   // blocks of B particles, N <= kKdeMaxBlocks B; the cells are dynamic LDS
+    constexpr int b = decltype(B)::value;
+    hipLaunchKernelGGL((k_kde_bandwidth_fast<b>), grid, block, sizeof(float) * kKdeWaves * (size_t)kdeCells<b>(N), s, T, dim, N, bel, circ_mask,
+                       tol_e, tol_c, bw, block_idx);
+  };
+  if (N < 8) slow(Int<1>{});
+  else if (N <= 70) fast(Int<7>{});
+  else if (N <= 100) fast(Int<10>{});
+  else if (N <= 128) fast(Int<13>{});
+  else if (N <= 256) slow(Int<4>{});
+  else slow(Int<8>{});
   return hipGetLastError();
 }
 

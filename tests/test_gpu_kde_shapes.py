@@ -2,7 +2,13 @@
 against the references of tests/kde_ref.py at every launch shape: EVERY task of every table is decided by rule 1 (same iterates, 64 ulp),
 rule 2 (optimum in the reference's basin) or rule 3 (root of the derivative within the caller's stopping rule).  The rules, the bounds and
 the CPU conditions that make them total are stated in kde_ref's docstring and checked in tests/test_kde_ref_host.py; nothing here comes
-from a GPU run."""
+from a GPU run, except tests/golden/kde_bits.json: the sha256 of the output bytes of every run and table below, written by
+scripts/kde_bits.py on an MI355X from the library of commit 9f5f8f2, the last one before rome_kde.hip was rewritten to say each thing
+once (profiles/kde_one_body.md).  That commit passes every rule test here, so the recorded bits are bits the rules accept."""
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -159,3 +165,18 @@ def test_kde_max_refuses_257_grid_points_and_no_particles():
         R.kde_max(np.zeros((V, dim, 0)), t["bw"], 64)
     DG.ctx.synchronize()
     assert bool(torch.isnan(buf).all()), "a refused call wrote to its output"
+
+
+def test_output_bits_are_the_recorded_ones():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("kde_bits", os.path.join(root, "scripts", "kde_bits.py"))
+    bits = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bits)
+    with open(os.path.join(root, "tests", "golden", "kde_bits.json")) as f:
+        want = json.load(f)["sha256"]
+    runs = [bits.run_key(name, mask, tols) for name, make in TABLES.items() for t in [make()] for mask in t["masks"] for tols in t["runs"]]
+    assert sorted(want) == sorted(runs + list(MAX_TABLES)) and len(want) == len(runs) + len(MAX_TABLES)
+    got = bits.hashes()
+    assert sorted(got) == sorted(want)
+    diff = [k for k in got if got[k] != want[k]]
+    assert not diff, diff

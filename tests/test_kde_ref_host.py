@@ -22,10 +22,19 @@ MAX_TABLES = dict(KR.all_max_tables())
 def test_launch_shape_mirrors_the_dispatch_and_every_class_is_run():
     src = open(os.path.join(ROOT, "rome.jl_amd", "csrc", "rome_kde.hip")).read()
     body = src[src.index("hipError_t launch_kde_bandwidth"):]
-    assert re.search(r"if \(N < 8\) ROME_LAUNCH_KDE\(1\);", body)
-    for B, top in ((7, 70), (10, 100), (13, 128)):
-        assert re.search(r"else if \(N <= %d\)\s*hipLaunchKernelGGL\(\(k_kde_bandwidth_fast<%d>\)" % (top, B), body)
-    assert re.search(r"else if \(N <= 256\) ROME_LAUNCH_KDE\(4\);\s*else ROME_LAUNCH_KDE\(8\);", body)
+    assert re.search(r"auto slow = \[&\]\(auto S\) \{[^{}]*hipLaunchKernelGGL\(\(k_kde_bandwidth<decltype\(S\)::value>\)", body)
+    assert re.search(r"auto fast = \[&\]\(auto B\) \{[^{}]*constexpr int b = decltype\(B\)::value;\s*hipLaunchKernelGGL\(\(k_kde_bandwidth_fast<b>\)", body)
+    assert body.count("hipLaunchKernelGGL") == 2                                  # each launch is written once
+    chain = re.findall(r"^  (if|else if|else)(?: \(N (<|<=) (\d+)\))? (slow|fast)\(Int<(\d+)>\{\}\);$", body, re.M)
+    assert [c[0] for c in chain] == ["if"] + ["else if"] * 4 + ["else"] and body.count("Int<") == 6
+    tops = [int(n) - (op == "<") for _, op, n, _, _ in chain[:-1]]               # the largest N of every class but the last
+    assert tops == [7, 70, 100, 128, 256]
+
+    def dispatched(N):                                                            # the class the chain in the source launches for N
+        kind, arg = next(((k, a) for (_, _, _, k, a), top in zip(chain, tops) if N <= top), chain[-1][3:])
+        return kind + arg
+    for top in tops:                                                              # every dispatch edge and the class on both sides of it
+        assert dispatched(top) == KR.launch_shape(top)["cls"] != KR.launch_shape(top + 1)["cls"] == dispatched(top + 1), top
     assert int(re.search(r"constexpr int kKdeWaves = (\d+);", src).group(1)) == KR.KDE_WAVES
     assert float(re.search(r"constexpr double kTieEps = ([0-9.e-]+);", src).group(1)) == KR.TIE_EPS
     assert re.search(r"nowrap = CIRC && \(yhi - ylo\) < 3\.0;", src) and KR.WRAP_EXTENT == 3.0
