@@ -677,6 +677,29 @@ int rome_product_bw_dev(rome_ctx*, const rome_opts*, int32_t dim, int32_t V, con
 int rome_product_gibbs_dev(rome_ctx*, const rome_opts*, int32_t dim, int32_t V, const int32_t* prop_ptr, const int32_t* prop_rows,
                            const double* prop, const double* prop_bw, int32_t n_prop_rows, const double* bel_in, double* bel_out,
                            uint32_t circular_mask, int32_t gibbs_iters, int32_t max_proposals);
+/* rome_product_partial*: stage 2 of the partial-aware product -- what IIF does with the proposals of partial factors
+ *   (Pose3Pose3XYYaw: coordinates {0, 1, 5}; PriorPose3ZRP: {2, 3, 4}; Pose2Point2Range towards the pose: {0, 1}; 0-based), whose
+ *   other coordinates only repeat the target's own particles and must not count as evidence.  Stage 1 is the caller's: one of the
+ *   products above over the FULL proposal rows only, its result J left in bel [V][dim][N].  Here task t = (task_var[t], task_coord[t])
+ *   rewrites ONE line bel[v][c][0..N) in place: the 1-D importance product (the dim = 1 case of rome_product_bw_dev's definition) of the
+ *   marginals prop[r][c][.] of the rows r = task_rows[task_ptr[t] .. task_ptr[t+1]) in that order and, last, of J[v][c][.] itself when
+ *   task_joint[t] != 0 (v has full rows).  One density: copied bit for bit.  Two or more: h_l = max(bw_l, 1e-6) with bw_l =
+ *   prop_bw[r][c] / joint_bw[v][c], or Silverman's (4/(3N))^(1/5)·sd_l where that array is NULL (sd about point 0, divisor N - 1);
+ *   base = the smallest h_l (ties: lowest l); weights of the base points by a running log-sum-exp over the other densities;
+ *   systematic resampling on ONE uniform of Philox stream opts->stream_offset + v·dim + c; output = picked base point + h_p·ξ_i,
+ *   1/h_p² = Σ_l 1/h_l², ξ_i the 1-D normal of (seed, stream, i).  Coordinate c is an angle of period 2π when bit c of circular_mask
+ *   is set (Pose2 0b100, Pose3 0b111000: a rotation-vector coordinate is treated as such an angle; the recombined rotation vector is
+ *   stored as computed): differences and outputs are wrapped.  Lines without a task keep J; pass-through coordinates of a partial row
+ *   are never read.  Every (v, c) may appear in at most one task; coordinates and rows are trusted like the CSR of rome_product_dev.
+ *   dim 2, 3 or 6; N <= ROME_MAX_PARTICLES_PRODUCT (512) at every dim; T = 0 is a no-op; prop and bel must not overlap. */
+int rome_product_partial_dev(rome_ctx*, const rome_opts*, int32_t dim, int32_t V, int32_t T, const int32_t* task_var,
+                             const int32_t* task_coord, const int32_t* task_ptr, const int32_t* task_rows, const int32_t* task_joint,
+                             const double* prop, const double* prop_bw, const double* joint_bw, uint32_t circular_mask, double* bel);
+/* host pointers (blocks in opts->layout); n_prop_rows = rows of prop / prop_bw */
+int rome_product_partial(rome_ctx*, const rome_opts*, int32_t dim, int32_t V, int32_t T, const int32_t* task_var,
+                         const int32_t* task_coord, const int32_t* task_ptr, const int32_t* task_rows, const int32_t* task_joint,
+                         const double* prop, const double* prop_bw, const double* joint_bw, uint32_t circular_mask, double* bel,
+                         int32_t n_prop_rows);
 
 /* thin device-memory helpers for callers without their own HIP runtime binding (e.g. the Julia shim) */
 int rome_dev_alloc(rome_ctx*, uint64_t bytes, void** out);

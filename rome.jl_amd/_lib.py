@@ -134,6 +134,9 @@ SIGNATURES = {
     "rome_scatter_plan_destroy": (None, [C.c_void_p]),
     "rome_product_gibbs_dev": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_uint32, C.c_int32, C.c_int32]),
+    "rome_product_partial_dev": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "rome_product_partial": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, C.c_int32, _PI, _PI, _PI, _PI, _PI, _PD, _PD, _PD, C.c_uint32, _PD, C.c_int32]),
     "rome_dev_alloc": (C.c_int, [_CTX, C.c_uint64, C.POINTER(C.c_void_p)]),
     "rome_dev_free": (C.c_int, [_CTX, C.c_void_p]),
     "rome_dev_upload": (C.c_int, [_CTX, C.c_void_p, C.c_void_p, C.c_uint64]),

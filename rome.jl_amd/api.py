@@ -258,6 +258,40 @@ def manifoldProduct(proposals, circular_mask=None, bandwidths=None, Niter=1, opt
     return out[0].cpu().numpy()
 
 
+def product_partial(opts, dim, tasks, prop, bel, prop_bw=None, joint_bw=None, circular_mask=None, ctx=None):
+    """Stage 2 of the partial-aware product on host arrays, via rome_product_partial.  tasks: the dict of
+    device.partial_tasks (task_var, task_coord, task_ptr, task_rows, task_joint); prop (rows, dim, N) the proposals; bel (V, dim, N)
+    the stage-1 result J; prop_bw (rows, dim) / joint_bw (V, dim) kernel bandwidths or None = Silverman's rule; circular_mask: bit c
+    set = coordinate c is an angle (default 0b100 for dim 3, 0b111000 for dim 6).  -> the new bel (V, dim, N): every task's line
+    replaced by the 1-D product of its densities, every other line J's, bit for bit.  The tables are validated here: the library
+    trusts them."""
+    prop, bel = _d(prop), _d(bel).copy()
+    (n_rows, V), N = (prop.shape[0], bel.shape[0]), opts.n_particles
+    if prop.shape[1:] != (dim, N) or bel.shape[1:] != (dim, N):
+        raise ValueError("product_partial: prop / bel must be (rows, %d, %d) / (V, %d, %d), got %s / %s" % (dim, N, dim, N, prop.shape, bel.shape))
+    tv, tc, tp, tr, tj = (np.ascontiguousarray(tasks[k], dtype=np.int32) for k in ("task_var", "task_coord", "task_ptr", "task_rows", "task_joint"))
+    T = len(tv)
+    if not (len(tc) == T and len(tj) == T and len(tp) == T + 1):
+        raise ValueError("product_partial: task tables of different lengths")
+    if T:
+        if tp[0] != 0 or (np.diff(tp) < 1).any() or tp[-1] != len(tr):
+            raise ValueError("product_partial: task_ptr must start at 0, give every task at least one row and end at len(task_rows)")
+        if tv.min() < 0 or tv.max() >= V or tc.min() < 0 or tc.max() >= dim or tr.min() < 0 or tr.max() >= n_rows:
+            raise ValueError("product_partial: a task names a variable, coordinate or row outside the arrays")
+        if len(set(zip(tv.tolist(), tc.tolist()))) != T:
+            raise ValueError("product_partial: a (variable, coordinate) line has more than one task")
+    if circular_mask is None:
+        circular_mask = 0b100 if dim == 3 else (0b111000 if dim == 6 else 0)
+    pbw = None if prop_bw is None else _d(prop_bw, (n_rows, dim))
+    jbw = None if joint_bw is None else _d(joint_bw, (V, dim))
+    one = lambda a: a if len(a) else np.zeros(1, np.int32)
+    tv, tc, tr, tj = one(tv), one(tc), one(tr), one(tj)
+    ctx = ctx or default_context()
+    _lib.check(_lib.load().rome_product_partial(ctx.handle, C.byref(opts), int(dim), V, T, _pi(tv), _pi(tc), _pi(tp), _pi(tr), _pi(tj), _p(prop),
+                                                _p(pbw), _p(jbw), int(circular_mask), _p(bel), n_rows), ctx.handle)
+    return bel
+
+
 def kde_max(bel, bw=None, grid_points=0, ctx=None):
     """bel (V, dim, N) host array -> (V, dim) max-density coordinates as IIF's getKDEMax computes them (PPE `max`), via rome_kde_max.
     bw (V, dim): kernel bandwidths; None selects them with kde_bandwidth (what `manikde!` would have stored)."""

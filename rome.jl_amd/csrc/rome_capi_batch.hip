@@ -175,6 +175,66 @@ int rome_product_gibbs_dev(rome_ctx* c, const rome_opts* o, int32_t dim, int32_t
   return ROME_OK;
 }
 
+/* ---- partial-aware product, stage 2 ---- */
+static int check_product_partial(rome_ctx* c, const rome_opts* o, int32_t dim, int32_t V, int32_t T, const int32_t* task_var,
+                                 const int32_t* task_coord, const int32_t* task_ptr, const int32_t* task_rows, const int32_t* task_joint,
+                                 const double* prop, double* bel) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || V < 0 || T < 0 || (dim != 2 && dim != 3 && dim != 6)) return ROME_ERR_INVALID_ARG;
+  if (T > 0 && (!task_var || !task_coord || !task_ptr || !task_rows || !task_joint || !prop || !bel)) return ROME_ERR_INVALID_ARG;
+  if (o->n_particles > ROME_MAX_PARTICLES_PRODUCT) return ROME_ERR_UNSUPPORTED_N;   /* stage 2 is 1-D: 512 at every dim */
+  return ROME_OK;
+}
+int rome_product_partial_dev(rome_ctx* c, const rome_opts* o, int32_t dim, int32_t V, int32_t T, const int32_t* task_var,
+                             const int32_t* task_coord, const int32_t* task_ptr, const int32_t* task_rows, const int32_t* task_joint,
+                             const double* prop, const double* prop_bw, const double* joint_bw, uint32_t circular_mask, double* bel) {
+  int rc = check_product_partial(c, o, dim, V, T, task_var, task_coord, task_ptr, task_rows, task_joint, prop, bel); if (rc) return rc;
+  if (T == 0) return ROME_OK;
+  ROME_BIND(c);
+  ROME_HIP(c, launch_product_partial(dim, T, o->n_particles, task_var, task_coord, task_ptr, task_rows, task_joint, prop, prop_bw, joint_bw,
+                                     circular_mask, bel, o->seed, o->stream_offset, c->stream));
+  return ROME_OK;
+}
+int rome_product_partial(rome_ctx* c, const rome_opts* o, int32_t dim, int32_t V, int32_t T, const int32_t* task_var,
+                         const int32_t* task_coord, const int32_t* task_ptr, const int32_t* task_rows, const int32_t* task_joint,
+                         const double* prop, const double* prop_bw, const double* joint_bw, uint32_t circular_mask, double* bel,
+                         int32_t n_prop_rows) {
+  int rc = check_product_partial(c, o, dim, V, T, task_var, task_coord, task_ptr, task_rows, task_joint, prop, bel); if (rc) return rc;
+  if (n_prop_rows < 0 || (T > 0 && (V < 1 || n_prop_rows < 1))) return ROME_ERR_INVALID_ARG;
+  if (T == 0) return ROME_OK;
+  ROME_HIP(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int N = o->n_particles;
+  const size_t nt = 4ull * T, nr = 4ull * (size_t)(task_ptr[T] > 0 ? task_ptr[T] : 0);
+  void *d_prop, *d_bel, *d_pbw = nullptr, *d_jbw = nullptr, *d_var, *d_coord, *d_ptr, *d_rows, *d_joint;
+  if ((rc = ensure(c, 0, 8ull * n_prop_rows * dim * N, &d_prop))) return rc;
+  if ((rc = ensure(c, 1, 8ull * V * dim * N, &d_bel))) return rc;
+  if ((rc = ensure(c, 4, nt, &d_var))) return rc;
+  if ((rc = ensure(c, 5, nt, &d_coord))) return rc;
+  if ((rc = ensure(c, 6, nt + 4, &d_ptr))) return rc;
+  if ((rc = ensure(c, 7, nr, &d_rows))) return rc;
+  if ((rc = ensure(c, 8, nt, &d_joint))) return rc;
+  if ((rc = stage_blocks(c, o->layout, n_prop_rows, dim, N, prop, (double*)d_prop))) return rc;
+  if ((rc = stage_blocks(c, o->layout, V, dim, N, bel, (double*)d_bel))) return rc;
+  if (prop_bw) {
+    if ((rc = ensure(c, 2, 8ull * n_prop_rows * dim, &d_pbw))) return rc;
+    ROME_HIP(c, hipMemcpyAsync(d_pbw, prop_bw, 8ull * n_prop_rows * dim, hipMemcpyHostToDevice, s));
+  }
+  if (joint_bw) {
+    if ((rc = ensure(c, 3, 8ull * V * dim, &d_jbw))) return rc;
+    ROME_HIP(c, hipMemcpyAsync(d_jbw, joint_bw, 8ull * V * dim, hipMemcpyHostToDevice, s));
+  }
+  ROME_HIP(c, hipMemcpyAsync(d_var, task_var, nt, hipMemcpyHostToDevice, s));
+  ROME_HIP(c, hipMemcpyAsync(d_coord, task_coord, nt, hipMemcpyHostToDevice, s));
+  ROME_HIP(c, hipMemcpyAsync(d_ptr, task_ptr, nt + 4, hipMemcpyHostToDevice, s));
+  if (nr) ROME_HIP(c, hipMemcpyAsync(d_rows, task_rows, nr, hipMemcpyHostToDevice, s));
+  ROME_HIP(c, hipMemcpyAsync(d_joint, task_joint, nt, hipMemcpyHostToDevice, s));
+  ROME_HIP(c, launch_product_partial(dim, T, N, (const int32_t*)d_var, (const int32_t*)d_coord, (const int32_t*)d_ptr, (const int32_t*)d_rows,
+                                     (const int32_t*)d_joint, (const double*)d_prop, (const double*)d_pbw, (const double*)d_jbw,
+                                     circular_mask, (double*)d_bel, o->seed, o->stream_offset, s));
+  return fetch_blocks(c, o->layout, V, dim, N, (const double*)d_bel, bel);   // (synchronises)
+}
+
 /* ---- device memory helpers ---- */
 int rome_dev_alloc(rome_ctx* c, uint64_t bytes, void** out) {
   if (!c || !out) return ROME_ERR_INVALID_ARG;

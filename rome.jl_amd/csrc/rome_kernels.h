@@ -85,6 +85,13 @@ hipError_t launch_product(int dim, int V, int N, const int32_t* prop_ptr, const 
                           const double* prop_bw, const double* bel_in, double* bel_out, double c_n, uint64_t seed,
                           uint64_t stream_offset, hipStream_t s);
 
+// stage 2 of the partial-aware product (rome_product_partial.hip): T tasks (variable, coordinate), one wave each; task t multiplies the
+// 1-D marginals `task_coord[t]` of rows task_rows[task_ptr[t] .. task_ptr[t+1]) of prop and (task_joint[t]) of bel[task_var[t]] itself;
+// bel is updated in place (prop and bel must not overlap); prop_bw / joint_bw nullable (Silverman in-kernel); N <= 512
+hipError_t launch_product_partial(int dim, int T, int N, const int32_t* task_var, const int32_t* task_coord, const int32_t* task_ptr,
+                                  const int32_t* task_rows, const int32_t* task_joint, const double* prop, const double* prop_bw,
+                                  const double* joint_bw, uint32_t circ, double* bel, uint64_t seed, uint64_t stream_offset, hipStream_t s);
+
 size_t gibbs_workspace_bytes(int dim, int n_rows, int V, int N);   // (N: 128-slot trees up to N = 128, 256-slot trees above)
 // GibbsPlace (optional): where the V variables of a launch live and what they draw -- var_block[v] = block of bel_in / bel_out
 // (nullptr: v; bel_in == bel_out is allowed then: a product only reads its own variable's block), var_stream[v] = Philox stream id

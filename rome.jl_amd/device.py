@@ -9,9 +9,41 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .factors import Pose2, Point2, Pose3
+from .factors import Pose2, Point2, Pose3, Pose2Point2Range, Pose3Pose3XYYaw, PriorPose3ZRP, partial_coverage
 from .graph import PackedGraph
 from .api import cholesky_lower
+
+
+def partial_tasks(ptr, rows, row_cover, dim):
+    """The tables of the partial-aware product of one variable type, on the host.  ptr [V+1] / rows: the CSR variable ->
+    proposal rows; row_cover[r]: the 0-based coordinates row r solves, or None for a full row.  -> dict of int32 arrays:
+    full_ptr / full_rows, the CSR of the full rows alone (stage 1), and one task per (variable, covered coordinate) in (v, c) order:
+    task_var, task_coord, task_ptr [T+1] / task_rows (the partial rows covering c, in CSR order), task_joint (1: v has full rows, whose
+    product enters as the last density)."""
+    ptr, rows = np.asarray(ptr, dtype=np.int64), np.asarray(rows, dtype=np.int64)
+    if len(rows) and (rows.min() < 0 or rows.max() >= len(row_cover)):
+        raise ValueError("partial_tasks: proposal row %d is outside the %d rows of row_cover" % (rows.min() if rows.min() < 0 else rows.max(), len(row_cover)))
+    for r, m in enumerate(row_cover):
+        if m is not None and (len(m) == 0 or min(m) < 0 or max(m) >= dim):
+            raise ValueError("partial_tasks: row %d covers coordinates %s of a %d-dimensional variable" % (r, tuple(m), dim))
+    i32 = lambda a: np.asarray(a, dtype=np.int32)
+    if all(m is None for m in row_cover):   # (the usual graph: nothing to walk)
+        none = i32([])
+        return dict(full_ptr=i32(ptr), full_rows=i32(rows), task_var=none, task_coord=none, task_ptr=i32([0]), task_rows=none, task_joint=none)
+    full_ptr, full_rows, task_var, task_coord, task_ptr, task_rows, task_joint = [0], [], [], [], [0], [], []
+    for v in range(len(ptr) - 1):
+        rv = [int(r) for r in rows[ptr[v]:ptr[v + 1]]]
+        full = [r for r in rv if row_cover[r] is None]
+        full_rows += full
+        full_ptr.append(len(full_rows))
+        for c in range(dim):
+            cov = [r for r in rv if row_cover[r] is not None and c in row_cover[r]]
+            if cov:
+                task_var.append(v); task_coord.append(c); task_joint.append(1 if full else 0)
+                task_rows += cov
+                task_ptr.append(len(task_rows))
+    return dict(full_ptr=i32(full_ptr), full_rows=i32(full_rows), task_var=i32(task_var), task_coord=i32(task_coord),
+                task_ptr=i32(task_ptr), task_rows=i32(task_rows), task_joint=i32(task_joint))
 
 
 def _require_torch_cuda():
@@ -64,11 +96,12 @@ class DeviceGraph:
         self.n_prop = {Pose2: 0, Point2: 0, Pose3: 0}
         dev = lambda a, dt: a if a is None or torch.is_tensor(a) else t(a, dt)
 
-        def add(name, entry, vt_fixed, vt_target, dir_all, stream, targets, mu, L, rows4=None, alt=None, w=None, nh=None, in_step=True):
-            """alt / w / nh stay None unless the graph has them: the library picks its kernel from which pointers are null"""
+        def add(name, entry, vt_fixed, vt_target, dir_all, stream, targets, mu, L, rows4=None, alt=None, w=None, nh=None, in_step=True, partial=None):
+            """alt / w / nh stay None unless the graph has them: the library picks its kernel from which pointers are null.
+            partial: the 0-based coordinates of the target that the family's proposals solve (factors.partial_coverage), None = all"""
             rec = dict(name=name, entry=entry, fn=entry if plan_only else getattr(self._lib, entry), vt_fixed=vt_fixed, vt_target=vt_target,
                        dir_all=dir_all, stream=stream, n=len(targets), targets_h=np.asarray(targets, dtype=np.int32), mu=mu, L=L,
-                       rows4=dev(rows4, i32), alt=dev(alt, i32), w=dev(w, f64), nh=dev(nh, f64), prop_lo=None)
+                       rows4=dev(rows4, i32), alt=dev(alt, i32), w=dev(w, f64), nh=dev(nh, f64), prop_lo=None, partial=partial)
             if in_step:   # (the PriorPose2 / PriorPose3 samplers are launchable but own no rows: their factors are rows of p2p2 / p3p3)
                 rec["prop_lo"] = self.n_prop[vt_target]
                 self.n_prop[vt_target] += rec["n"]
@@ -151,7 +184,8 @@ class DeviceGraph:
             mu, sigma, nh = t(rp["mu"], f64), t(rp["sigma"], f64), dev(nh_or_none(rp["nh"]), f64)
             for name, d, stream, vf, vt, fx, tg in (("pprng1", 1, self.STREAM_PPRNG1, Point2, Pose2, rp["point"], rp["pose"]),
                                                     ("pprng0", 0, self.STREAM_PPRNG0, Pose2, Point2, rp["pose"], rp["point"])):
-                add(name, "rome_conv_pose2point2range_dev", vf, vt, d, stream, tg, mu, sigma, rows4=np.stack([fac, col(d, F), fx, tg], axis=1), nh=nh)
+                add(name, "rome_conv_pose2point2range_dev", vf, vt, d, stream, tg, mu, sigma, rows4=np.stack([fac, col(d, F), fx, tg], axis=1), nh=nh,
+                    partial=partial_coverage(Pose2Point2Range, 1 - d))   # (dir 1 solves the pose, variable 0 of the factor)
             self.tab["pprng"] = dict(F=F)
         # bearing-only factors (Bearing2D.jl): behind the range families; L = the [F][1] bearing sigmas
         pb = getattr(pk, "pbear", None)
@@ -172,14 +206,16 @@ class DeviceGraph:
         if xy is not None and xy["F"]:
             factor, dr, fixed, target = PackedGraph.conv_table(xy)
             add("p3xyy", "rome_conv_pose3pose3xyyaw_dev", Pose3, Pose3, 0, self.STREAM_P3XYY, target, t(xy["mu"], f64), t(cholesky_lower(xy["cov"]), f64),
-                rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(xy["nh"], 2)))
+                rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(xy["nh"], 2)),
+                partial=partial_coverage(Pose3Pose3XYYaw, 0))   # (the same coordinates towards either pose)
             self.tab["p3xyy"] = dict(F=xy["F"], C=2 * xy["F"])
         zr = getattr(pk, "zrp3", None)
         if zr is not None and zr["F"]:
             F = zr["F"]
             L = np.concatenate([zr["sigma_z"].reshape(F, 1), cholesky_lower(zr["cov_rp"]).reshape(F, 3)], axis=1)
             add("zrp3", "rome_conv_priorpose3zrp_dev", Pose3, Pose3, 0, self.STREAM_ZRP3, zr["var"], t(zr["mu"], f64), t(L, f64),
-                rows4=np.stack([np.arange(F, dtype=np.int32), col(0, F), zr["var"], zr["var"]], axis=1), nh=nh_or_none(zr["nh"]))
+                rows4=np.stack([np.arange(F, dtype=np.int32), col(0, F), zr["var"], zr["var"]], axis=1), nh=nh_or_none(zr["nh"]),
+                partial=partial_coverage(PriorPose3ZRP, 0))
             self.tab["zrp3"] = dict(F=F)
 
         # one conv_step: the fused Pose2 / Point2 call for its three records when all three have rows, then every other record that
@@ -197,15 +233,17 @@ class DeviceGraph:
         self.bel_next = {vt: torch.zeros_like(self.bel[vt]) for vt in (Pose2, Point2, Pose3)}
         self._prop_targets = {vt: np.concatenate([np.zeros(0, np.int32)] + [r["targets_h"] for r in step if r["vt_target"] is vt])
                               for vt in (Pose2, Point2, Pose3)}
+        self._prop_cover = {vt: [r["partial"] for r in step if r["vt_target"] is vt for _ in range(r["n"])] for vt in (Pose2, Point2, Pose3)}
         self.frozen = set()
         self._build_csr()
 
     def _build_csr(self):
-        """variable -> proposal rows; frozen (marginalized) variables get no rows, so the product keeps their belief."""
+        """variable -> proposal rows; frozen (marginalized) variables get no rows, so the product keeps their belief.  csr_full / tasks:
+        the same for the partial-aware product (partial_tasks): the full rows alone, and the per-coordinate tasks of the partial ones."""
         pk = self.packed
         t = lambda a, dt: self.torch.as_tensor(np.ascontiguousarray(a), dtype=dt, device=self.device)
         i32 = self.torch.int32
-        self.csr = {}
+        self.csr, self.csr_full, self.tasks = {}, {}, {}
         for vt in (Pose2, Point2, Pose3):
             tg = np.asarray(self._prop_targets[vt], dtype=np.int64)
             nv = len(pk.labels[vt])
@@ -221,6 +259,15 @@ class DeviceGraph:
             ptr = np.cumsum(ptr).astype(np.int32)
             self.csr[vt] = dict(ptr=t(ptr, i32), rows=t(order if len(order) else np.zeros(1, np.int32), i32),
                                 ptr_h=ptr, rows_h=order)
+            pt = partial_tasks(ptr, order, self._prop_cover[vt], vt.dim)
+            T = len(pt["task_var"])
+            if T == 0:   # no partial rows: stage 1 IS the product of today, on the same tables
+                self.csr_full[vt], self.tasks[vt] = self.csr[vt], dict(T=0, any_joint=False, host=pt)
+                continue
+            one = lambda a: t(a if len(a) else np.zeros(1, np.int32), i32)
+            self.csr_full[vt] = dict(ptr=t(pt["full_ptr"], i32), rows=one(pt["full_rows"]), ptr_h=pt["full_ptr"], rows_h=pt["full_rows"])
+            self.tasks[vt] = dict(T=T, any_joint=bool(pt["task_joint"].any()), host=pt,
+                                  **{k: one(pt["task_" + k]) for k in ("var", "coord", "ptr", "rows", "joint")})
 
     def set_frozen(self, labels):
         """Fixed-lag operation (IIF `fifoFreeze!` / isMarginalized): the beliefs of `labels` are no longer updated by product_step /
@@ -339,6 +386,10 @@ class DeviceGraph:
 
     STREAM_P3XYY, STREAM_ZRP3 = 13 << 28, 14 << 28   # partial Pose3 factors (Pose3Pose3XYYaw both directions, PriorPose3ZRP)
 
+    # stage 2 of the partial-aware product (task (v, c) draws base + v·dim + c): Pose2, Pose3.  15 << 28 is the last 28-bit slot below
+    # the sweep field (sweep << 32), so the two bases share it, 2^27 streams each
+    STREAM_PARTIAL2, STREAM_PARTIAL3 = 15 << 28, (15 << 28) + (1 << 27)
+
     def has_partial3(self):
         """does the graph hold partial Pose3 factors (served by conv_step / solve only: not by the multi-rank drivers)"""
         return "p3xyy" in self.tab or "zrp3" in self.tab
@@ -375,7 +426,7 @@ class DeviceGraph:
                      fused=k < len(self._fused))
                 for k, r in enumerate(self._fused + self._unfused)]
 
-    def product_step(self, opts, sweep=0, bandwidth="silverman", product="importance", gibbs_iters=1):
+    def product_step(self, opts, sweep=0, bandwidth="silverman", product="importance", gibbs_iters=1, partial_product="off"):
         """bel <- product of the proposals targeting each variable (Jacobi update: computed into bel_next, copied back in place
         so that launch plans holding the belief pointers stay valid).
         product:   "gibbs" = the reference's algorithm, ⚠AMP manifoldProduct / KDE.jl multiscale Gibbs sampling
@@ -383,7 +434,15 @@ class DeviceGraph:
                    "importance" = the round-1 importance-sampling stand-in (rome_product_bw_dev).
         bandwidth: "silverman" (in-kernel rule on the proposal spread; importance product only) or "lcv" (leave-one-out
                    likelihood bandwidths of every proposal by rome_kde_bandwidth_dev first -- what the reference's `manikde!`
-                   attaches to each convolution result)."""
+                   attaches to each convolution result).
+        partial_product: "off" = every proposal row enters the product above as a full-dimensional density (the pass-through coordinates
+                   of a partial factor's proposal then count as evidence for the current belief); "coordinate" = IIF's rule (DESIGN.md
+                   §12d): the product above over the FULL rows only, then rome_product_partial_dev -- every coordinate that a partial
+                   row covers becomes the 1-D importance product of the marginals covering it (and of the joint result, when the
+                   variable has full rows); under "lcv" / "gibbs" on the manikde! bandwidths of those marginals.  A variable type
+                   without partial rows launches the same under either setting."""
+        if partial_product not in ("off", "coordinate"):
+            raise ValueError("partial_product must be 'off' or 'coordinate'")
         if bandwidth not in ("silverman", "lcv"):
             raise ValueError("bandwidth must be 'silverman' or 'lcv'")
         if product not in ("importance", "gibbs"):
@@ -395,7 +454,8 @@ class DeviceGraph:
             if V == 0:
                 continue
             o = self._opts_at(opts, base + off)
-            c = self.csr[vt]
+            tk = self.tasks[vt] if partial_product == "coordinate" else None
+            c = self.csr_full[vt] if tk is not None and tk["T"] else self.csr[vt]
             bw_ptr = None
             rows = self.n_prop[vt]
             gibbs = product == "gibbs"
@@ -417,15 +477,27 @@ class DeviceGraph:
                 _lib.check(self._lib.rome_product_bw_dev(self.ctx.handle, C.byref(o), dim, V, c["ptr"].data_ptr(), c["rows"].data_ptr(),
                                                          self.prop[vt].data_ptr(), bw_ptr, self.bel[vt].data_ptr(),
                                                          self.bel_next[vt].data_ptr()), self.ctx.handle)
+            if tk is not None and tk["T"]:
+                jbw_ptr = None
+                if bw_ptr is not None and tk["any_joint"]:   # the joint result enters as a density of its own: its manikde! bandwidths
+                    jbw = self.torch.empty((V, dim), dtype=self.torch.float64, device=self.device)
+                    _lib.check(self._lib.rome_kde_bandwidth_dev(self.ctx.handle, dim, V, self.N, self.bel_next[vt].data_ptr(), circ, 0.0, 0.0,
+                                                                jbw.data_ptr()), self.ctx.handle)
+                    jbw_ptr = jbw.data_ptr()
+                op = self._opts_at(opts, base + (self.STREAM_PARTIAL2 if vt is Pose2 else self.STREAM_PARTIAL3))
+                _lib.check(self._lib.rome_product_partial_dev(self.ctx.handle, C.byref(op), dim, V, tk["T"], tk["var"].data_ptr(),
+                                                              tk["coord"].data_ptr(), tk["ptr"].data_ptr(), tk["rows"].data_ptr(),
+                                                              tk["joint"].data_ptr(), self.prop[vt].data_ptr(), bw_ptr, jbw_ptr, circ,
+                                                              self.bel_next[vt].data_ptr()), self.ctx.handle)
             self.bel[vt].copy_(self.bel_next[vt])
 
-    def solve(self, opts, n_sweeps=10, bandwidth="silverman", product="importance", gibbs_iters=1):
+    def solve(self, opts, n_sweeps=10, bandwidth="silverman", product="importance", gibbs_iters=1, partial_product="off"):
         """n_sweeps x (convolution sweep, product): whole-graph nonparametric inference, a Jacobi schedule in place of the
         clique-by-clique Gibbs of `solveTree!` (no Bayes tree)."""
         self.check_particle_limits(bandwidth, product)
         for s in range(n_sweeps):
             self.conv_step(opts, s)
-            self.product_step(opts, s, bandwidth, product, gibbs_iters)
+            self.product_step(opts, s, bandwidth, product, gibbs_iters, partial_product)
 
     # ---- row-range forms of the two `next` stages, as the sharded drivers call them (rome_jl_amd.distributed) ----
     def kde_bandwidth_rows(self, dim, n_rows, prop, circ, bw_out):

@@ -243,6 +243,18 @@ RANGE_FACTORS = (Point2Point2Range, Pose2Point2Range)
 PARTIAL3_FACTORS = (Pose3Pose3XYYaw, PriorPose3ZRP)
 
 
+def partial_coverage(factor, position):
+    """0-based coordinates of the variable at `position` of `factor` (a factor or a factor class) that its proposal towards that
+    variable solves, or None when it solves all of them.  From the `partial` class attributes (1-based, as in the reference); the
+    `partial` of Pose2Point2Range is on the pose alone (Range2D.jl:44): its proposal towards the landmark is full."""
+    cls = factor if isinstance(factor, type) else type(factor)
+    p = getattr(cls, "partial", None)
+    if p is None or (cls is Pose2Point2Range and position != 0):
+        return None
+    cover = tuple(int(k) - 1 for k in p)
+    return None if len(cover) == cls.variable_types[position].dim else cover
+
+
 def refuse_range(factors, where):
     """TypeError naming the first range-only factor in `factors` (paths that do not serve them yet)."""
     for f in factors:

@@ -683,6 +683,29 @@ function kde_max(X::Matrix{Float64}, bw::Vector{Float64} = kde_bandwidths(X))
   m
 end
 
+# ---- stage 2 of the partial-aware product (rome_product_partial; include/rome_mi355.h, DESIGN.md §12d) -----------
+# prop: N x dim x rows, bel: N x dim x V (exactly the C side's SoA blocks [.][dim][N]); bel holds the product of the full proposals on
+# entry and is updated in place.  The task tables are 0-based, as the header defines them: task t rewrites coordinate task_coord[t] of
+# variable task_var[t] from the marginals of rows task_rows[task_ptr[t]+1 : task_ptr[t+1]] of prop and (task_joint[t] != 0) of bel itself.
+# prop_bw (dim x rows) / joint_bw (dim x V): kernel bandwidths, or nothing = Silverman's rule.
+function product_partial!(bel::Array{Float64,3}, prop::Array{Float64,3}, task_var::Vector{Int32}, task_coord::Vector{Int32},
+                          task_ptr::Vector{Int32}, task_rows::Vector{Int32}, task_joint::Vector{Int32};
+                          prop_bw::Union{Nothing,Matrix{Float64}}=nothing, joint_bw::Union{Nothing,Matrix{Float64}}=nothing,
+                          circular_mask::Integer = size(bel, 2) == 3 ? 0b100 : (size(bel, 2) == 6 ? 0b111000 : 0),
+                          seed::Integer=rand(UInt64), stream_offset::Integer=0)
+  N, d, V = size(bel)
+  o = Ref{RomeOpts}()
+  ccall((:rome_opts_default, LIB), Cvoid, (Ref{RomeOpts}, Int32), o, 1)
+  q = o[]
+  o[] = RomeOpts(N, q.solver, q.max_iters, q.inflate_cycles, q.tol, q.inflation, seed, stream_offset, 0 #=SoA=#, 0, q.spread_nh, 0.0)
+  check(ccall((:rome_product_partial, LIB), Cint,
+    (Ptr{Cvoid}, Ref{RomeOpts}, Int32, Int32, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+     Ptr{Float64}, UInt32, Ptr{Float64}, Int32),
+    ctx().h, o, d, V, length(task_var), task_var, task_coord, task_ptr, task_rows, task_joint, prop,
+    prop_bw === nothing ? C_NULL : prop_bw, joint_bw === nothing ? C_NULL : joint_bw, UInt32(circular_mask), bel, size(prop, 3)))
+  bel
+end
+
 # ---- residual KATs through the library (mirrors calcFactorResidualTemporary) ---------------------------
 function residual_pose2pose2(z::AbstractMatrix, p::AbstractMatrix, q::AbstractMatrix)   # 3 x n each
   r = similar(z)

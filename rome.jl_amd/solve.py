@@ -65,13 +65,14 @@ def initAllOrdered(fg, seed=1, ctx=None, sweeps=0, kind="colour", solver=None):
 
 
 def solveGraph(fg, n_sweeps=10, seed=0x524F4D45, init="graph", bandwidth="silverman", frozen=None, opts=None, product="importance",
-               gibbs_iters=1):
+               gibbs_iters=1, partial_product="off"):
     """initialise -> device sweeps -> download -> setPPE.  init: "graph" (initAll for whatever has no belief yet), "parametric"
     (beliefs around solveGraphParametric's solution, like IIF's initParametricFrom!), "ordered" (initAllOrdered: IIF's initAll! order with
     the product of ALL usable factors per variable, device-resident) or None (beliefs must exist).
     product: "gibbs" = the reference's `manifoldProduct` (multiscale Gibbs product on `manikde!` bandwidths) per variable,
     "importance" = the round-1 stand-in; gibbs_iters = AMP's `Niter` (1 at the reference's default; the relative weight of the modes of
-    a multimodal product needs ~3, tests/test_gpu_gibbs.py).  Returns the DeviceGraph (beliefs stay resident for further sweeps)."""
+    a multimodal product needs ~3, tests/test_gpu_gibbs.py).  partial_product: "off", or "coordinate" = the partial-aware product
+    (DeviceGraph.product_step; what graphs with Pose3Pose3XYYaw / PriorPose3ZRP / Pose2Point2Range factors need).  Returns the DeviceGraph (beliefs stay resident for further sweeps)."""
     from .api import make_opts
     from .canonical import setPPE
     from .device import DeviceGraph
@@ -92,7 +93,7 @@ def solveGraph(fg, n_sweeps=10, seed=0x524F4D45, init="graph", bandwidth="silver
     if frozen:
         dg.set_frozen(frozen)
     dg.solve(opts if opts is not None else make_opts(N=fg.N, seed=seed), n_sweeps=n_sweeps, bandwidth=bandwidth, product=product,
-             gibbs_iters=gibbs_iters)
+             gibbs_iters=gibbs_iters, partial_product=partial_product)
     dg.download_beliefs(fg)
     setPPE(fg)
     return dg
