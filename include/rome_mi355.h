@@ -12,6 +12,7 @@
  *     Pose2Point2Bearing         src/factors/Bearing2D.jl:10-32
  *     Pose3Pose3XYYaw            src/factors/PartialPose3.jl:101-136  (partial = (1, 2, 6))
  *     PriorPose3ZRP              src/factors/PartialPose3.jl:12-46    (partial = (3, 4, 5))
+ *     Pose3Pose3Rotation         src/factors/PartialPose3.jl:204-227  (partial = (4, 5, 6))
  * (paths relative to the RoME.jl v0.24.6 checkout).  Each entry point names the reference
  * interface it replaces.  Plain pointers and sizes only; no exceptions cross the ABI; the library
  * never retains caller pointers past a call.  There is NO CPU fallback: without a HIP device
@@ -44,7 +45,7 @@
 extern "C" {
 #endif
 
-#define ROME_MI355_VERSION 122 /* 0.1.22 (appended since, the number unchanged: the partial Pose3 entries rome_*_pose3pose3xyyaw* / rome_conv_priorpose3zrp*;ROME_BLOCKOP_COMPOSE on Pose3 blocks, ROME_BLOCKOP_ANCHOR_MEAN, p3p3_meas at the end of rome_clique_host -- solveTree as variable elimination on Pose3 graphs): ROME_BLOCKOP_COMPOSE / MIX, rome_blockop_plan_create_ex (round 6: solveTree as variable elimination in relative-factor algebra); rome_ctx_set_stream orders streams by event.  0.1.21: store-resident messages (smsg_*) in rome_clique_upsolve_host (a tree level reads its children's separator beliefs from HBM); multihypo / nullhypo / stream-id columns in rome_clique_host; rome_store + rome_upsolve_plan
+#define ROME_MI355_VERSION 122 /* 0.1.22 (appended since, the number unchanged: the partial Pose3 entries rome_*_pose3pose3xyyaw* / rome_conv_priorpose3zrp* / rome_*_pose3pose3rotation*; ROME_BLOCKOP_COMPOSE on Pose3 blocks, ROME_BLOCKOP_ANCHOR_MEAN, p3p3_meas at the end of rome_clique_host -- solveTree as variable elimination on Pose3 graphs): ROME_BLOCKOP_COMPOSE / MIX, rome_blockop_plan_create_ex (round 6: solveTree as variable elimination in relative-factor algebra); rome_ctx_set_stream orders streams by event.  0.1.21: store-resident messages (smsg_*) in rome_clique_upsolve_host (a tree level reads its children's separator beliefs from HBM); multihypo / nullhypo / stream-id columns in rome_clique_host; rome_store + rome_upsolve_plan
                                  * (device-resident clique up-solves: beliefs stay in HBM across frontiers) */
 
 enum {
@@ -308,6 +309,31 @@ int rome_conv_pose3pose3xyyaw(rome_ctx*, const rome_opts*, int32_t C, const int3
                               double* target_inout /*C*N*6*/, int32_t* status);
 int rome_conv_priorpose3zrp(rome_ctx*, const rome_opts*, int32_t C, const double* mu /*C*3*/, const double* sigma_z /*C*/,
                             const double* cov_rp /*C*4*/, const double* noise /*C*N*3 or NULL*/, double* target_inout /*C*N*6*/);
+/* Pose3Pose3Rotation(Z) over [p, q], partial = (4, 5, 6) (:204-227), dz = dr = 3: the relative attitude.  z is a rotation
+ *   vector, the coordinates of a tangent of SO(3) (test/testPartialPose3.jl:539-542 feeds hat(M, ϵ, rpy)).  Residual (:212-227)
+ *     r = z − Log(R_pᵀ R_q),   Log the principal rotation vector, |Log| <= π;
+ *   the translations do not enter.  rome_residual_pose3pose3rotation: rows of coordinates; _pt: p, q as native points (n*12).
+ *   Convolution: the partial rule above with partial coordinates 3, 4, 5 (0-based): the spread over the whole variable, additive entropy
+ *   from u[3..5] of the d = 6 draw, the target's translation returned BIT FOR BIT.  dir[c] 0 solves q from p, 1 solves p from q (NULL:
+ *   all 0); mu [C][3], cov [C][9], z = μ + Lξ (the d = 3 normal rule of Pose3Pose3XYYaw); noise [C][N][3].  Root:
+ *     dir 0: R_q = R_p Exp(z);   dir 1: R_p = R_q Exp(−z);
+ *   the stored rotation coordinates are the principal rotation vector of the new rotation.  This is the zero of the functor whenever
+ *   |z| < π.  For |z| >= π the functor has no zero (z − Log(Exp z) is a whole turn about the axis): the closed form returns the same
+ *   rotation, and every status output that is computed (NEWTON with a status array, GAUSS_NEWTON, NELDER_MEAD) reports the functor, so
+ *   status is 1 there -- documented behaviour, not an error.  CLOSED_FORM writes zeros, as for every family.
+ *   CLOSED_FORM / NEWTON: the root above; the start points' ω is not read.  NEWTON with a status array: the functor at the returned
+ *     point, 0 iff max|r| <= tol.
+ *   GAUSS_NEWTON: from the start particle's own rotation; at every iterate the group difference e = Log(Exp(z)ᵀ R_pᵀ R_q) (dir 0; the
+ *     mirrored product Exp(z) R_qᵀ R_p for dir 1) updates the target by R <- R Exp(−e) (the residual rotation itself is the update, as in
+ *     the Pose3Pose3 Gauss-Newton) and the functor is tested; one pass, status 1 at max_iters.
+ *   NELDER_MEAD: nelder_mead<3> on Σr² over the target's (ω_x, ω_y, ω_z), inflate_cycles x {entropy, minimise}: the only solver that
+ *     cycles; the minimiser's coordinates are stored as they are.                                                                       */
+int rome_residual_pose3pose3rotation(rome_ctx*, int32_t n, const double* z /*n*3*/, const double* p /*n*6*/, const double* q /*n*6*/, double* r /*n*3*/);
+int rome_residual_pose3pose3rotation_pt(rome_ctx*, int32_t n, const double* z /*n*3*/, const double* p_pt /*n*12*/, const double* q_pt /*n*12*/, double* r /*n*3*/);
+int rome_conv_pose3pose3rotation(rome_ctx*, const rome_opts*, int32_t C, const int32_t* dir /*[C] or NULL*/,
+                                 const double* mu /*C*3*/, const double* cov /*C*9*/,
+                                 const double* fixed /*C*N*6*/, const double* noise /*C*N*3 or NULL*/,
+                                 double* target_inout /*C*N*6*/, int32_t* status);
 /* Prior "convolution" = N samples of the prior as points: IIF samplePoint on PriorPose2.Z / PriorPose3.Z
  * (src/factors/PriorPose2.jl:13-17, src/factors/Pose3D.jl:8-12).                                 */
 int rome_sample_priorpose2(rome_ctx*, const rome_opts*, int32_t C, const double* mu /*C*3*/, const double* cov /*C*9*/,
@@ -591,6 +617,9 @@ int rome_conv_pose2point2bearing_dev(rome_ctx*, const rome_opts*, const rome_con
  * 3, 4, 5 replaced), bel_fixed may be NULL; status, when given, receives zeros */
 int rome_conv_pose3pose3xyyaw_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 int rome_conv_priorpose3zrp_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
+/* pose3pose3rotation on device tables: the shape of pose3pose3xyyaw (mu [F][3], L = [F][6] packed Cholesky, the row direction from
+ * rows4 / dir / dir_all); no multihypo */
+int rome_conv_pose3pose3rotation_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 /* The whole convolution sweep of a Pose2 / Point2 graph (odometry + bearing-range sightings: MIT.g2o with landmarks, the beehive) in ONE
  * call: the Pose2Pose2 (+ PriorPose2 rows) table, the bearing-range -> pose table (dir_all = 1) and the bearing-range -> landmark table
  * (dir_all = 0); any of them may be NULL.  Philox stream of row r of family k = opts->stream_offset + family_stream_offset[k] + r
@@ -678,7 +707,7 @@ int rome_product_gibbs_dev(rome_ctx*, const rome_opts*, int32_t dim, int32_t V, 
                            const double* prop, const double* prop_bw, int32_t n_prop_rows, const double* bel_in, double* bel_out,
                            uint32_t circular_mask, int32_t gibbs_iters, int32_t max_proposals);
 /* rome_product_partial*: stage 2 of the partial-aware product -- what IIF does with the proposals of partial factors
- *   (Pose3Pose3XYYaw: coordinates {0, 1, 5}; PriorPose3ZRP: {2, 3, 4}; Pose2Point2Range towards the pose: {0, 1}; 0-based), whose
+ *   (Pose3Pose3XYYaw: coordinates {0, 1, 5}; PriorPose3ZRP: {2, 3, 4}; Pose3Pose3Rotation: {3, 4, 5}; Pose2Point2Range towards the pose: {0, 1}; 0-based), whose
  *   other coordinates only repeat the target's own particles and must not count as evidence.  Stage 1 is the caller's: one of the
  *   products above over the FULL proposal rows only, its result J left in bel [V][dim][N].  Here task t = (task_var[t], task_coord[t])
  *   rewrites ONE line bel[v][c][0..N) in place: the 1-D importance product (the dim = 1 case of rome_product_bw_dev's definition) of the

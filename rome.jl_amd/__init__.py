@@ -2,7 +2,7 @@
 
 Scope: ONE hot path of RoME.jl + IncrementalInference.jl -- the per-particle residual + root-find
 inside `approxConvBelief` for Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3 and the range-only
-Point2Point2Range / Pose2Point2Range, the bearing-only Pose2Point2Bearing and the partial Pose3 factors Pose3Pose3XYYaw / PriorPose3ZRP --
+Point2Point2Range / Pose2Point2Range, the bearing-only Pose2Point2Bearing and the partial Pose3 factors Pose3Pose3XYYaw / PriorPose3ZRP / Pose3Pose3Rotation --
 as hand-written HIP kernels in librome_mi355.so (C ABI: include/rome_mi355.h).  This package is the
 host-side mirror of the reference interface; it contains no compute and no CPU fallback.
 """
@@ -10,7 +10,7 @@ from . import _lib
 from ._lib import (Context, Opts, RomeError, SOLVER_CLOSED_FORM, SOLVER_NEWTON, SOLVER_NELDER_MEAD, SOLVER_GAUSS_NEWTON,
                    LAYOUT_SOA, LAYOUT_AOS, LAYOUT_AOS_POINTS, MAX_PARTICLES, MAX_PARTICLES_REGISTER)
 from .factors import (MvNormal, Normal, Uniform, Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange,
-                      Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP, getMeasurementParametric, getPoint, getCoordinates, pack_factor,
+                      Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP, Pose3Pose3Rotation, getMeasurementParametric, getPoint, getCoordinates, pack_factor,
                       unpack_factor)
 from .api import (linearize, belief_stats, kde_bandwidth, kde_max, manifoldProduct, product_partial, calcPPE, points_to_coords, coords_to_points, calcFactorResidualTemporary, make_opts, cholesky_lower, default_context,
                   residual_pose2pose2, residual_priorpose2, residual_pose2point2br, residual_pose2point2br_pt,
@@ -18,7 +18,8 @@ from .api import (linearize, belief_stats, kde_bandwidth, kde_max, manifoldProdu
                   conv_pose2pose2, conv_pose2point2br, conv_pose3pose3, sample_priorpose2, sample_priorpose3, sample_priorpoint2,
                   residual_point2point2range, residual_pose2point2range, conv_point2point2range, conv_pose2point2range,
                   residual_pose2point2bearing, residual_pose2point2bearing_pt, conv_pose2point2bearing,
-                  residual_pose3pose3xyyaw, residual_pose3pose3xyyaw_pt, conv_pose3pose3xyyaw, conv_priorpose3zrp)
+                  residual_pose3pose3xyyaw, residual_pose3pose3xyyaw_pt, conv_pose3pose3xyyaw, conv_priorpose3zrp,
+                  residual_pose3pose3rotation, residual_pose3pose3rotation_pt, conv_pose3pose3rotation)
 from .graph import (FactorGraph, initfg, fifoFreeze, isMarginalized, importG2o, parseG2oInstruction, loadG2o, synth_manhattan,
                     synth_manhattan_edges, synth_pose2_tables, synth_helix3d, synth_mit_br, add_synthetic_landmarks, dead_reckon_init_pose3, generateGraph_Circle, generateGraph_Hexagonal,
                     PackedGraph, dead_reckon_init)

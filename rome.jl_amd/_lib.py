@@ -92,6 +92,10 @@ SIGNATURES = {
     "rome_conv_priorpose3zrp": (C.c_int, [_CTX, _PO, C.c_int32, _PD, _PD, _PD, _PD, _PD]),
     "rome_conv_pose3pose3xyyaw_dev": (C.c_int, [_CTX, _PO, _PT]),
     "rome_conv_priorpose3zrp_dev": (C.c_int, [_CTX, _PO, _PT]),
+    "rome_residual_pose3pose3rotation": (C.c_int, [_CTX, C.c_int32, _PD, _PD, _PD, _PD]),
+    "rome_residual_pose3pose3rotation_pt": (C.c_int, [_CTX, C.c_int32, _PD, _PD, _PD, _PD]),
+    "rome_conv_pose3pose3rotation": (C.c_int, [_CTX, _PO, C.c_int32, _PI, _PD, _PD, _PD, _PD, _PD, _PI]),
+    "rome_conv_pose3pose3rotation_dev": (C.c_int, [_CTX, _PO, _PT]),
     "rome_conv_pose2pose2_mh":(C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD, _PI]),
     "rome_conv_pose3pose3": (C.c_int, [_CTX, _PO, C.c_int32, _PI, _PD, _PD, _PD, _PD, _PD, _PI]),
     "rome_sample_priorpose2": (C.c_int, [_CTX, _PO, C.c_int32, _PD, _PD, _PD, _PD]),

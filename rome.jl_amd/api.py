@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3,
-                      PriorPose3, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, getCoordinates)
+                      PriorPose3, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, Pose3Pose3Rotation, getCoordinates)
 
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
@@ -116,6 +116,16 @@ def residual_pose3pose3xyyaw_pt(z, p_pt, q_pt, ctx=None):
     return _rows(_lib.load().rome_residual_pose3pose3xyyaw_pt, ctx, (z, p_pt, q_pt), (3, 12, 12), 3)
 
 
+def residual_pose3pose3rotation(z, p, q, ctx=None):
+    """z − Log(R_pᵀ R_q) per row (PartialPose3.jl:212-227): z (n, 3) rotation vectors, p / q (n, 6) Pose3 coordinates -> (n, 3)"""
+    return _rows(_lib.load().rome_residual_pose3pose3rotation, ctx, (z, p, q), (3, 6, 6), 3)
+
+
+def residual_pose3pose3rotation_pt(z, p_pt, q_pt, ctx=None):
+    """the same with the poses as native points (n, 12)"""
+    return _rows(_lib.load().rome_residual_pose3pose3rotation_pt, ctx, (z, p_pt, q_pt), (3, 12, 12), 3)
+
+
 def _meas_coords(factor, meas):
     """Accepts the reference's tangent containers (hat form) or plain coordinates."""
     m = np.asarray(meas, dtype=np.float64).ravel()
@@ -137,6 +147,11 @@ def _meas_coords(factor, meas):
             return m
         if m.size == 4:   # [0 -b; b 0] column-major (the so(2) tangent the reference samples)
             return m[1:2]
+    elif isinstance(factor, Pose3Pose3Rotation):   # (an SO(3) tangent, getManifold PartialPose3.jl:210)
+        if m.size == 3:
+            return m
+        if m.size == 9:   # skew matrix column-major -> (X32, X13, X21)
+            return np.array([m[5], m[6], m[1]])
     elif isinstance(factor, (Pose3Pose3, PriorPose3)):
         if m.size == 6:
             return m
@@ -174,6 +189,10 @@ def calcFactorResidualTemporary(factor, vartypes, meas, points, ctx=None):
         if pts[0].size == 12:
             return residual_pose3pose3xyyaw_pt([z], [pts[0]], [pts[1]], ctx)[0]
         return residual_pose3pose3xyyaw([z], [pts[0]], [pts[1]], ctx)[0]
+    if isinstance(factor, Pose3Pose3Rotation):
+        if pts[0].size == 12:
+            return residual_pose3pose3rotation_pt([z], [pts[0]], [pts[1]], ctx)[0]
+        return residual_pose3pose3rotation([z], [pts[0]], [pts[1]], ctx)[0]
     if isinstance(factor, Pose3Pose3):
         if pts[0].size == 12:
             return residual_pose3pose3_pt([z], [pts[0]], [pts[1]], ctx)[0]
@@ -520,6 +539,25 @@ def conv_pose3pose3xyyaw(opts, mu, cov, fixed, target, dirs=None, noise=None, wa
     st = np.zeros((C_, N), dtype=np.int32) if want_status else None
     _lib.check(_lib.load().rome_conv_pose3pose3xyyaw(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(cov), _p(fixed),
                                                     _p(noise), _p(out), _pi(st)), ctx.handle)
+    return (out, st) if want_status else out
+
+
+def conv_pose3pose3rotation(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None):
+    """C Pose3Pose3Rotation convolutions (PartialPose3.jl:204-227): mu (C, 3), cov (C, 3, 3), dirs (C,) or None (0: solve q from p, 1: solve p
+    from q), fixed / target C Pose3 blocks, noise C blocks of three standard normals per particle (or the rotation-vector samples themselves
+    under presampled=NOISE_MEASUREMENTS).  Solves the target's (ω_x, ω_y, ω_z); every particle's translation is returned unchanged (bit
+    for bit in the coordinate layouts).  nullhypo: the fraction of particles the factor does not apply to (opts.nullhypo when None)."""
+    ctx = ctx or default_context()
+    opts = _with_nullhypo(_with_layout(opts, layout), nullhypo)
+    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
+    mu = _d(mu, (C_, 3)); cov = _d(cov, (C_, 3, 3))
+    fixed = _blocks(fixed, C_, N, 6, opts.layout)
+    out = _blocks(target, C_, N, 6, opts.layout).copy()
+    noise = None if noise is None else _blocks(noise, C_, N, 3, opts.layout, points_ok=False)
+    dirs = None if dirs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dirs, dtype=np.int32), (C_,)))
+    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
+    _lib.check(_lib.load().rome_conv_pose3pose3rotation(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(cov), _p(fixed),
+                                                       _p(noise), _p(out), _pi(st)), ctx.handle)
     return (out, st) if want_status else out
 
 

@@ -3,7 +3,7 @@ test/testBasicPose2Conv.jl:25, test/TestPoseAndPoint2Constraints.jl:36,97)."""
 import numpy as np
 
 from . import _lib, api
-from .factors import Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP
+from .factors import Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP, Pose3Pose3Rotation
 
 
 def approxConv(fg, flabel, target, solver=_lib.SOLVER_NEWTON, seed=None, ctx=None, **optkw):
@@ -54,6 +54,8 @@ def approxConv(fg, flabel, target, solver=_lib.SOLVER_NEWTON, seed=None, ctx=Non
         return api.conv_pose3pose3(opts, [f.Z.mu], [f.Z.cov], fixed, u0, dirs=[direction], ctx=ctx)[0]
     if isinstance(f, Pose3Pose3XYYaw):
         return api.conv_pose3pose3xyyaw(opts, [f.Z.mu], [f.Z.cov], fixed, u0, dirs=[direction], ctx=ctx)[0]
+    if isinstance(f, Pose3Pose3Rotation):
+        return api.conv_pose3pose3rotation(opts, [f.Z.mu], [f.Z.cov], fixed, u0, dirs=[direction], ctx=ctx)[0]
     if isinstance(f, Pose2Point2BearingRange):
         return api.conv_pose2point2br(opts, direction, [[f.bearing.mu, f.range.mu]], [[f.bearing.sigma, f.range.sigma]],
                                       fixed, u0, ctx=ctx)[0]

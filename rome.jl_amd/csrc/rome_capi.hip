@@ -157,7 +157,7 @@ int cholesky_one(int d, const double* cov, double* Lp) {
   return ROME_OK;
 }
 
-enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2, kP2R, kPPR, kPB, kP3XYY, kP3ZRP };
+enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2, kP2R, kPPR, kPB, kP3XYY, kP3ZRP, kP3ROT };
 
 // common host-pointer path: stage -> launch -> fetch
 int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const int32_t* dir, int dir_all,
@@ -245,6 +245,7 @@ int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const i
     case kPB: e = launch_conv_pose2point2bearing(a, o->solver, s); break;
     case kP3XYY: e = launch_conv_pose3pose3xyyaw(a, o->solver, s); break;
     case kP3ZRP: e = launch_conv_priorpose3zrp(a, s); break;
+    case kP3ROT: e = launch_conv_pose3pose3rotation(a, o->solver, s); break;
   }
   ROME_HIP(ctx, e);
   if (status) ROME_HIP(ctx, hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)C * N, hipMemcpyDeviceToHost, s));
@@ -427,6 +428,16 @@ int rome_residual_pose3pose3xyyaw_pt(rome_ctx* c, int32_t n, const double* z, co
   return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
     return launch_residual_pose3pose3xyyaw(n, a, b, d, 1, o, s); });
 }
+int rome_residual_pose3pose3rotation(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
+  RowBuf in[3] = {{z, 3}, {p, 6}, {q, 6}};
+  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
+    return launch_residual_pose3pose3rotation(n, a, b, d, 0, o, s); });
+}
+int rome_residual_pose3pose3rotation_pt(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
+  RowBuf in[3] = {{z, 3}, {p, 12}, {q, 12}};
+  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
+    return launch_residual_pose3pose3rotation(n, a, b, d, 1, o, s); });
+}
 int rome_residual_priorpose3(rome_ctx* c, int32_t n, const double* m, const double* p, double* r) {
   RowBuf in[2] = {{m, 6}, {p, 6}};
   return host_rows(c, n, in, 2, r, 6, [&](const double* a, const double* b, const double*, double* o, hipStream_t s) {
@@ -536,6 +547,16 @@ int rome_conv_pose3pose3xyyaw(rome_ctx* c, const rome_opts* o, int32_t C, const 
   if ((rc = rome_cholesky_lower(3, C, cov, L.data()))) return rc;
   return host_conv(c, o, kP3XYY, C, dir, 0, 3, 6, 6, mu, L.data(), 6, fixed, noise, target_inout, status);
 }
+int rome_conv_pose3pose3rotation(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* cov,
+                                const double* fixed, const double* noise, double* target_inout, int32_t* status) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || C < 0 || (C > 0 && (!mu || !cov || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
+  if (C == 0) return ROME_OK;
+  if (dir) for (int i = 0; i < C; ++i) if (dir[i] != 0 && dir[i] != 1) return ROME_ERR_INVALID_ARG;
+  std::vector<double> L((size_t)C * 6);
+  if ((rc = rome_cholesky_lower(3, C, cov, L.data()))) return rc;
+  return host_conv(c, o, kP3ROT, C, dir, 0, 3, 6, 6, mu, L.data(), 6, fixed, noise, target_inout, status);
+}
 int rome_conv_priorpose3zrp(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* sigma_z, const double* cov_rp,
                             const double* noise, double* target_inout) {
   int rc = check_opts(o); if (rc) return rc;
@@ -622,6 +643,11 @@ int rome_conv_pose3pose3xyyaw_dev(rome_ctx* c, const rome_opts* o, const rome_co
   if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;   // no multihypo on the partial Pose3 factors
   if (t && !t->dir && !t->rows4 && t->dir_all != 0 && t->dir_all != 1) return ROME_ERR_INVALID_ARG;
   return dev_launch(c, o, t, true, launch_conv_pose3pose3xyyaw);
+}
+int rome_conv_pose3pose3rotation_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
+  if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;   // no multihypo on the partial Pose3 factors
+  if (t && !t->dir && !t->rows4 && t->dir_all != 0 && t->dir_all != 1) return ROME_ERR_INVALID_ARG;
+  return dev_launch(c, o, t, true, launch_conv_pose3pose3rotation);
 }
 int rome_conv_priorpose3zrp_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
   if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;

@@ -1,13 +1,13 @@
 // rome_conv_pose3_partial.hip -- the partial Pose3 factors (src/factors/PartialPose3.jl) on the kernels of rome_conv.hpp:
-// Pose3Pose3XYYaw, partial = (1, 2, 6), and PriorPose3ZRP, partial = (3, 4, 5).  The partial rule of DESIGN §12a on a Pose3 target: the
+// Pose3Pose3XYYaw, partial = (1, 2, 6), PriorPose3ZRP, partial = (3, 4, 5), and Pose3Pose3Rotation, partial = (4, 5, 6).  The partial rule of DESIGN §12a on a Pose3 target: the
 // spread over the whole variable (P3P3::spread, all six tangent coordinates), entropy and solve on the partial coordinates only, every
-// other coordinate stored from the loaded value -- bit for bit.  Both policies stay off the packed sweep (kUniqueRoot = false): it has no
+// other coordinate stored from the loaded value -- bit for bit.  The policies stay off the packed sweep (kUniqueRoot = false): it has no
 // partial notion.  The wave-per-row kernels only (k_conv, k_conv_big).
 #include "rome_conv_p3.hpp"
 
 namespace rome {
 
-// What the two policies share.  The state is the COORDINATES (t, ω) from load to store (no Aux, no Log on the way out); a quaternion is
+// What the policies share.  The state is the COORDINATES (t, ω) from load to store (no Aux, no Log on the way out); a quaternion is
 // built only where the statistic over all six coordinates needs one.  I0, I1, I2: the partial coordinates (0-based).
 // The entropy is ADDITIVE on the partial coordinates, t[I] += spread (u[I] − ½): the compose form u0 ∘ exp(e) of P3P3::add_entropy would move
 // the other three as soon as the pose is tilted.  Uniforms: the d = 6 draw, three of them used.
@@ -194,10 +194,116 @@ struct P3ZRP : P3Partial<2, 3, 4> {
   }
 };
 
+// ---- Pose3Pose3Rotation (PartialPose3.jl:204-227) over [p, q]: r = z − Log(R_pᵀ R_q), z a rotation vector, Log the principal one.
+// Unknowns: the target's (ω_x, ω_y, ω_z); its translation is a constant of the solve (and no translation enters the residual).
+// The root rotation qa, as a unit quaternion:
+//   dir 0 (solve q): R_q = R_p Exp(z),   qa = q_p ⊗ q_z
+//   dir 1 (solve p): R_p = R_q Exp(−z),  qa = q_q ⊗ conj(q_z)
+// It is the zero of the functor whenever |z| < π; for |z| >= π the functor has none (z − Log(Exp z) is a whole turn about the axis), the
+// closed form returns the same rotation and every status output reports the functor: status 1 there.
+//   CLOSED_FORM / NEWTON: ω = Log qa (the start point's ω is not read).
+//   GAUSS_NEWTON:         from the start particle's own rotation u: e = conj(qa) ⊗ u (= Exp(z)ᵀ R_pᵀ R_q for dir 0, the mirrored product for
+//                         dir 1), u <- u ⊗ conj(e) -- the residual rotation itself is the update, as in P3P3::gauss_newton; the functor at
+//                         every iterate, its Log taken only where the test can pass; one pass, the loop ends on a wave ballot.
+//   NELDER_MEAD:          nelder_mead<3> on Σr² over (ω_x, ω_y, ω_z) through 3x3 frames (as P3P3Cost); the only solver that cycles.
+struct ROTCost {
+  double z[3]; double F[9]; int dir;   // F: the fixed pose's frame
+  __device__ __forceinline__ double operator()(const double (&x)[3]) const {
+    double T[9], r[3];
+    so3_exp(x, T);
+    if (dir == 0) residual_pose3pose3rotation(z, F, T, r); else residual_pose3pose3rotation(z, T, F, r);
+    return r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+  }
+};
+
+struct P3ROT : P3Partial<3, 4, 5> {
+  static constexpr int NL = 6, NK = 9;
+  struct Consts { double mu[3]; double L[6]; int dir; };
+  __device__ static __forceinline__ Consts load(const ConvArgs& a, int f, int dr) {
+    Consts K;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) K.mu[k] = a.mu[3 * f + k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) K.L[k] = a.L[6 * f + k];
+    K.dir = dr;
+    return K;
+  }
+  __device__ static __forceinline__ void measurement(const Consts& K, const double (&xi)[3], double (&z)[3]) {   // the d = 3 normal rule of P3XYY
+    z[0] = K.mu[0] + K.L[0] * xi[0];
+    z[1] = K.mu[1] + K.L[1] * xi[0] + K.L[2] * xi[1];
+    z[2] = K.mu[2] + K.L[3] * xi[0] + K.L[4] * xi[1] + K.L[5] * xi[2];
+  }
+  __device__ static __forceinline__ bool needs_cycles(int solver, const Consts&) { return solver == kSolverNelderMead; }
+  struct Prep { double qa[4]; };
+  __device__ static __forceinline__ Prep prepare(const Consts& K, const double (&z)[3], const double (&fxc)[6]) {
+    Prep P;
+    double qF[4], qz[4];
+    quat_exp(&fxc[3], qF); quat_exp(z, qz);
+    const double sg = K.dir != 0 ? -1.0 : 1.0;
+    qz[1] *= sg; qz[2] *= sg; qz[3] *= sg;
+    quat_mul(qF, qz, P.qa);
+    return P;
+  }
+  // the residual FUNCTOR at the target rotation qT (unit quaternions: the same rotation R_pᵀ R_q as the 3x3 form of the residual entry points)
+  __device__ static __forceinline__ double functor_max(const Consts& K, const double (&z)[3], const double (&qF)[4], const double (&qT)[4]) {
+    const bool back = K.dir != 0;
+    double X[4], Y[4], g[4], w[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { X[k] = back ? qT[k] : qF[k]; Y[k] = back ? qF[k] : qT[k]; }
+    quat_cmul(X, Y, g); quat_log(g, w);
+    return fmax(fabs(z[0] - w[0]), fmax(fabs(z[1] - w[1]), fabs(z[2] - w[2])));
+  }
+  __device__ static __forceinline__ int verify(const Consts& K, const double (&z)[3], const double (&fxc)[6], const double (&t)[6], const Aux&, double tol) {
+    double qF[4], qT[4];
+    quat_exp(&fxc[3], qF); quat_exp(&t[3], qT);
+    return functor_max(K, z, qF, qT) <= tol ? 0 : 1;
+  }
+  __device__ static __forceinline__ int gauss_newton(const Consts& K, const Prep& P, const double (&z)[3], const double (&fxc)[6], double (&t)[6],
+                                                     int max_iters, double tol) {
+    double qF[4], u[4];
+    quat_exp(&fxc[3], qF); quat_exp(&t[3], u);
+    bool done = false;
+    for (int it = 0; it < max_iters; ++it) {
+      double e[4];
+      quat_cmul(P.qa, u, e);
+      // Exp is 1-Lipschitz, so the angle of e is at most |r|₂ <= √3 |r|∞, and 2 |vec e| is at most that angle: a lane with 4 |vec e|² > 3 tol²
+      // is not converged whatever the functor's Log is (the rule of P3P3::gauss_newton)
+      const double n2e = e[1] * e[1] + e[2] * e[2] + e[3] * e[3];
+      const bool undecided = !(4.0 * n2e > 3.0 * tol * tol);
+      if (__builtin_amdgcn_ballot_w64(undecided) != 0) done = undecided && functor_max(K, z, qF, u) <= tol;
+      if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
+      double qn[4];
+      quat_mulc(u, e, qn);
+      // (renormalised: a product of unit quaternions drifts by an ulp per step; 1/|q| = 3/2 − |q|²/2 to O(eps²))
+      const double nn = __builtin_fma(-0.5, qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3], 1.5);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) u[k] = done ? u[k] : qn[k] * nn;
+    }
+    quat_log(u, &t[3]);
+    return done ? 0 : 1;
+  }
+  template <int SOLVER>
+  __device__ static __forceinline__ int solve(const Consts& K, const Prep& P, const double (&z)[3], const double (&fxc)[6],
+                                              double (&t)[6], Aux&, int max_iters, double tol) {
+    if constexpr (SOLVER == kSolverClosedForm || SOLVER == kSolverNewton) { quat_log(P.qa, &t[3]); return 0; }
+    else if constexpr (SOLVER == kSolverGaussNewton) return gauss_newton(K, P, z, fxc, t, max_iters, tol);
+    else {
+      ROTCost cost;
+      cost.z[0] = z[0]; cost.z[1] = z[1]; cost.z[2] = z[2];
+      so3_exp(&fxc[3], cost.F); cost.dir = K.dir;
+      double x[3] = {t[3], t[4], t[5]};
+      const int st = nelder_mead<3>(cost, x, max_iters, tol);
+      t[3] = x[0]; t[4] = x[1]; t[5] = x[2];
+      return st;
+    }
+  }
+};
+
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
 hipError_t launch_conv_pose3pose3xyyaw(const ConvArgs& a, int solver, hipStream_t s) { return launch_solver<P3XYY>(a, solver, s); }
+hipError_t launch_conv_pose3pose3rotation(const ConvArgs& a, int solver, hipStream_t s) { return launch_solver<P3ROT>(a, solver, s); }
 hipError_t launch_conv_priorpose3zrp(const ConvArgs& a, hipStream_t s) { return launch_ppl<P3ZRP, kSolverClosedForm>(a, s); }
 
 }  // namespace rome

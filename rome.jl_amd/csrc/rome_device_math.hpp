@@ -633,6 +633,14 @@ __device__ __forceinline__ Se2 se2_of_pose3(double x, double y, double r11, doub
 __device__ __forceinline__ void residual_pose3pose3xyyaw(double zx, double zy, double cz, double sz, const Se2& p2, const Se2& q2, double (&r)[3]) {
   residual_pose2pose2(zx, zy, cz, sz, p2, q2, r);
 }
+// Pose3Pose3Rotation (src/factors/PartialPose3.jl:212-227): r = z − Log(R_pᵀ R_q), z a rotation vector; Rp, Rq column-major 3x3 frames.
+// The translations do not enter.  Log is so3_log: the principal rotation vector, |Log| <= π.
+__device__ __forceinline__ void residual_pose3pose3rotation(const double* z, const double* Rp, const double* Rq, double (&r)[3]) {
+  double U[9], w[3];
+  mat3_tmul(Rp, Rq, U);
+  so3_log(U, w);
+  r[0] = z[0] - w[0]; r[1] = z[1] - w[1]; r[2] = z[2] - w[2];
+}
 __device__ __forceinline__ void se3_add_entropy(Se3& T, double spread, const double (&u)[6]) {
   double e[6];
 #pragma unroll

@@ -57,6 +57,7 @@ hipError_t launch_conv_pose2point2range(const ConvArgs& a, int solver, hipStream
 hipError_t launch_conv_pose2point2bearing(const ConvArgs& a, int solver, hipStream_t s);  // dir_all: 0 solve the landmark, 1 the pose
 hipError_t launch_conv_pose3pose3xyyaw(const ConvArgs& a, int solver, hipStream_t s);     // rows of both directions (dir column / rows4)
 hipError_t launch_conv_priorpose3zrp(const ConvArgs& a, hipStream_t s);                    // prior rows that read the target belief (fixed = target)
+hipError_t launch_conv_pose3pose3rotation(const ConvArgs& a, int solver, hipStream_t s);   // rows of both directions (dir column / rows4)
 hipError_t launch_sweep_pose2(const ConvArgs* p2p2, const ConvArgs* br1, const ConvArgs* br0, int solver, hipStream_t s);
 hipError_t launch_sample_priorpose2(const ConvArgs& a, hipStream_t s);
 hipError_t launch_sample_priorpose3(const ConvArgs& a, hipStream_t s);
@@ -68,6 +69,7 @@ hipError_t launch_residual_bearingrange(int n, const double* z, const double* p,
 hipError_t launch_residual_pose3pose3(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s);
 hipError_t launch_residual_priorpose3(int n, const double* m, const double* p, double* r, hipStream_t s);
 hipError_t launch_residual_pose3pose3xyyaw(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s);
+hipError_t launch_residual_pose3pose3rotation(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s);
 hipError_t launch_residual_range(int n, const double* z, const double* x, int dx, const double* l, double* r, hipStream_t s);
 hipError_t launch_residual_bearing(int n, const double* z, const double* p, int p_is_point, const double* l, double* r, hipStream_t s);
 

@@ -120,6 +120,19 @@ __global__ void k_residual_pose3pose3xyyaw(int n, const double* z, const double*
   residual_pose3pose3xyyaw(z[3 * i], z[3 * i + 1], cz, sz, P, Q, rr);
   r[3 * i] = rr[0]; r[3 * i + 1] = rr[1]; r[3 * i + 2] = rr[2];
 }
+// Pose3Pose3Rotation (PartialPose3.jl:212-227): z rows are rotation vectors (3); p, q rows as k_residual_pose3pose3 (only the rotations are read)
+__global__ void k_residual_pose3pose3rotation(int n, const double* z, const double* p, const double* q, int pts, double* r) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double Rp[9], Rq[9];
+  if (pts) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { Rp[k] = p[12 * i + 3 + k]; Rq[k] = q[12 * i + 3 + k]; }
+  } else { so3_exp(p + 6 * i + 3, Rp); so3_exp(q + 6 * i + 3, Rq); }
+  double rr[3];
+  residual_pose3pose3rotation(z + 3 * i, Rp, Rq, rr);
+  r[3 * i] = rr[0]; r[3 * i + 1] = rr[1]; r[3 * i + 2] = rr[2];
+}
 __global__ void k_residual_priorpose3(int n, const double* m, const double* p, double* r) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -209,6 +222,9 @@ hipError_t launch_residual_pose3pose3(int n, const double* z, const double* p, c
 }
 hipError_t launch_residual_pose3pose3xyyaw(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s) {
   return launch_rows(k_residual_pose3pose3xyyaw, n, s, z, p, q, pts, r);
+}
+hipError_t launch_residual_pose3pose3rotation(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s) {
+  return launch_rows(k_residual_pose3pose3rotation, n, s, z, p, q, pts, r);
 }
 hipError_t launch_residual_priorpose3(int n, const double* m, const double* p, double* r, hipStream_t s) {
   return launch_rows(k_residual_priorpose3, n, s, m, p, r);

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .factors import Pose2, Point2, Pose3, Pose2Point2Range, Pose3Pose3XYYaw, PriorPose3ZRP, partial_coverage
+from .factors import Pose2, Point2, Pose3, Pose2Point2Range, Pose3Pose3XYYaw, PriorPose3ZRP, Pose3Pose3Rotation, partial_coverage
 from .graph import PackedGraph
 from .api import cholesky_lower
 
@@ -217,6 +217,14 @@ class DeviceGraph:
                 rows4=np.stack([np.arange(F, dtype=np.int32), col(0, F), zr["var"], zr["var"]], axis=1), nh=nh_or_none(zr["nh"]),
                 partial=partial_coverage(PriorPose3ZRP, 0))
             self.tab["zrp3"] = dict(F=F)
+        # p3rot: Pose3Pose3Rotation, the shape of p3xyy; the last record, so a graph without it keeps its launches, rows and streams
+        ro = getattr(pk, "p3rot", None)
+        if ro is not None and ro["F"]:
+            factor, dr, fixed, target = PackedGraph.conv_table(ro)
+            add("p3rot", "rome_conv_pose3pose3rotation_dev", Pose3, Pose3, 0, self.STREAM_P3ROT, target, t(ro["mu"], f64), t(cholesky_lower(ro["cov"]), f64),
+                rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(ro["nh"], 2)),
+                partial=partial_coverage(Pose3Pose3Rotation, 0))   # (the same coordinates towards either pose)
+            self.tab["p3rot"] = dict(F=ro["F"], C=2 * ro["F"])
 
         # one conv_step: the fused Pose2 / Point2 call for its three records when all three have rows, then every other record that
         # owns proposal rows, in list order
@@ -385,6 +393,7 @@ class DeviceGraph:
     STREAM_PB1, STREAM_PB0 = 11 << 28, 12 << 28   # bearing-only factor (Pose2Point2Bearing dir 1 / 0)
 
     STREAM_P3XYY, STREAM_ZRP3 = 13 << 28, 14 << 28   # partial Pose3 factors (Pose3Pose3XYYaw both directions, PriorPose3ZRP)
+    STREAM_P3ROT = (14 << 28) + (1 << 27)            # Pose3Pose3Rotation both directions: the upper half of zrp3's slot (every slot is taken)
 
     # stage 2 of the partial-aware product (task (v, c) draws base + v·dim + c): Pose2, Pose3.  15 << 28 is the last 28-bit slot below
     # the sweep field (sweep << 32), so the two bases share it, 2^27 streams each
@@ -392,7 +401,7 @@ class DeviceGraph:
 
     def has_partial3(self):
         """does the graph hold partial Pose3 factors (served by conv_step / solve only: not by the multi-rank drivers)"""
-        return "p3xyy" in self.tab or "zrp3" in self.tab
+        return "p3xyy" in self.tab or "zrp3" in self.tab or "p3rot" in self.tab
 
     def has_bearing(self):
         """does the graph hold bearing-only factors (served by conv_step / solve only: not by the multi-rank drivers)"""
@@ -619,6 +628,10 @@ class DeviceGraph:
         """direction 0: poses -> landmark proposals [F, 2, N] (on the sighting rays); 1: landmarks -> pose proposals [F, 3, N]
         (translations kept, headings turned to the bearing)."""
         return self._sweep(self.fams["pb0" if direction == 0 else "pb1"], opts, out, noise, status)
+
+    def sweep_pose3pose3rotation(self, opts, out=None, noise=None, status=None):
+        """Pose3Pose3Rotation rows, both directions interleaved -> proposals [2F, 6, N] ((ω_x, ω_y, ω_z) solved, the translation kept)."""
+        return self._sweep(self.fams["p3rot"], opts, out, noise, status)
 
     def sweep_pose3pose3xyyaw(self, opts, out=None, noise=None, status=None):
         """Pose3Pose3XYYaw rows, both directions interleaved -> proposals [2F, 6, N] ((x, y, ω_z) solved, z, ω_x, ω_y kept)."""

@@ -22,7 +22,7 @@ def _refuse_range_tables(dg, where):
     if getattr(dg, "has_bearing", None) is not None and dg.has_bearing():
         raise TypeError("%s: Pose2Point2Bearing factors are not supported by the multi-rank drivers" % where)
     if getattr(dg, "has_partial3", None) is not None and dg.has_partial3():
-        names = [n for n, k in (("Pose3Pose3XYYaw", "p3xyy"), ("PriorPose3ZRP", "zrp3")) if k in dg.tab]
+        names = [n for n, k in (("Pose3Pose3XYYaw", "p3xyy"), ("PriorPose3ZRP", "zrp3"), ("Pose3Pose3Rotation", "p3rot")) if k in dg.tab]
         raise TypeError("%s: %s factors are not supported by the multi-rank drivers" % (where, " / ".join(names)))
 
 

@@ -9,6 +9,7 @@ Same names and argument meaning as the reference (paths relative to the RoME.jl 
   Point2Point2Range(Z), Pose2Point2Range(Z)                 src/factors/Range2D.jl:8-17, 40-54
   Pose2Point2Bearing(Z)                                      src/factors/Bearing2D.jl:10-32
   Pose3Pose3XYYaw(Z), PriorPose3ZRP(z, rp)                   src/factors/PartialPose3.jl:101-136, 12-46
+  Pose3Pose3Rotation(Z)                                      src/factors/PartialPose3.jl:204-227
   getMeasurementParametric(::Pose2Point2BearingRange)        src/factors/BearingRange2D.jl:30-37
   Packed* <-> factor converters                              src/factors/Pose2D.jl:76-84 etc.
 These objects only hold the measurement model; all arithmetic is done by the HIP library.
@@ -239,8 +240,23 @@ class PriorPose3ZRP(_PriorFactor):
         self.rp = rp
 
 
+class Pose3Pose3Rotation(_RelativeFactor):
+    """Relative attitude between two `Pose3` variables (src/factors/PartialPose3.jl:204-227), partial = (4, 5, 6): r = Z − Log(R_pᵀ R_q),
+    Z a 3-dimensional `MvNormal` of the rotation vector.  Solving a pose moves its (ω_x, ω_y, ω_z) only; every particle's translation
+    passes through unchanged."""
+    variable_types = (Pose3, Pose3)
+    partial = (4, 5, 6)
+
+    def __init__(self, Z):
+        if not isinstance(Z, MvNormal):
+            raise TypeError("Pose3Pose3Rotation: this build supports an MvNormal belief, got %s" % type(Z).__name__)
+        if Z.mu.size != 3:
+            raise ValueError("Pose3Pose3Rotation needs a 3-dimensional belief (the rotation vector)")
+        self.Z = Z
+
+
 RANGE_FACTORS = (Point2Point2Range, Pose2Point2Range)
-PARTIAL3_FACTORS = (Pose3Pose3XYYaw, PriorPose3ZRP)
+PARTIAL3_FACTORS = (Pose3Pose3XYYaw, PriorPose3ZRP, Pose3Pose3Rotation)
 
 
 def partial_coverage(factor, position):
@@ -328,7 +344,8 @@ def unpack_factor(d):
     cls = {"Pose2Pose2": Pose2Pose2, "PriorPose2": PriorPose2, "Pose3Pose3": Pose3Pose3, "PriorPose3": PriorPose3,
            "PriorPoint2": PriorPoint2, "Point2Point2Range": Point2Point2Range, "Pose2Point2Range": Pose2Point2Range,
            "Pose2Point2Bearing": Pose2Point2Bearing,    # PackedPose2Point2Bearing: Z (Bearing2D.jl:36-45)
-           "Pose3Pose3XYYaw": Pose3Pose3XYYaw}[t]       # PackedPose3Pose3XYYaw: Z (PartialPose3.jl:172-174)
+           "Pose3Pose3XYYaw": Pose3Pose3XYYaw,          # PackedPose3Pose3XYYaw: Z (PartialPose3.jl:172-174)
+           "Pose3Pose3Rotation": Pose3Pose3Rotation}[t]  # PackedPose3Pose3Rotation: Z (PartialPose3.jl:234-236)
     return cls(_unpack_belief(d["Z"]))
 
 

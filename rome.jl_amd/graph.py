@@ -14,7 +14,7 @@ import numpy as np
 
 from .factors import (MvNormal, Normal, Uniform, Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange,
                       Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw,
-                      PriorPose3ZRP)
+                      PriorPose3ZRP, Pose3Pose3Rotation)
 
 
 @_contextlib.contextmanager
@@ -458,7 +458,7 @@ class PackedGraph:
         for l, t in fg.variables.items():
             self.index[l] = len(self.labels[t])
             self.labels[t].append(l)
-        p2, br, p3, pr2, pr3, prpt, p2r, ppr, pb, xyy, zrp = [], [], [], [], [], [], [], [], [], [], []
+        p2, br, p3, pr2, pr3, prpt, p2r, ppr, pb, xyy, zrp, rot = [], [], [], [], [], [], [], [], [], [], [], []
         nullh = getattr(fg, "nullhypo", {})
         for flabel, labels, f in fg.factors:
             ids = [self.index[l] for l in labels]
@@ -473,6 +473,7 @@ class PackedGraph:
             elif isinstance(f, Pose2Point2Bearing): pb.append((ids, f, flabel))
             elif isinstance(f, Pose3Pose3XYYaw): xyy.append((ids, f, flabel))
             elif isinstance(f, PriorPose3ZRP): zrp.append((ids, f, flabel))
+            elif isinstance(f, Pose3Pose3Rotation): rot.append((ids, f, flabel))
             else: raise TypeError("factor type %s is outside the hot path" % type(f).__name__)
 
         def rel_tables(items, d):
@@ -532,13 +533,20 @@ class PackedGraph:
         self.pprng = range_tables(ppr, "pose", "point")   # Pose2Point2Range over [x, lm]
         self.pbear = range_tables(pb, "pose", "point")    # Pose2Point2Bearing over [p, l] (Bearing2D.jl): one bearing belief per factor
         # partial Pose3 factors (PartialPose3.jl), nullhypo per factor.  p3xyy: Pose3Pose3XYYaw over [p, q], one 3-dimensional normal belief
-        # per factor; zrp3: PriorPose3ZRP, mu = (μ_z, μ_roll, μ_pitch), sigma_z, cov_rp the 2x2 roll / pitch covariance
-        Fx, Fz = len(xyy), len(zrp)
+        # per factor (p3rot: Pose3Pose3Rotation, the same shape); zrp3: PriorPose3ZRP, mu = (μ_z, μ_roll, μ_pitch), sigma_z, cov_rp the 2x2
+        # roll / pitch covariance
+        Fz = len(zrp)
         nhs = lambda items: np.array([nullh.get(fl, 0.0) for _, _, fl in items], dtype=np.float64)
-        self.p3xyy = dict(F=Fx, mu=np.array([f.Z.mu for _, f, _ in xyy], dtype=np.float64).reshape(Fx, 3),
-                          cov=np.array([f.Z.cov for _, f, _ in xyy], dtype=np.float64).reshape(Fx, 3, 3),
-                          var_from=np.array([ids[0] for ids, _, _ in xyy], dtype=np.int32), var_to=np.array([ids[1] for ids, _, _ in xyy], dtype=np.int32),
-                          nh=nhs(xyy), labels=[it[2] for it in xyy])
+
+        def rel3_tables(items):
+            F = len(items)
+            return dict(F=F, mu=np.array([f.Z.mu for _, f, _ in items], dtype=np.float64).reshape(F, 3),
+                        cov=np.array([f.Z.cov for _, f, _ in items], dtype=np.float64).reshape(F, 3, 3),
+                        var_from=np.array([ids[0] for ids, _, _ in items], dtype=np.int32), var_to=np.array([ids[1] for ids, _, _ in items], dtype=np.int32),
+                        nh=nhs(items), labels=[it[2] for it in items])
+
+        self.p3xyy = rel3_tables(xyy)
+        self.p3rot = rel3_tables(rot)
         self.zrp3 = dict(F=Fz, mu=np.array([[f.z.mu, f.rp.mu[0], f.rp.mu[1]] for _, f, _ in zrp], dtype=np.float64).reshape(Fz, 3),
                          sigma_z=np.array([f.z.sigma for _, f, _ in zrp], dtype=np.float64).reshape(Fz),
                          cov_rp=np.array([f.rp.cov for _, f, _ in zrp], dtype=np.float64).reshape(Fz, 2, 2),
@@ -570,6 +578,7 @@ class PackedGraph:
         self.pprng = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "pose": z32, "point": z32, "nh": np.zeros(0), "labels": []}
         self.pbear = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "pose": z32, "point": z32, "nh": np.zeros(0), "labels": []}
         self.p3xyy = dict(F=0, mu=np.zeros((0, 3)), cov=np.zeros((0, 3, 3)), var_from=z32, var_to=z32, nh=np.zeros(0), labels=[])
+        self.p3rot = dict(F=0, mu=np.zeros((0, 3)), cov=np.zeros((0, 3, 3)), var_from=z32, var_to=z32, nh=np.zeros(0), labels=[])
         self.zrp3 = dict(F=0, mu=np.zeros((0, 3)), sigma_z=np.zeros(0), cov_rp=np.zeros((0, 2, 2)), var=z32, nh=np.zeros(0), labels=[])
         return self
 
@@ -612,7 +621,7 @@ class PackedGraph:
         return bool(getattr(self, "pbear", {"F": 0})["F"])
 
     def has_partial3(self):
-        return bool(getattr(self, "p3xyy", {"F": 0})["F"] or getattr(self, "zrp3", {"F": 0})["F"])
+        return bool(getattr(self, "p3xyy", {"F": 0})["F"] or getattr(self, "zrp3", {"F": 0})["F"] or getattr(self, "p3rot", {"F": 0})["F"])
 
     def beliefs(self, fg, vartype):
         """(V, dim, N) SoA blocks from fg.vals (all variables of the type must be initialised)."""

@@ -246,6 +246,29 @@ function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:
   return manikde!(M3, pts)
 end
 
+# Pose3Pose3Rotation over [p, q], partial = (4, 5, 6): solving a pose moves its rotation only, r = z − Log(R_pᵀ R_q)
+function conv_pose3pose3rotation(fg, f::Pose3Pose3Rotation{<:MvNormal}, fixedpts, u0pts, dir::Integer; solver=1)
+  o = default_opts(fg; solver)
+  μ = collect(Float64, mean(f.Z)); Σ = collect(Float64, cov(f.Z))'
+  fixed = coords(Pose3, fixedpts); target = coords(Pose3, u0pts)
+  d = Int32[dir]
+  GC.@preserve μ Σ fixed target d begin
+    check(ccall((:rome_conv_pose3pose3rotation, LIB), Cint,
+      (Ptr{Cvoid}, Ref{RomeOpts}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+      ctx().h, o, 1, d, μ, Σ, fixed, C_NULL, target, C_NULL))
+  end
+  points(Pose3, target)
+end
+
+function approxConvBelief(dfg::AbstractDFG, fc::DFGFactor{<:CommonConvWrapper{<:Pose3Pose3Rotation{<:MvNormal}}}, target::Symbol,
+                          measurement::AbstractVector=Tuple[]; solveKey::Symbol=:default, kw...)
+  vars = getVariableOrder(fc)
+  dir = vars[2] == target ? 0 : 1
+  other = dir == 0 ? vars[1] : vars[2]
+  pts = conv_pose3pose3rotation(dfg, getFactorType(fc), getVal(dfg, other; solveKey), getVal(dfg, target; solveKey), dir)
+  return manikde!(M3, pts)
+end
+
 function conv_priorpose3zrp(fg, f::PriorPose3ZRP{<:Normal,<:MvNormal}, u0pts)
   o = default_opts(fg)
   μ = Float64[mean(f.z), mean(f.rp)[1], mean(f.rp)[2]]; σz = Float64[std(f.z)]; Σ = collect(Float64, cov(f.rp))'
@@ -268,6 +291,8 @@ conv_pose3pose3xyyaw_dev(o::RomeOpts, tab::Ptr{Cvoid}) =
   check(ccall((:rome_conv_pose3pose3xyyaw_dev, LIB), Cint, (Ptr{Cvoid}, Ref{RomeOpts}, Ptr{Cvoid}), ctx().h, o, tab))
 conv_priorpose3zrp_dev(o::RomeOpts, tab::Ptr{Cvoid}) =
   check(ccall((:rome_conv_priorpose3zrp_dev, LIB), Cint, (Ptr{Cvoid}, Ref{RomeOpts}, Ptr{Cvoid}), ctx().h, o, tab))
+conv_pose3pose3rotation_dev(o::RomeOpts, tab::Ptr{Cvoid}) =
+  check(ccall((:rome_conv_pose3pose3rotation_dev, LIB), Cint, (Ptr{Cvoid}, Ref{RomeOpts}, Ptr{Cvoid}), ctx().h, o, tab))
 
 # ---- priors: N samples of the prior as points (IIF samplePoint) ------------------------------------------------
 function sample_prior(fg, f::Union{PriorPose2,PriorPose3})
@@ -728,6 +753,18 @@ end
 function residual_pose3pose3xyyaw_pt(z::AbstractMatrix, p::AbstractMatrix, q::AbstractMatrix)   # the poses as native points, 12 x n
   r = similar(z)
   check(ccall((:rome_residual_pose3pose3xyyaw_pt, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              ctx().h, size(z, 2), z, p, q, r))
+  r
+end
+function residual_pose3pose3rotation(z::AbstractMatrix, p::AbstractMatrix, q::AbstractMatrix)   # 3 x n rotation vectors, 6 x n pose coordinates
+  r = similar(z)
+  check(ccall((:rome_residual_pose3pose3rotation, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              ctx().h, size(z, 2), z, p, q, r))
+  r
+end
+function residual_pose3pose3rotation_pt(z::AbstractMatrix, p::AbstractMatrix, q::AbstractMatrix)   # the poses as native points, 12 x n
+  r = similar(z)
+  check(ccall((:rome_residual_pose3pose3rotation_pt, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
               ctx().h, size(z, 2), z, p, q, r))
   r
 end

@@ -28,13 +28,13 @@ import numpy as np
 
 from .factors import (MvNormal, Normal, Uniform, Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3,
                       PriorPose3, PriorPoint2, Point2Point2,
-                      Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP)
+                      Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP, Pose3Pose3Rotation)
 from .graph import FactorGraph
 
 _VERSION = "0.25.1"
 _VARTYPES = {"Pose2": Pose2, "Point2": Point2, "Pose3": Pose3}
 _FACTORS = {c.__name__: c for c in (Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2,
-                                     Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP)}
+                                     Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP, Pose3Pose3Rotation)}
 
 
 # ---------------------------------------------------------------- Packed beliefs (IIF PackedSamplableBelief JSON forms)
