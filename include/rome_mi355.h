@@ -188,7 +188,10 @@ int rome_residual_pose2point2bearing_pt(rome_ctx*, int32_t n, const double* z /*
  *   fixed  C blocks of the fixed variable's particles (layout per opts->layout)
  *   noise  C blocks [.][dz] of standard-normal ξ (z = μ + chol(Σ) ξ), or NULL -> in-kernel Philox
  *   target_inout  C blocks: start points u0 (current belief of the target) in, solutions out
- *   status [C][N] or NULL                                                                        */
+ *   status [C][N] or NULL
+ * Every entry of this section checks in one order and returns at the first failure: the options; the context, C >= 0 and a scalar
+ * direction; required pointers (C > 0); C == 0 (ROME_OK, nothing touched); the values of a direction column; hypo_w in [0, 1]; the
+ * noise parameters (NaN or not positive definite: ROME_ERR_NOT_POSDEF).                                                          */
 int rome_conv_pose2pose2(rome_ctx*, const rome_opts*, int32_t C, const int32_t* dir,
                          const double* mu /*C*3*/, const double* cov /*C*9*/,
                          const double* fixed /*C*N*3*/, const double* noise /*C*N*3 or NULL*/,

@@ -126,81 +126,69 @@ def residual_pose3pose3rotation_pt(z, p_pt, q_pt, ctx=None):
     return _rows(_lib.load().rome_residual_pose3pose3rotation_pt, ctx, (z, p_pt, q_pt), (3, 12, 12), 3)
 
 
+def _same(m):
+    return m
+
+
+def _se2_tangent(m):     # ((x, y), [0 -θ; θ 0]) column-major
+    return np.array([m[0], m[1], m[3]])
+
+
+def _se3_tangent(m):     # (t, skew) -> (X32, X13, X21)
+    return np.array([m[0], m[1], m[2], m[3 + 5], m[3 + 6], m[3 + 1]])
+
+
+# factor class -> ({measurement length: its coordinates}, variable types, residual on rows of coordinates, residual on rows of native
+# points or None).  The lengths are the plain coordinates and the reference's tangent container (hat form).  A factor with a native-point
+# residual is given its points as they come (the first point's length selects the function); for the others a native point is converted
+# to coordinates.  Looked up along the factor's classes (_residual_entry), as isinstance would.
+_RESIDUALS = {
+    Pose2Pose2: ({3: _same, 6: _se2_tangent}, (Pose2, Pose2), residual_pose2pose2, None),
+    # the prior residual is evaluated between the sampled measurement POINT and the variable
+    PriorPose2: ({3: _same, 6: _se2_tangent}, (Pose2,), residual_priorpose2, None),
+    Pose2Point2BearingRange: ({2: _same, 5: lambda m: np.array([m[1], m[4]])},     # ([0 -b; b 0], [ρ])
+                              (Pose2, Point2), residual_pose2point2br, residual_pose2point2br_pt),
+    Point2Point2Range: ({1: _same}, (Point2, Point2), residual_point2point2range, None),     # the range sample ρ
+    Pose2Point2Range: ({1: _same}, (Pose2, Point2), residual_pose2point2range, None),
+    Pose2Point2Bearing: ({1: _same, 4: lambda m: m[1:2]},     # [0 -b; b 0] column-major (the so(2) tangent the reference samples)
+                         (Pose2, Point2), residual_pose2point2bearing, residual_pose2point2bearing_pt),
+    # an SE(2) tangent (getManifold PartialPose3.jl:112)
+    Pose3Pose3XYYaw: ({3: _same, 6: _se2_tangent}, (Pose3, Pose3), residual_pose3pose3xyyaw, residual_pose3pose3xyyaw_pt),
+    # an SO(3) tangent (getManifold PartialPose3.jl:210): skew matrix column-major -> (X32, X13, X21)
+    Pose3Pose3Rotation: ({3: _same, 9: lambda m: np.array([m[5], m[6], m[1]])},
+                         (Pose3, Pose3), residual_pose3pose3rotation, residual_pose3pose3rotation_pt),
+    Pose3Pose3: ({6: _same, 12: _se3_tangent}, (Pose3, Pose3), residual_pose3pose3, residual_pose3pose3_pt),
+    PriorPose3: ({6: _same, 12: _se3_tangent}, (Pose3,), residual_priorpose3, None),
+}
+
+
+def _residual_entry(factor):
+    for cls in type(factor).__mro__:
+        if cls in _RESIDUALS:
+            return _RESIDUALS[cls]
+    return {}, (), None, None
+
+
 def _meas_coords(factor, meas):
     """Accepts the reference's tangent containers (hat form) or plain coordinates."""
     m = np.asarray(meas, dtype=np.float64).ravel()
-    if isinstance(factor, (Pose2Pose2, PriorPose2, Pose3Pose3XYYaw)):   # (XYYaw: an SE(2) tangent, getManifold PartialPose3.jl:112)
-        if m.size == 3:
-            return m
-        if m.size == 6:  # ((x,y), [0 -θ; θ 0]) column-major
-            return np.array([m[0], m[1], m[3]])
-    elif isinstance(factor, Pose2Point2BearingRange):
-        if m.size == 2:
-            return m
-        if m.size == 5:  # ([0 -b; b 0], [ρ])
-            return np.array([m[1], m[4]])
-    elif isinstance(factor, (Point2Point2Range, Pose2Point2Range)):
-        if m.size == 1:   # the range sample ρ
-            return m
-    elif isinstance(factor, Pose2Point2Bearing):
-        if m.size == 1:
-            return m
-        if m.size == 4:   # [0 -b; b 0] column-major (the so(2) tangent the reference samples)
-            return m[1:2]
-    elif isinstance(factor, Pose3Pose3Rotation):   # (an SO(3) tangent, getManifold PartialPose3.jl:210)
-        if m.size == 3:
-            return m
-        if m.size == 9:   # skew matrix column-major -> (X32, X13, X21)
-            return np.array([m[5], m[6], m[1]])
-    elif isinstance(factor, (Pose3Pose3, PriorPose3)):
-        if m.size == 6:
-            return m
-        if m.size == 12:  # (t, skew) -> (X32, X13, X21)
-            return np.array([m[0], m[1], m[2], m[3 + 5], m[3 + 6], m[3 + 1]])
-    raise ValueError("measurement of unexpected length %d for %s" % (m.size, type(factor).__name__))
+    coords = _residual_entry(factor)[0].get(m.size)
+    if coords is None:
+        raise ValueError("measurement of unexpected length %d for %s" % (m.size, type(factor).__name__))
+    return coords(m)
 
 
 def calcFactorResidualTemporary(factor, vartypes, meas, points, ctx=None):
     """Residual of `factor` for one measurement and one point per variable (native point layouts,
     or coordinate vectors of the variable's dimension)."""
     z = _meas_coords(factor, meas)
-    pts = [np.asarray(p, dtype=np.float64).ravel() for p in points]
-    if isinstance(factor, Pose2Pose2):
-        c = [p if p.size == 3 else getCoordinates(Pose2, p) for p in pts]
-        return residual_pose2pose2([z], [c[0]], [c[1]], ctx)[0]
-    if isinstance(factor, PriorPose2):
-        # prior residual is evaluated between the sampled measurement POINT and the variable
-        c = pts[0] if pts[0].size == 3 else getCoordinates(Pose2, pts[0])
-        return residual_priorpose2([z], [c], ctx)[0]
-    if isinstance(factor, Pose2Point2BearingRange):
-        if pts[0].size == 6:
-            return residual_pose2point2br_pt([z], [pts[0]], [pts[1]], ctx)[0]
-        return residual_pose2point2br([z], [pts[0]], [pts[1]], ctx)[0]
-    if isinstance(factor, Point2Point2Range):
-        return residual_point2point2range(z, [pts[0]], [pts[1]], ctx)[0]
-    if isinstance(factor, Pose2Point2Range):
-        c = pts[0] if pts[0].size == 3 else getCoordinates(Pose2, pts[0])
-        return residual_pose2point2range(z, [c], [pts[1]], ctx)[0]
-    if isinstance(factor, Pose2Point2Bearing):
-        if pts[0].size == 6:
-            return residual_pose2point2bearing_pt(z, [pts[0]], [pts[1]], ctx)[0]
-        return residual_pose2point2bearing(z, [pts[0]], [pts[1]], ctx)[0]
-    if isinstance(factor, Pose3Pose3XYYaw):
-        if pts[0].size == 12:
-            return residual_pose3pose3xyyaw_pt([z], [pts[0]], [pts[1]], ctx)[0]
-        return residual_pose3pose3xyyaw([z], [pts[0]], [pts[1]], ctx)[0]
-    if isinstance(factor, Pose3Pose3Rotation):
-        if pts[0].size == 12:
-            return residual_pose3pose3rotation_pt([z], [pts[0]], [pts[1]], ctx)[0]
-        return residual_pose3pose3rotation([z], [pts[0]], [pts[1]], ctx)[0]
-    if isinstance(factor, Pose3Pose3):
-        if pts[0].size == 12:
-            return residual_pose3pose3_pt([z], [pts[0]], [pts[1]], ctx)[0]
-        return residual_pose3pose3([z], [pts[0]], [pts[1]], ctx)[0]
-    if isinstance(factor, PriorPose3):
-        c = pts[0] if pts[0].size == 6 else getCoordinates(Pose3, pts[0])
-        return residual_priorpose3([z], [c], ctx)[0]
-    raise TypeError("unsupported factor type %s" % type(factor).__name__)
+    _, types, on_coords, on_points = _residual_entry(factor)
+    pts = [np.asarray(p, dtype=np.float64).ravel() for p in points][:len(types)]
+    if on_points is not None:
+        fn = on_points if pts[0].size == types[0].point_len else on_coords
+    else:
+        fn, pts = on_coords, [p if p.size == t.dim else getCoordinates(t, p) for t, p in zip(types, pts)]
+    return fn([z], *[[p] for p in pts], ctx)[0]
 
 
 # ------------------------------------------------------------------ parametric linearisation
@@ -382,96 +370,89 @@ def coords_to_points(dim, coords, ctx=None):
 
 
 # ------------------------------------------------------------------ host-pointer convolutions
+def _override(opts, layout=None, nullhypo=None):
+    """opts, or a copy with the layout / nullhypo a wrapper was given"""
+    if layout is None and nullhypo is None:
+        return opts
+    o = _lib.Opts.from_buffer_copy(opts)
+    if layout is not None:
+        o.layout = int(layout)
+    if nullhypo is not None:
+        o.nullhypo = float(nullhypo)
+    return o
+
+
+_ABSENT = object()   # the entry point has no such argument
+
+
+def _conv(entry, dims, opts, mu, prms, fixed, target, noise, ctx, layout=None, nullhypo=None, dirs=_ABSENT, direction=_ABSENT,
+          want_status=None, alt=None, hypo_w=None):
+    """THE call of a host-pointer convolution entry `entry`.  dims = (dz, d1, d2), the dimensions of the measurement and of the factor's
+    first and second variable: direction 0 fixes the first and solves the second, another one swaps them.  prms: the noise parameters as
+    (array, shape of one row).  fixed None: the entry takes no fixed blocks.  The direction is a column `dirs` (None: all 0; one value is
+    repeated for every row; an array must have one value per row) or one scalar `direction`; want_status None: the entry has no status
+    array; alt / hypo_w: a multihypo entry (the blocks of the other candidate for the second variable)."""
+    ctx = ctx or default_context()
+    opts = _override(opts, layout, nullhypo)
+    dz, d1, d2 = dims
+    df, dt = (d1, d2) if direction is _ABSENT or direction == 0 else (d2, d1)
+    mu = np.atleast_2d(_d(mu)) if dz > 1 else np.atleast_1d(_d(mu)).reshape(-1, 1)
+    C_, N = mu.shape[0], opts.n_particles
+    mu = _d(mu, (C_, dz))
+    prms = [_d(a if shape else np.atleast_1d(_d(a)).ravel(), (C_,) + shape) for a, shape in prms]
+    args = [] if direction is _ABSENT else [int(direction)]
+    if dirs is not _ABSENT:
+        dirs = None if dirs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dirs, dtype=np.int32), (C_,)))
+        args.append(_pi(dirs))
+    args += [_p(mu)] + [_p(a) for a in prms]
+    if fixed is not None:
+        fixed = _blocks(fixed, C_, N, df, opts.layout)
+        args.append(_p(fixed))
+    out = _blocks(target, C_, N, dt, opts.layout).copy()
+    if alt is not None:
+        alt, hypo_w = _blocks(alt, C_, N, d2, opts.layout), _d(hypo_w, (C_,))
+        args += [_p(alt), _p(hypo_w)]
+    noise = None if noise is None else _blocks(noise, C_, N, dz, opts.layout, points_ok=False)
+    args += [_p(noise), _p(out)]
+    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
+    if want_status is not None:
+        args.append(_pi(st))
+    _lib.check(getattr(_lib.load(), entry)(ctx.handle, C.byref(opts), C_, *args), ctx.handle)
+    return (out, st) if want_status else out
+
+
 def conv_pose2pose2(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, alt=None, hypo_w=None):
     """alt / hypo_w: multihypo over two candidates for the factor's second pose (blocks of the other candidate, P(primary));
     `dirs` must then be one direction (0 or 1) for the whole call."""
-    ctx = ctx or default_context()
-    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
-    cov = _d(cov, (C_, 3, 3))
-    fixed = _blocks(fixed, C_, N, 3, opts.layout)
-    out = _blocks(target, C_, N, 3, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 3, opts.layout, points_ok=False)
-    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
-    if alt is not None:
-        d = np.unique(np.asarray(0 if dirs is None else dirs, dtype=np.int32))
-        if d.size != 1 or int(d[0]) not in (0, 1):
-            raise ValueError("conv_pose2pose2 with multihypo: one direction (0 or 1) per call")
-        alt = _blocks(alt, C_, N, 3, opts.layout); hypo_w = _d(hypo_w, (C_,))
-        _lib.check(_lib.load().rome_conv_pose2pose2_mh(ctx.handle, C.byref(opts), C_, int(d[0]), _p(mu), _p(cov), _p(fixed), _p(alt),
-                                                      _p(hypo_w), _p(noise), _p(out), _pi(st)), ctx.handle)
-        return (out, st) if want_status else out
-    dirs = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.int32)
-    _lib.check(_lib.load().rome_conv_pose2pose2(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(cov), _p(fixed),
-                                               _p(noise), _p(out), _pi(st)), ctx.handle)
-    return (out, st) if want_status else out
+    if alt is None:
+        return _conv("rome_conv_pose2pose2", (3, 3, 3), opts, mu, [(cov, (3, 3))], fixed, target, noise, ctx, dirs=dirs, want_status=want_status)
+    d = np.unique(np.asarray(0 if dirs is None else dirs, dtype=np.int32))
+    if d.size != 1 or int(d[0]) not in (0, 1):
+        raise ValueError("conv_pose2pose2 with multihypo: one direction (0 or 1) per call")
+    return _conv("rome_conv_pose2pose2_mh", (3, 3, 3), opts, mu, [(cov, (3, 3))], fixed, target, noise, ctx, direction=int(d[0]),
+                 want_status=want_status, alt=alt, hypo_w=hypo_w)
 
 
 def conv_pose2point2br(opts, direction, mu, sigma, fixed, target, noise=None, want_status=False, ctx=None,
                        alt=None, hypo_w=None):
     """alt / hypo_w: multihypo over two landmark candidates (blocks of the other landmark, P(primary))."""
-    ctx = ctx or default_context()
-    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
-    sigma = _d(sigma, (C_, 2))
-    df, dt = (3, 2) if direction == 0 else (2, 3)
-    fixed = _blocks(fixed, C_, N, df, opts.layout)
-    out = _blocks(target, C_, N, dt, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 2, opts.layout, points_ok=False)
-    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
-    if alt is None:
-        _lib.check(_lib.load().rome_conv_pose2point2br(ctx.handle, C.byref(opts), C_, int(direction), _p(mu), _p(sigma),
-                                                      _p(fixed), _p(noise), _p(out), _pi(st)), ctx.handle)
-    else:
-        alt = _blocks(alt, C_, N, 2, opts.layout); hypo_w = _d(hypo_w, (C_,))
-        _lib.check(_lib.load().rome_conv_pose2point2br_mh(ctx.handle, C.byref(opts), C_, int(direction), _p(mu), _p(sigma),
-                                                         _p(fixed), _p(alt), _p(hypo_w), _p(noise), _p(out), _pi(st)), ctx.handle)
-    return (out, st) if want_status else out
-
-
-def _with_layout(opts, layout):
-    if layout is None:
-        return opts
-    o = _lib.Opts.from_buffer_copy(opts)
-    o.layout = int(layout)
-    return o
+    return _conv("rome_conv_pose2point2br" if alt is None else "rome_conv_pose2point2br_mh", (2, 3, 2), opts, mu, [(sigma, (2,))], fixed, target,
+                 noise, ctx, direction=direction, want_status=want_status, alt=alt, hypo_w=hypo_w)
 
 
 def conv_point2point2range(opts, mu, sigma, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None):
     """C Point2Point2Range convolutions (Range2D.jl:8-17): mu / sigma (C,) range means and sigmas (sigma < 0: Uniform(mu ± |sigma|)),
     dirs (C,) or None (0: solve lm from xi, 1: solve xi from lm), fixed / target C Point2 blocks, noise C blocks of one standard
     normal per particle (or the range samples themselves under presampled=NOISE_MEASUREMENTS)."""
-    ctx = ctx or default_context()
-    opts = _with_layout(opts, layout)
-    mu = np.atleast_1d(_d(mu)).ravel(); C_ = mu.shape[0]; N = opts.n_particles
-    sigma = np.atleast_1d(_d(sigma)).ravel()
-    if sigma.shape != (C_,):
-        raise ValueError("sigma: expected %d values, got %s" % (C_, sigma.shape))
-    fixed = _blocks(fixed, C_, N, 2, opts.layout)
-    out = _blocks(target, C_, N, 2, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 1, opts.layout, points_ok=False)
-    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
-    dirs = None if dirs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dirs, dtype=np.int32), (C_,)))
-    _lib.check(_lib.load().rome_conv_point2point2range(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(sigma), _p(fixed),
-                                                      _p(noise), _p(out), _pi(st)), ctx.handle)
-    return (out, st) if want_status else out
+    return _conv("rome_conv_point2point2range", (1, 2, 2), opts, mu, [(sigma, ())], fixed, target, noise, ctx, layout, dirs=dirs,
+                 want_status=want_status)
 
 
 def conv_pose2point2range(opts, direction, mu, sigma, fixed, target, noise=None, want_status=False, ctx=None, layout=None):
     """C Pose2Point2Range convolutions (Range2D.jl:40-54), one direction per call: 0 solves the landmarks from the fixed poses, 1 the
     poses from the fixed landmarks -- (x, y) only, every particle's heading is returned unchanged."""
-    ctx = ctx or default_context()
-    opts = _with_layout(opts, layout)
-    mu = np.atleast_1d(_d(mu)).ravel(); C_ = mu.shape[0]; N = opts.n_particles
-    sigma = np.atleast_1d(_d(sigma)).ravel()
-    if sigma.shape != (C_,):
-        raise ValueError("sigma: expected %d values, got %s" % (C_, sigma.shape))
-    df, dt = (3, 2) if direction == 0 else (2, 3)
-    fixed = _blocks(fixed, C_, N, df, opts.layout)
-    out = _blocks(target, C_, N, dt, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 1, opts.layout, points_ok=False)
-    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
-    _lib.check(_lib.load().rome_conv_pose2point2range(ctx.handle, C.byref(opts), C_, int(direction), _p(mu), _p(sigma),
-                                                     _p(fixed), _p(noise), _p(out), _pi(st)), ctx.handle)
-    return (out, st) if want_status else out
+    return _conv("rome_conv_pose2point2range", (1, 3, 2), opts, mu, [(sigma, ())], fixed, target, noise, ctx, layout, direction=direction,
+                 want_status=want_status)
 
 
 def conv_pose2point2bearing(opts, direction, mu, sigma, fixed, target, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None):
@@ -480,47 +461,14 @@ def conv_pose2point2bearing(opts, direction, mu, sigma, fixed, target, noise=Non
     translation and is turned to the measured bearing).  mu / sigma (C,): the bearing belief (sigma < 0: Uniform(mu ± |sigma|));
     noise: C blocks of one standard normal per particle (or the bearings themselves under presampled=NOISE_MEASUREMENTS);
     nullhypo: the fraction of particles the factor does not apply to (opts.nullhypo when None)."""
-    ctx = ctx or default_context()
-    opts = _with_layout(opts, layout)
-    if nullhypo is not None:
-        opts = _lib.Opts.from_buffer_copy(opts)
-        opts.nullhypo = float(nullhypo)
     if direction not in (0, 1):
         raise ValueError("direction must be 0 (solve the landmark) or 1 (solve the pose)")
-    mu = np.atleast_1d(_d(mu)).ravel(); C_ = mu.shape[0]; N = opts.n_particles
-    sigma = np.atleast_1d(_d(sigma)).ravel()
-    if sigma.shape != (C_,):
-        raise ValueError("sigma: expected %d values, got %s" % (C_, sigma.shape))
-    df, dt = (3, 2) if direction == 0 else (2, 3)
-    fixed = _blocks(fixed, C_, N, df, opts.layout)
-    out = _blocks(target, C_, N, dt, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 1, opts.layout, points_ok=False)
-    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
-    _lib.check(_lib.load().rome_conv_pose2point2bearing(ctx.handle, C.byref(opts), C_, int(direction), _p(mu), _p(sigma),
-                                                       _p(fixed), _p(noise), _p(out), _pi(st)), ctx.handle)
-    return (out, st) if want_status else out
+    return _conv("rome_conv_pose2point2bearing", (1, 3, 2), opts, mu, [(sigma, ())], fixed, target, noise, ctx, layout, nullhypo,
+                 direction=direction, want_status=want_status)
 
 
 def conv_pose3pose3(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None):
-    ctx = ctx or default_context()
-    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
-    cov = _d(cov, (C_, 6, 6))
-    fixed = _blocks(fixed, C_, N, 6, opts.layout)
-    out = _blocks(target, C_, N, 6, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 6, opts.layout, points_ok=False)
-    dirs = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.int32)
-    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
-    _lib.check(_lib.load().rome_conv_pose3pose3(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(cov), _p(fixed),
-                                               _p(noise), _p(out), _pi(st)), ctx.handle)
-    return (out, st) if want_status else out
-
-
-def _with_nullhypo(opts, nullhypo):
-    if nullhypo is None:
-        return opts
-    o = _lib.Opts.from_buffer_copy(opts)
-    o.nullhypo = float(nullhypo)
-    return o
+    return _conv("rome_conv_pose3pose3", (6, 6, 6), opts, mu, [(cov, (6, 6))], fixed, target, noise, ctx, dirs=dirs, want_status=want_status)
 
 
 def conv_pose3pose3xyyaw(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None):
@@ -528,18 +476,8 @@ def conv_pose3pose3xyyaw(opts, mu, cov, fixed, target, dirs=None, noise=None, wa
     from q), fixed / target C Pose3 blocks, noise C blocks of three standard normals per particle (or the (x, y, θ) samples themselves under
     presampled=NOISE_MEASUREMENTS).  Solves the target's (x, y, ω_z); every particle's z, ω_x, ω_y is returned unchanged (bit for bit
     in the coordinate layouts).  nullhypo: the fraction of particles the factor does not apply to (opts.nullhypo when None)."""
-    ctx = ctx or default_context()
-    opts = _with_nullhypo(_with_layout(opts, layout), nullhypo)
-    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
-    mu = _d(mu, (C_, 3)); cov = _d(cov, (C_, 3, 3))
-    fixed = _blocks(fixed, C_, N, 6, opts.layout)
-    out = _blocks(target, C_, N, 6, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 3, opts.layout, points_ok=False)
-    dirs = None if dirs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dirs, dtype=np.int32), (C_,)))
-    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
-    _lib.check(_lib.load().rome_conv_pose3pose3xyyaw(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(cov), _p(fixed),
-                                                    _p(noise), _p(out), _pi(st)), ctx.handle)
-    return (out, st) if want_status else out
+    return _conv("rome_conv_pose3pose3xyyaw", (3, 6, 6), opts, mu, [(cov, (3, 3))], fixed, target, noise, ctx, layout, nullhypo, dirs=dirs,
+                 want_status=want_status)
 
 
 def conv_pose3pose3rotation(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None):
@@ -547,18 +485,8 @@ def conv_pose3pose3rotation(opts, mu, cov, fixed, target, dirs=None, noise=None,
     from q), fixed / target C Pose3 blocks, noise C blocks of three standard normals per particle (or the rotation-vector samples themselves
     under presampled=NOISE_MEASUREMENTS).  Solves the target's (ω_x, ω_y, ω_z); every particle's translation is returned unchanged (bit
     for bit in the coordinate layouts).  nullhypo: the fraction of particles the factor does not apply to (opts.nullhypo when None)."""
-    ctx = ctx or default_context()
-    opts = _with_nullhypo(_with_layout(opts, layout), nullhypo)
-    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
-    mu = _d(mu, (C_, 3)); cov = _d(cov, (C_, 3, 3))
-    fixed = _blocks(fixed, C_, N, 6, opts.layout)
-    out = _blocks(target, C_, N, 6, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 3, opts.layout, points_ok=False)
-    dirs = None if dirs is None else np.ascontiguousarray(np.broadcast_to(np.asarray(dirs, dtype=np.int32), (C_,)))
-    st = np.zeros((C_, N), dtype=np.int32) if want_status else None
-    _lib.check(_lib.load().rome_conv_pose3pose3rotation(ctx.handle, C.byref(opts), C_, _pi(dirs), _p(mu), _p(cov), _p(fixed),
-                                                       _p(noise), _p(out), _pi(st)), ctx.handle)
-    return (out, st) if want_status else out
+    return _conv("rome_conv_pose3pose3rotation", (3, 6, 6), opts, mu, [(cov, (3, 3))], fixed, target, noise, ctx, layout, nullhypo, dirs=dirs,
+                 want_status=want_status)
 
 
 def conv_priorpose3zrp(opts, mu, sigma_z, cov_rp, target, noise=None, ctx=None, layout=None, nullhypo=None):
@@ -566,14 +494,7 @@ def conv_priorpose3zrp(opts, mu, sigma_z, cov_rp, target, noise=None, ctx=None, 
     blocks -> the same blocks with coordinates 3, 4, 5 (z, ω_x, ω_y) replaced by the samples; x, y, ω_z unchanged (bit for bit in the
     coordinate layouts).  noise: C blocks of three standard normals per particle (or the three sample coordinates themselves under
     presampled=NOISE_MEASUREMENTS)."""
-    ctx = ctx or default_context()
-    opts = _with_nullhypo(_with_layout(opts, layout), nullhypo)
-    mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles
-    mu = _d(mu, (C_, 3)); sigma_z = _d(np.atleast_1d(_d(sigma_z)).ravel(), (C_,)); cov_rp = _d(cov_rp, (C_, 2, 2))
-    out = _blocks(target, C_, N, 6, opts.layout).copy()
-    noise = None if noise is None else _blocks(noise, C_, N, 3, opts.layout, points_ok=False)
-    _lib.check(_lib.load().rome_conv_priorpose3zrp(ctx.handle, C.byref(opts), C_, _p(mu), _p(sigma_z), _p(cov_rp), _p(noise), _p(out)), ctx.handle)
-    return out
+    return _conv("rome_conv_priorpose3zrp", (3, 6, 6), opts, mu, [(sigma_z, ()), (cov_rp, (2, 2))], None, target, noise, ctx, layout, nullhypo)
 
 
 def _sample_prior(fn, d, opts, mu, cov, noise, ctx):

@@ -157,33 +157,114 @@ int cholesky_one(int d, const double* cov, double* Lp) {
   return ROME_OK;
 }
 
+// ---- the factor families behind the convolution entries: everything their entry points differ in, said once.  A new family is a row
+// of kFamily, its exported functions (one call each, below) and its wrapper in api.py.
 enum FactorKind { kP2P2, kBR, kP3P3, kPrior2, kPrior3, kPriorPt2, kP2R, kPPR, kPB, kP3XYY, kP3ZRP, kP3ROT };
+enum NoiseForm {   // how the noise parameters arrive at a host-pointer entry, and what the device table L holds
+  kCov,            // cov [C][dz][dz] -> [C][dz (dz + 1) / 2], the row-packed lower Cholesky factor
+  kSigma,          // sigma [C][dz], passed through (sigma < 0 encodes Uniform(mu ± |sigma|); NaN is refused)
+  kZrp             // PriorPose3ZRP: sigma_z [C], cov_rp [C][2][2] -> [C][4] = [σ_z | packed 2x2 Cholesky of the roll / pitch covariance]
+};
+enum DirForm {     // how the direction arrives
+  kDirNone,        // the family has none
+  kDirRowsAny,     // a nullable per-row column, values unchecked: a row may be ROME_DIR_PRIOR
+  kDirRows01,      // a nullable per-row column of 0 / 1
+  kDirScalar       // one direction, 0 or 1, for the whole call (dir_all)
+};
+typedef hipError_t (*ConvLaunch)(const ConvArgs&, int solver, hipStream_t);
+struct Family {
+  int dz;                // dimension of the measurement
+  int d1, d2;            // ... of the factor's first and second variable: direction 0 fixes the first and solves the second, 1 swaps
+                         // them; d1 == 0: a sampler, nothing is fixed
+  NoiseForm noise;
+  DirForm dir;
+  bool mh;               // alt_var / hypo_w of a device table reach the kernel (false: the _dev entry refuses them)
+  bool fixed_is_target;  // a prior row that reads the target belief: the table's fixed block IS the target block (not read by the kernel)
+  ConvLaunch launch;
+};
+constexpr Family kFamily[] = {
+    /* kP2P2     */ {3, 3, 3, kCov, kDirRowsAny, true, false, launch_conv_pose2pose2},
+    /* kBR       */ {2, 3, 2, kSigma, kDirScalar, true, false, launch_conv_bearingrange},
+    /* kP3P3     */ {6, 6, 6, kCov, kDirRowsAny, true, false, launch_conv_pose3pose3},
+    /* kPrior2   */ {3, 0, 3, kCov, kDirNone, true, false, [](const ConvArgs& a, int, hipStream_t s) { return launch_sample_priorpose2(a, s); }},
+    /* kPrior3   */ {6, 0, 6, kCov, kDirNone, true, false, [](const ConvArgs& a, int, hipStream_t s) { return launch_sample_priorpose3(a, s); }},
+    /* kPriorPt2 */ {2, 0, 2, kCov, kDirNone, true, false, [](const ConvArgs& a, int, hipStream_t s) { return launch_sample_priorpoint2(a, s); }},
+    /* kP2R      */ {1, 2, 2, kSigma, kDirRows01, false, false, launch_conv_point2point2range},   // (a Point2 point IS its coordinates)
+    /* kPPR      */ {1, 3, 2, kSigma, kDirScalar, false, false, launch_conv_pose2point2range},
+    /* kPB       */ {1, 3, 2, kSigma, kDirScalar, false, false, launch_conv_pose2point2bearing},
+    /* kP3XYY    */ {3, 6, 6, kCov, kDirRows01, false, false, launch_conv_pose3pose3xyyaw},
+    /* kP3ZRP    */ {3, 6, 6, kZrp, kDirNone, false, true, [](const ConvArgs& a, int, hipStream_t s) { return launch_conv_priorpose3zrp(a, s); }},
+    /* kP3ROT    */ {3, 6, 6, kCov, kDirRows01, false, false, launch_conv_pose3pose3rotation},
+};
+static_assert(sizeof(kFamily) / sizeof(kFamily[0]) == kP3ROT + 1, "one row per FactorKind, in its order");
 
-// common host-pointer path: stage -> launch -> fetch
-int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const int32_t* dir, int dir_all,
-              int dz, int df, int dt, const double* mu, const double* Ltab /*[C][nL]*/, int nL,
-              const double* fixed, const double* noise, double* target_inout, int32_t* status,
-              const double* alt = nullptr /*C blocks of the other landmark candidate*/, const double* hypo_w = nullptr) {
-  const int N = o->n_particles;
-  const int lz = o->layout == ROME_LAYOUT_AOS_POINTS ? ROME_LAYOUT_AOS : o->layout;   // noise rows are measurement coordinates, never points
+// noise parameters of C rows -> the table L [C][nL] (kSigma: `prm` itself, nothing is packed); NaN or not positive definite: refused
+int pack_noise(const Family& f, int C, const double* prm, const double* prm2, std::vector<double>& L, const double** Ltab, int* nL) {
+  int rc;
+  switch (f.noise) {
+    case kCov:
+      *nL = f.dz * (f.dz + 1) / 2;
+      L.resize((size_t)C * *nL);
+      if ((rc = rome_cholesky_lower(f.dz, C, prm, L.data()))) return rc;
+      break;
+    case kSigma:
+      *nL = f.dz;
+      for (int i = 0; i < C * f.dz; ++i) if (prm[i] != prm[i]) return ROME_ERR_NOT_POSDEF;   // (sigma < 0 encodes Uniform(mu ± |sigma|))
+      *Ltab = prm;
+      return ROME_OK;
+    case kZrp:
+      *nL = 4;
+      L.resize((size_t)C * 4);
+      for (int i = 0; i < C; ++i) {
+        if (!(prm[i] >= 0.0)) return ROME_ERR_NOT_POSDEF;
+        L[4 * (size_t)i] = prm[i];
+        if ((rc = rome_cholesky_lower(2, 1, prm2 + 4 * (size_t)i, L.data() + 4 * (size_t)i + 1))) return rc;
+      }
+      break;
+  }
+  *Ltab = L.data();
+  return ROME_OK;
+}
+
+// THE host-pointer convolution: checks (in the order the header states) -> pack the noise parameters -> stage -> launch -> fetch.
+// dir: the per-row column of a kDirRows* family (nullable); dir_all: the scalar of a kDirScalar family and of every multihypo call.
+// prm / prm2: the noise parameters as f.noise says.  alt / hypo_w: the multihypo entries (mh), C blocks of the other candidate.
+int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const int32_t* dir, int dir_all, const double* mu,
+              const double* prm, const double* prm2, const double* fixed, const double* noise, double* target_inout, int32_t* status,
+              bool mh = false, const double* alt = nullptr, const double* hypo_w = nullptr) {
+  const Family& f = kFamily[kind];
+  const bool has_fixed = f.d1 != 0, one_dir = mh || f.dir == kDirScalar;
+  if (f.fixed_is_target) fixed = target_inout;   // (staged once more)
+  int rc = check_opts(o); if (rc) return rc;
+  if (!ctx || C < 0 || (one_dir && dir_all != 0 && dir_all != 1)) return ROME_ERR_INVALID_ARG;
+  if (C > 0 && (!mu || !prm || (f.noise == kZrp && !prm2) || (has_fixed && !fixed) || !target_inout || (mh && (!alt || !hypo_w)))) return ROME_ERR_INVALID_ARG;
+  if (C == 0) return ROME_OK;
+  if (f.dir == kDirRows01 && dir) for (int i = 0; i < C; ++i) if (dir[i] != 0 && dir[i] != 1) return ROME_ERR_INVALID_ARG;
+  if (mh) for (int i = 0; i < C; ++i) if (!(hypo_w[i] >= 0.0 && hypo_w[i] <= 1.0)) return ROME_ERR_INVALID_ARG;
+  // the host vectors that asynchronous copies read, then the guard that drains the stream before any return destroys them
+  std::vector<double> L, h_nh;
+  std::vector<int32_t> h_alt;
+  const double* Ltab; int nL;
+  if ((rc = pack_noise(f, C, prm, prm2, L, &Ltab, &nL))) return rc;
   ROME_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const bool has_fixed = (kind != kPrior2 && kind != kPrior3 && kind != kPriorPt2);
-  const bool mh = alt && hypo_w;   // multihypo: the alternative landmark blocks are appended behind the landmark-side array
+  DrainOnExit drain{s};
+
+  const int N = o->n_particles, dz = f.dz, df = dir_all == 1 ? f.d2 : f.d1, dt = dir_all == 1 ? f.d1 : f.d2;
+  const int lz = o->layout == ROME_LAYOUT_AOS_POINTS ? ROME_LAYOUT_AOS : o->layout;   // noise rows are measurement coordinates, never points
+  // multihypo: the alternative landmark blocks are appended behind the landmark-side array
   const size_t blk_f = (size_t)C * N * df, blk_t = (size_t)C * N * dt;
   const size_t n_fixed = has_fixed ? blk_f * ((mh && dir_all == 1) ? 2 : 1) : 0;
   const size_t n_target = has_fixed ? blk_t * ((mh && dir_all != 1) ? 2 : 1) : 0;
   const size_t n_noise = noise ? (size_t)C * N * dz : 0;
   double *h_fixed = nullptr, *h_target = nullptr, *h_noise = nullptr, *h_out = nullptr;
   void *d_mu, *d_L, *d_fixed = nullptr, *d_target = nullptr, *d_noise = nullptr, *d_out, *d_dir = nullptr, *d_status = nullptr;
-  int rc;
   if ((rc = ensure(ctx, 0, sizeof(double) * C * dz, &d_mu))) return rc;
   if ((rc = ensure(ctx, 1, sizeof(double) * C * nL, &d_L))) return rc;
   if ((rc = ensure(ctx, 2, sizeof(double) * blk_t, &d_out))) return rc;
   if ((rc = ensure_host(ctx, 3, sizeof(double) * blk_t, &h_out))) return rc;
   ROME_HIP(ctx, hipMemcpyAsync(d_mu, mu, sizeof(double) * C * dz, hipMemcpyHostToDevice, s));
   ROME_HIP(ctx, hipMemcpyAsync(d_L, Ltab, sizeof(double) * C * nL, hipMemcpyHostToDevice, s));
-  std::vector<int32_t> h_alt;
   if (has_fixed) {
     if ((rc = ensure_host(ctx, 0, sizeof(double) * n_fixed, &h_fixed))) return rc;
     if ((rc = ensure_host(ctx, 1, sizeof(double) * n_target, &h_target))) return rc;
@@ -219,10 +300,9 @@ int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const i
   }
   void* d_nh = nullptr;
   if (o->nullhypo > 0.0 && has_fixed) {
-    std::vector<double> h_nh((size_t)C, o->nullhypo);
+    h_nh.assign((size_t)C, o->nullhypo);
     if ((rc = ensure(ctx, 10, sizeof(double) * C, &d_nh))) return rc;
     ROME_HIP(ctx, hipMemcpyAsync(d_nh, h_nh.data(), sizeof(double) * C, hipMemcpyHostToDevice, s));
-    ROME_HIP(ctx, hipStreamSynchronize(s));  // h_nh goes out of scope
   }
   ConvArgs a;
   fill_args(a, o);
@@ -232,22 +312,7 @@ int host_conv(rome_ctx* ctx, const rome_opts* o, FactorKind kind, int C, const i
   a.mu = (const double*)d_mu; a.L = (const double*)d_L;
   a.bel_fixed = (const double*)d_fixed; a.bel_target = (const double*)d_target;
   a.noise = (const double*)d_noise; a.out = (double*)d_out; a.status = (int32_t*)d_status;
-  hipError_t e = hipSuccess;
-  switch (kind) {
-    case kP2P2: e = launch_conv_pose2pose2(a, o->solver, s); break;
-    case kBR: e = launch_conv_bearingrange(a, o->solver, s); break;
-    case kP3P3: e = launch_conv_pose3pose3(a, o->solver, s); break;
-    case kPrior2: e = launch_sample_priorpose2(a, s); break;
-    case kPrior3: e = launch_sample_priorpose3(a, s); break;
-    case kPriorPt2: e = launch_sample_priorpoint2(a, s); break;
-    case kP2R: e = launch_conv_point2point2range(a, o->solver, s); break;
-    case kPPR: e = launch_conv_pose2point2range(a, o->solver, s); break;
-    case kPB: e = launch_conv_pose2point2bearing(a, o->solver, s); break;
-    case kP3XYY: e = launch_conv_pose3pose3xyyaw(a, o->solver, s); break;
-    case kP3ZRP: e = launch_conv_priorpose3zrp(a, s); break;
-    case kP3ROT: e = launch_conv_pose3pose3rotation(a, o->solver, s); break;
-  }
-  ROME_HIP(ctx, e);
+  ROME_HIP(ctx, f.launch(a, o->solver, s));
   if (status) ROME_HIP(ctx, hipMemcpyAsync(status, d_status, sizeof(int32_t) * (size_t)C * N, hipMemcpyDeviceToHost, s));
   return fetch_blocks(ctx, o->layout, C, dt, N, (const double*)d_out, target_inout, h_out);   // (synchronises)
 }
@@ -387,214 +452,114 @@ int rome_cholesky_lower(int32_t d, int32_t n, const double* cov, double* L) {
   return ROME_OK;
 }
 
-/* ---- residual entry points ---- */
+/* ---- residual entry points: widths of the rows of z, a, b (0: none) and r, the kernel's kind, whether pose rows are native points ---- */
+struct ResidualEntry { int zw, aw, bw, rw, kind, pts; };
+static int host_residual(rome_ctx* c, const ResidualEntry& e, int32_t n, const double* z, const double* a, const double* b, double* r) {
+  const RowBuf in[3] = {{z, e.zw}, {a, e.aw}, {b, e.bw}};
+  return host_rows(c, n, in, e.bw ? 3 : 2, r, e.rw, [&](const double* dz, const double* da, const double* db, double* dr, hipStream_t s) {
+    return launch_residual(e.kind, e.pts, n, dz, da, db, dr, s); });
+}
 int rome_residual_pose2pose2(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
-  RowBuf in[3] = {{z, 3}, {p, 3}, {q, 3}};
-  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_pose2pose2(n, a, b, d, o, s); });
+  return host_residual(c, {3, 3, 3, 3, kResPose2Pose2, 0}, n, z, p, q, r);
 }
 int rome_residual_priorpose2(rome_ctx* c, int32_t n, const double* m, const double* p, double* r) {
-  RowBuf in[2] = {{m, 3}, {p, 3}};
-  return host_rows(c, n, in, 2, r, 3, [&](const double* a, const double* b, const double*, double* o, hipStream_t s) {
-    return launch_residual_priorpose2(n, a, b, o, s); });
+  return host_residual(c, {3, 3, 0, 3, kResPriorPose2, 0}, n, m, p, nullptr, r);
 }
 int rome_residual_pose2point2br(rome_ctx* c, int32_t n, const double* z, const double* p, const double* l, double* r) {
-  RowBuf in[3] = {{z, 2}, {p, 3}, {l, 2}};
-  return host_rows(c, n, in, 3, r, 2, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_bearingrange(n, a, b, 0, d, o, s); });
+  return host_residual(c, {2, 3, 2, 2, kResBearingRange, 0}, n, z, p, l, r);
 }
 int rome_residual_pose2point2br_pt(rome_ctx* c, int32_t n, const double* z, const double* p, const double* l, double* r) {
-  RowBuf in[3] = {{z, 2}, {p, 6}, {l, 2}};
-  return host_rows(c, n, in, 3, r, 2, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_bearingrange(n, a, b, 1, d, o, s); });
+  return host_residual(c, {2, 6, 2, 2, kResBearingRange, 1}, n, z, p, l, r);
 }
 int rome_residual_pose3pose3(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
-  RowBuf in[3] = {{z, 6}, {p, 6}, {q, 6}};
-  return host_rows(c, n, in, 3, r, 6, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_pose3pose3(n, a, b, d, 0, o, s); });
+  return host_residual(c, {6, 6, 6, 6, kResPose3Pose3, 0}, n, z, p, q, r);
 }
 int rome_residual_pose3pose3_pt(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
-  RowBuf in[3] = {{z, 6}, {p, 12}, {q, 12}};
-  return host_rows(c, n, in, 3, r, 6, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_pose3pose3(n, a, b, d, 1, o, s); });
+  return host_residual(c, {6, 12, 12, 6, kResPose3Pose3, 1}, n, z, p, q, r);
 }
 int rome_residual_pose3pose3xyyaw(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
-  RowBuf in[3] = {{z, 3}, {p, 6}, {q, 6}};
-  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_pose3pose3xyyaw(n, a, b, d, 0, o, s); });
+  return host_residual(c, {3, 6, 6, 3, kResPose3Pose3XYYaw, 0}, n, z, p, q, r);
 }
 int rome_residual_pose3pose3xyyaw_pt(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
-  RowBuf in[3] = {{z, 3}, {p, 12}, {q, 12}};
-  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_pose3pose3xyyaw(n, a, b, d, 1, o, s); });
+  return host_residual(c, {3, 12, 12, 3, kResPose3Pose3XYYaw, 1}, n, z, p, q, r);
 }
 int rome_residual_pose3pose3rotation(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
-  RowBuf in[3] = {{z, 3}, {p, 6}, {q, 6}};
-  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_pose3pose3rotation(n, a, b, d, 0, o, s); });
+  return host_residual(c, {3, 6, 6, 3, kResPose3Pose3Rotation, 0}, n, z, p, q, r);
 }
 int rome_residual_pose3pose3rotation_pt(rome_ctx* c, int32_t n, const double* z, const double* p, const double* q, double* r) {
-  RowBuf in[3] = {{z, 3}, {p, 12}, {q, 12}};
-  return host_rows(c, n, in, 3, r, 3, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_pose3pose3rotation(n, a, b, d, 1, o, s); });
+  return host_residual(c, {3, 12, 12, 3, kResPose3Pose3Rotation, 1}, n, z, p, q, r);
 }
 int rome_residual_priorpose3(rome_ctx* c, int32_t n, const double* m, const double* p, double* r) {
-  RowBuf in[2] = {{m, 6}, {p, 6}};
-  return host_rows(c, n, in, 2, r, 6, [&](const double* a, const double* b, const double*, double* o, hipStream_t s) {
-    return launch_residual_priorpose3(n, a, b, o, s); });
+  return host_residual(c, {6, 6, 0, 6, kResPriorPose3, 0}, n, m, p, nullptr, r);
 }
 int rome_residual_point2point2range(rome_ctx* c, int32_t n, const double* z, const double* xi, const double* lm, double* r) {
-  RowBuf in[3] = {{z, 1}, {xi, 2}, {lm, 2}};
-  return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_range(n, a, b, 2, d, o, s); });
+  return host_residual(c, {1, 2, 2, 1, kResPoint2Point2Range, 0}, n, z, xi, lm, r);
 }
 int rome_residual_pose2point2range(rome_ctx* c, int32_t n, const double* z, const double* p, const double* lm, double* r) {
-  RowBuf in[3] = {{z, 1}, {p, 3}, {lm, 2}};
-  return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_range(n, a, b, 3, d, o, s); });
+  return host_residual(c, {1, 3, 2, 1, kResPose2Point2Range, 0}, n, z, p, lm, r);
 }
 int rome_residual_pose2point2bearing(rome_ctx* c, int32_t n, const double* z, const double* p, const double* l, double* r) {
-  RowBuf in[3] = {{z, 1}, {p, 3}, {l, 2}};
-  return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_bearing(n, a, b, 0, d, o, s); });
+  return host_residual(c, {1, 3, 2, 1, kResBearing, 0}, n, z, p, l, r);
 }
 int rome_residual_pose2point2bearing_pt(rome_ctx* c, int32_t n, const double* z, const double* p, const double* l, double* r) {
-  RowBuf in[3] = {{z, 1}, {p, 6}, {l, 2}};
-  return host_rows(c, n, in, 3, r, 1, [&](const double* a, const double* b, const double* d, double* o, hipStream_t s) {
-    return launch_residual_bearing(n, a, b, 1, d, o, s); });
+  return host_residual(c, {1, 6, 2, 1, kResBearing, 1}, n, z, p, l, r);
 }
 
-/* ---- host-pointer convolutions ---- */
+/* ---- host-pointer convolutions: host_conv(kind, C, dir column, dir scalar, mu, noise parameters, fixed, noise, target, status) ---- */
 int rome_conv_pose2pose2(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* cov,
                          const double* fixed, const double* noise, double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !cov || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  std::vector<double> L((size_t)C * 6);
-  if ((rc = rome_cholesky_lower(3, C, cov, L.data()))) return rc;
-  return host_conv(c, o, kP2P2, C, dir, 0, 3, 3, 3, mu, L.data(), 6, fixed, noise, target_inout, status);
+  return host_conv(c, o, kP2P2, C, dir, 0, mu, cov, nullptr, fixed, noise, target_inout, status);
 }
 int rome_conv_pose2pose2_mh(rome_ctx* c, const rome_opts* o, int32_t C, int32_t dir, const double* mu, const double* cov,
                             const double* fixed, const double* alt, const double* hypo_w, const double* noise,
                             double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (dir != 0 && dir != 1) || (C > 0 && (!mu || !cov || !fixed || !alt || !hypo_w || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  for (int i = 0; i < C; ++i) if (!(hypo_w[i] >= 0.0 && hypo_w[i] <= 1.0)) return ROME_ERR_INVALID_ARG;
-  std::vector<double> L((size_t)C * 6);
-  if ((rc = rome_cholesky_lower(3, C, cov, L.data()))) return rc;
-  return host_conv(c, o, kP2P2, C, nullptr, dir, 3, 3, 3, mu, L.data(), 6, fixed, noise, target_inout, status, alt, hypo_w);
+  return host_conv(c, o, kP2P2, C, nullptr, dir, mu, cov, nullptr, fixed, noise, target_inout, status, true, alt, hypo_w);
 }
 int rome_conv_pose2point2br(rome_ctx* c, const rome_opts* o, int32_t C, int32_t dir, const double* mu, const double* sigma,
                             const double* fixed, const double* noise, double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (dir != 0 && dir != 1) || (C > 0 && (!mu || !sigma || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  for (int i = 0; i < 2 * C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;  /* sigma < 0 encodes Uniform(mu ± |sigma|) */
-  return host_conv(c, o, kBR, C, nullptr, dir, 2, dir == 0 ? 3 : 2, dir == 0 ? 2 : 3, mu, sigma, 2, fixed, noise, target_inout, status);
+  return host_conv(c, o, kBR, C, nullptr, dir, mu, sigma, nullptr, fixed, noise, target_inout, status);
 }
 int rome_conv_pose2point2br_mh(rome_ctx* c, const rome_opts* o, int32_t C, int32_t dir, const double* mu, const double* sigma,
                                const double* fixed, const double* alt, const double* hypo_w, const double* noise,
                                double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (dir != 0 && dir != 1) || (C > 0 && (!mu || !sigma || !fixed || !alt || !hypo_w || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  for (int i = 0; i < 2 * C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;
-  for (int i = 0; i < C; ++i) if (!(hypo_w[i] >= 0.0 && hypo_w[i] <= 1.0)) return ROME_ERR_INVALID_ARG;
-  return host_conv(c, o, kBR, C, nullptr, dir, 2, dir == 0 ? 3 : 2, dir == 0 ? 2 : 3, mu, sigma, 2, fixed, noise, target_inout, status, alt, hypo_w);
+  return host_conv(c, o, kBR, C, nullptr, dir, mu, sigma, nullptr, fixed, noise, target_inout, status, true, alt, hypo_w);
 }
 int rome_conv_pose3pose3(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* cov,
                          const double* fixed, const double* noise, double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !cov || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  std::vector<double> L((size_t)C * 21);
-  if ((rc = rome_cholesky_lower(6, C, cov, L.data()))) return rc;
-  return host_conv(c, o, kP3P3, C, dir, 0, 6, 6, 6, mu, L.data(), 21, fixed, noise, target_inout, status);
+  return host_conv(c, o, kP3P3, C, dir, 0, mu, cov, nullptr, fixed, noise, target_inout, status);
 }
 int rome_conv_point2point2range(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* sigma,
                                 const double* fixed, const double* noise, double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !sigma || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  if (dir) for (int i = 0; i < C; ++i) if (dir[i] != 0 && dir[i] != 1) return ROME_ERR_INVALID_ARG;
-  for (int i = 0; i < C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;  /* sigma < 0 encodes Uniform(mu ± |sigma|) */
-  return host_conv(c, o, kP2R, C, dir, 0, 1, 2, 2, mu, sigma, 1, fixed, noise, target_inout, status);   // (a Point2 point IS its coordinates: no conversion in any layout)
+  return host_conv(c, o, kP2R, C, dir, 0, mu, sigma, nullptr, fixed, noise, target_inout, status);
 }
 int rome_conv_pose2point2range(rome_ctx* c, const rome_opts* o, int32_t C, int32_t dir, const double* mu, const double* sigma,
                                const double* fixed, const double* noise, double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (dir != 0 && dir != 1) || (C > 0 && (!mu || !sigma || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  for (int i = 0; i < C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;
-  return host_conv(c, o, kPPR, C, nullptr, dir, 1, dir == 0 ? 3 : 2, dir == 0 ? 2 : 3, mu, sigma, 1, fixed, noise, target_inout, status);
+  return host_conv(c, o, kPPR, C, nullptr, dir, mu, sigma, nullptr, fixed, noise, target_inout, status);
 }
 int rome_conv_pose2point2bearing(rome_ctx* c, const rome_opts* o, int32_t C, int32_t dir, const double* mu, const double* sigma,
                                  const double* fixed, const double* noise, double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (dir != 0 && dir != 1) || (C > 0 && (!mu || !sigma || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  for (int i = 0; i < C; ++i) if (sigma[i] != sigma[i]) return ROME_ERR_NOT_POSDEF;  /* sigma < 0 encodes Uniform(mu ± |sigma|) */
-  return host_conv(c, o, kPB, C, nullptr, dir, 1, dir == 0 ? 3 : 2, dir == 0 ? 2 : 3, mu, sigma, 1, fixed, noise, target_inout, status);
+  return host_conv(c, o, kPB, C, nullptr, dir, mu, sigma, nullptr, fixed, noise, target_inout, status);
 }
 int rome_conv_pose3pose3xyyaw(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* cov,
                               const double* fixed, const double* noise, double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !cov || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  if (dir) for (int i = 0; i < C; ++i) if (dir[i] != 0 && dir[i] != 1) return ROME_ERR_INVALID_ARG;
-  std::vector<double> L((size_t)C * 6);
-  if ((rc = rome_cholesky_lower(3, C, cov, L.data()))) return rc;
-  return host_conv(c, o, kP3XYY, C, dir, 0, 3, 6, 6, mu, L.data(), 6, fixed, noise, target_inout, status);
+  return host_conv(c, o, kP3XYY, C, dir, 0, mu, cov, nullptr, fixed, noise, target_inout, status);
 }
 int rome_conv_pose3pose3rotation(rome_ctx* c, const rome_opts* o, int32_t C, const int32_t* dir, const double* mu, const double* cov,
                                 const double* fixed, const double* noise, double* target_inout, int32_t* status) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !cov || !fixed || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  if (dir) for (int i = 0; i < C; ++i) if (dir[i] != 0 && dir[i] != 1) return ROME_ERR_INVALID_ARG;
-  std::vector<double> L((size_t)C * 6);
-  if ((rc = rome_cholesky_lower(3, C, cov, L.data()))) return rc;
-  return host_conv(c, o, kP3ROT, C, dir, 0, 3, 6, 6, mu, L.data(), 6, fixed, noise, target_inout, status);
+  return host_conv(c, o, kP3ROT, C, dir, 0, mu, cov, nullptr, fixed, noise, target_inout, status);
 }
 int rome_conv_priorpose3zrp(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* sigma_z, const double* cov_rp,
                             const double* noise, double* target_inout) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !sigma_z || !cov_rp || !target_inout))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  std::vector<double> L((size_t)C * 4);   // [σ_z, packed 2x2 Cholesky of the roll / pitch covariance]
-  for (int i = 0; i < C; ++i) {
-    if (!(sigma_z[i] >= 0.0)) return ROME_ERR_NOT_POSDEF;
-    L[4 * (size_t)i] = sigma_z[i];
-    if ((rc = rome_cholesky_lower(2, 1, cov_rp + 4 * (size_t)i, L.data() + 4 * (size_t)i + 1))) return rc;
-  }
-  // a prior row that reads the target belief: the table's fixed block IS the target block (staged once more; the kernel does not read it)
-  return host_conv(c, o, kP3ZRP, C, nullptr, 0, 3, 6, 6, mu, L.data(), 4, target_inout, noise, target_inout, nullptr);
+  return host_conv(c, o, kP3ZRP, C, nullptr, 0, mu, sigma_z, cov_rp, nullptr, noise, target_inout, nullptr);
 }
 int rome_sample_priorpose2(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* cov, const double* noise, double* out) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !cov || !out))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  std::vector<double> L((size_t)C * 6);
-  if ((rc = rome_cholesky_lower(3, C, cov, L.data()))) return rc;
-  return host_conv(c, o, kPrior2, C, nullptr, 0, 3, 3, 3, mu, L.data(), 6, nullptr, noise, out, nullptr);
+  return host_conv(c, o, kPrior2, C, nullptr, 0, mu, cov, nullptr, nullptr, noise, out, nullptr);
 }
 int rome_sample_priorpose3(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* cov, const double* noise, double* out) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !cov || !out))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  std::vector<double> L((size_t)C * 21);
-  if ((rc = rome_cholesky_lower(6, C, cov, L.data()))) return rc;
-  return host_conv(c, o, kPrior3, C, nullptr, 0, 6, 6, 6, mu, L.data(), 21, nullptr, noise, out, nullptr);
+  return host_conv(c, o, kPrior3, C, nullptr, 0, mu, cov, nullptr, nullptr, noise, out, nullptr);
 }
-
 int rome_sample_priorpoint2(rome_ctx* c, const rome_opts* o, int32_t C, const double* mu, const double* cov, const double* noise, double* out) {
-  int rc = check_opts(o); if (rc) return rc;
-  if (!c || C < 0 || (C > 0 && (!mu || !cov || !out))) return ROME_ERR_INVALID_ARG;
-  if (C == 0) return ROME_OK;
-  std::vector<double> L((size_t)C * 3);
-  if ((rc = rome_cholesky_lower(2, C, cov, L.data()))) return rc;
-  return host_conv(c, o, kPriorPt2, C, nullptr, 0, 2, 2, 2, mu, L.data(), 3, nullptr, noise, out, nullptr);   // (a Point2 point IS its coordinates: no conversion in any layout)
+  return host_conv(c, o, kPriorPt2, C, nullptr, 0, mu, cov, nullptr, nullptr, noise, out, nullptr);
 }
 
 /* ---- device-pointer convolutions ---- */
@@ -607,66 +572,35 @@ static int dev_common(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t, b
   ROME_BIND(c);
   return ROME_OK;
 }
-// one device-pointer family: common checks + device binding -> arguments -> launch on the context's stream
-typedef hipError_t (*ConvLaunch)(const ConvArgs&, int solver, hipStream_t);
-static int dev_launch(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t, bool need_beliefs, ConvLaunch launch) {
-  int rc = dev_common(c, o, t, need_beliefs); if (rc) return rc;
+// THE device-pointer convolution: the family's refusals (kFamily) -> common checks + device binding -> arguments -> launch on the
+// context's stream
+static int dev_conv(rome_ctx* c, const rome_opts* o, FactorKind kind, const rome_conv_dev* t) {
+  const Family& f = kFamily[kind];
+  if (t) {
+    const bool dir01 = t->dir_all == 0 || t->dir_all == 1;
+    if (!f.mh && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;                          // no multihypo on this family
+    if (f.dir == kDirScalar && (t->dir || !dir01)) return ROME_ERR_INVALID_ARG;                   // one direction per call
+    if (f.dir == kDirRows01 && !t->dir && !t->rows4 && !dir01) return ROME_ERR_INVALID_ARG;       // a direction column, or 0 / 1 for all rows
+  }
+  int rc = dev_common(c, o, t, f.d1 != 0 && !f.fixed_is_target); if (rc) return rc;
+  if (f.fixed_is_target && t->n_conv > 0 && !t->bel_target) return ROME_ERR_INVALID_ARG;   // the target belief is read: the proposal is its own particle, partly replaced
   ConvArgs a; args_from_dev(a, o, t);
-  ROME_HIP(c, launch(a, o->solver, c->stream));
+  if (f.fixed_is_target) a.bel_fixed = a.bel_target;   // (fixed = target in every row; the block is not read)
+  ROME_HIP(c, f.launch(a, o->solver, c->stream));
   return ROME_OK;
 }
-static bool one_dir(const rome_conv_dev* t) { return t->dir == nullptr && (t->dir_all == 0 || t->dir_all == 1); }   // dir_all families
-int rome_conv_pose2pose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  return dev_launch(c, o, t, true, launch_conv_pose2pose2);
-}
-int rome_conv_pose2point2br_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  if (t && !one_dir(t)) return ROME_ERR_INVALID_ARG;
-  return dev_launch(c, o, t, true, launch_conv_bearingrange);
-}
-int rome_conv_point2point2range_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;   // no multihypo on range factors
-  if (t && !t->dir && !t->rows4 && t->dir_all != 0 && t->dir_all != 1) return ROME_ERR_INVALID_ARG;
-  return dev_launch(c, o, t, true, launch_conv_point2point2range);
-}
-int rome_conv_pose2point2range_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  if (t && (t->alt_var || t->hypo_w || !one_dir(t))) return ROME_ERR_INVALID_ARG;
-  return dev_launch(c, o, t, true, launch_conv_pose2point2range);
-}
-int rome_conv_pose2point2bearing_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  if (t && (t->alt_var || t->hypo_w || !one_dir(t))) return ROME_ERR_INVALID_ARG;   // no multihypo on bearing-only factors
-  return dev_launch(c, o, t, true, launch_conv_pose2point2bearing);
-}
-int rome_conv_pose3pose3_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  return dev_launch(c, o, t, true, launch_conv_pose3pose3);
-}
-int rome_conv_pose3pose3xyyaw_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;   // no multihypo on the partial Pose3 factors
-  if (t && !t->dir && !t->rows4 && t->dir_all != 0 && t->dir_all != 1) return ROME_ERR_INVALID_ARG;
-  return dev_launch(c, o, t, true, launch_conv_pose3pose3xyyaw);
-}
-int rome_conv_pose3pose3rotation_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;   // no multihypo on the partial Pose3 factors
-  if (t && !t->dir && !t->rows4 && t->dir_all != 0 && t->dir_all != 1) return ROME_ERR_INVALID_ARG;
-  return dev_launch(c, o, t, true, launch_conv_pose3pose3rotation);
-}
-int rome_conv_priorpose3zrp_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  if (t && (t->alt_var || t->hypo_w)) return ROME_ERR_INVALID_ARG;
-  int rc = dev_common(c, o, t, false); if (rc) return rc;
-  if (t->n_conv > 0 && !t->bel_target) return ROME_ERR_INVALID_ARG;   // the target belief is read: the proposal is its own particle, partly replaced
-  ConvArgs a; args_from_dev(a, o, t);
-  a.bel_fixed = a.bel_target;   // (fixed = target in every row; the block is not read)
-  ROME_HIP(c, launch_conv_priorpose3zrp(a, c->stream));
-  return ROME_OK;
-}
-int rome_sample_priorpose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  return dev_launch(c, o, t, false, [](const ConvArgs& a, int, hipStream_t s) { return launch_sample_priorpose2(a, s); });
-}
-int rome_sample_priorpose3_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  return dev_launch(c, o, t, false, [](const ConvArgs& a, int, hipStream_t s) { return launch_sample_priorpose3(a, s); });
-}
-int rome_sample_priorpoint2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) {
-  return dev_launch(c, o, t, false, [](const ConvArgs& a, int, hipStream_t s) { return launch_sample_priorpoint2(a, s); });
-}
+int rome_conv_pose2pose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kP2P2, t); }
+int rome_conv_pose2point2br_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kBR, t); }
+int rome_conv_point2point2range_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kP2R, t); }
+int rome_conv_pose2point2range_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kPPR, t); }
+int rome_conv_pose2point2bearing_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kPB, t); }
+int rome_conv_pose3pose3_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kP3P3, t); }
+int rome_conv_pose3pose3xyyaw_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kP3XYY, t); }
+int rome_conv_pose3pose3rotation_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kP3ROT, t); }
+int rome_conv_priorpose3zrp_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kP3ZRP, t); }
+int rome_sample_priorpose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kPrior2, t); }
+int rome_sample_priorpose3_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kPrior3, t); }
+int rome_sample_priorpoint2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* t) { return dev_conv(c, o, kPriorPt2, t); }
 int rome_sweep_pose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* p2p2, const rome_conv_dev* br1, const rome_conv_dev* br0,
                          const uint64_t* family_stream_offset) {
   int rc = check_opts(o); if (rc) return rc;

@@ -63,15 +63,11 @@ hipError_t launch_sample_priorpose2(const ConvArgs& a, hipStream_t s);
 hipError_t launch_sample_priorpose3(const ConvArgs& a, hipStream_t s);
 hipError_t launch_sample_priorpoint2(const ConvArgs& a, hipStream_t s);
 
-hipError_t launch_residual_pose2pose2(int n, const double* z, const double* p, const double* q, double* r, hipStream_t s);
-hipError_t launch_residual_priorpose2(int n, const double* m, const double* p, double* r, hipStream_t s);
-hipError_t launch_residual_bearingrange(int n, const double* z, const double* p, int p_is_point, const double* l, double* r, hipStream_t s);
-hipError_t launch_residual_pose3pose3(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s);
-hipError_t launch_residual_priorpose3(int n, const double* m, const double* p, double* r, hipStream_t s);
-hipError_t launch_residual_pose3pose3xyyaw(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s);
-hipError_t launch_residual_pose3pose3rotation(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s);
-hipError_t launch_residual_range(int n, const double* z, const double* x, int dx, const double* l, double* r, hipStream_t s);
-hipError_t launch_residual_bearing(int n, const double* z, const double* p, int p_is_point, const double* l, double* r, hipStream_t s);
+// residual-only rows (the KAT entry points): r[i] = residual of kind `kind` at (z[i], a[i], b[i]); b is not read by the priors; pts: the
+// pose rows of a / b are native points (Pose2: 6, Pose3: 12 doubles), not coordinates -- the kinds that read a heading or a rotation only
+enum { kResPose2Pose2, kResPriorPose2, kResBearingRange, kResBearing, kResPose3Pose3, kResPose3Pose3XYYaw, kResPose3Pose3Rotation,
+       kResPriorPose3, kResPoint2Point2Range, kResPose2Point2Range };
+hipError_t launch_residual(int kind, int pts, int n, const double* z, const double* a, const double* b, double* r, hipStream_t s);
 
 hipError_t launch_points_to_coords(int n, int dim, const double* pts, double* c, hipStream_t s);
 hipError_t launch_coords_to_points(int n, int dim, const double* c, double* pts, hipStream_t s);

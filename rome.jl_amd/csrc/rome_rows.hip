@@ -45,111 +45,119 @@ __global__ void __launch_bounds__(256) k_sample_prior(const ConvArgs a) {
   }
 }
 
-// ---- residual-only kernels (rows of AoS coordinates), used by the KAT entry points
-__global__ void k_residual_pose2pose2(int n, const double* z, const double* p, const double* q, double* r) {
+// ---- residual-only kernel (rows of AoS coordinates), used by the KAT entry points: thread i reads row i of the measurements z and of
+// the variables a, b (b absent: a prior), evaluates R on them and writes row i of r.  Each R states its row widths and evaluates one row.
+template <class R>
+__global__ void k_residual(int n, const double* z, const double* a, const double* b, double* r) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const Se2 P = se2_from_coords(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
-  const Se2 Q = se2_from_coords(q[3 * i], q[3 * i + 1], q[3 * i + 2]);
-  double sz, cz; fast_sincos(z[3 * i + 2], &sz, &cz);
-  double rr[3];
-  residual_pose2pose2(z[3 * i], z[3 * i + 1], cz, sz, P, Q, rr);
-  r[3 * i] = rr[0]; r[3 * i + 1] = rr[1]; r[3 * i + 2] = rr[2];
-}
-__global__ void k_residual_priorpose2(int n, const double* m, const double* p, double* r) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const Se2 M = se2_from_coords(m[3 * i], m[3 * i + 1], m[3 * i + 2]);
-  const Se2 P = se2_from_coords(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
-  double rr[3];
-  residual_priorpose2(M, P, rr);
-  r[3 * i] = rr[0]; r[3 * i + 1] = rr[1]; r[3 * i + 2] = rr[2];
-}
-// p_is_point: 0 -> p rows are coords (x,y,θ); 1 -> native points [tx,ty,R11,R21,R12,R22]
-__global__ void k_residual_bearingrange(int n, const double* z, const double* p, int p_is_point, const double* l, double* r) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Se2 P;
-  if (p_is_point) { P.x = p[6 * i]; P.y = p[6 * i + 1]; P.c = p[6 * i + 2]; P.s = p[6 * i + 3]; }
-  else P = se2_from_coords(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
-  double rr[2];
-  residual_bearingrange(z[2 * i], z[2 * i + 1], P, l[2 * i], l[2 * i + 1], rr);
-  r[2 * i] = rr[0]; r[2 * i + 1] = rr[1];
-}
-// bearing-only residual; p rows as k_residual_bearingrange
-__global__ void k_residual_bearing(int n, const double* z, const double* p, int p_is_point, const double* l, double* r) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Se2 P;
-  if (p_is_point) { P.x = p[6 * i]; P.y = p[6 * i + 1]; P.c = p[6 * i + 2]; P.s = p[6 * i + 3]; }
-  else P = se2_from_coords(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
-  r[i] = residual_bearing(z[i], P, l[2 * i], l[2 * i + 1]);
-}
-// p,q rows are native points (12 doubles: t, R col-major) when pts != 0, else coords (6)
-__global__ void k_residual_pose3pose3(int n, const double* z, const double* p, const double* q, int pts, double* r) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Se3 P, Q;
-  if (pts) {
+  double rr[R::RW];
+  R::eval(z + (size_t)R::ZW * i, a + (size_t)R::AW * i, b + (size_t)R::BW * i, rr);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { P.t[k] = p[12 * i + k]; Q.t[k] = q[12 * i + k]; }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { P.R[k] = p[12 * i + 3 + k]; Q.R[k] = q[12 * i + 3 + k]; }
-  } else { se3_from_coords(p + 6 * i, P); se3_from_coords(q + 6 * i, Q); }
-  double Z[9], rr[6];
-  so3_exp(z + 6 * i + 3, Z);
-  residual_pose3pose3(z + 6 * i, Z, P, Q, rr);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) r[6 * i + k] = rr[k];
-}
-// Pose3Pose3XYYaw (PartialPose3.jl:116-136): z rows (x, y, θ); p, q rows as k_residual_pose3pose3 (only t_x, t_y and R's first column are read)
-__global__ void k_residual_pose3pose3xyyaw(int n, const double* z, const double* p, const double* q, int pts, double* r) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Se2 P, Q;
-  if (pts) {
-    P = se2_of_pose3(p[12 * i], p[12 * i + 1], p[12 * i + 3], p[12 * i + 4]);
-    Q = se2_of_pose3(q[12 * i], q[12 * i + 1], q[12 * i + 3], q[12 * i + 4]);
-  } else {
-    double c[3], u[3];
-    so3_col1_dz(p[6 * i + 3], p[6 * i + 4], p[6 * i + 5], c, u); P = se2_of_pose3(p[6 * i], p[6 * i + 1], c[0], c[1]);
-    so3_col1_dz(q[6 * i + 3], q[6 * i + 4], q[6 * i + 5], c, u); Q = se2_of_pose3(q[6 * i], q[6 * i + 1], c[0], c[1]);
-  }
-  double sz, cz; fast_sincos(z[3 * i + 2], &sz, &cz);
-  double rr[3];
-  residual_pose3pose3xyyaw(z[3 * i], z[3 * i + 1], cz, sz, P, Q, rr);
-  r[3 * i] = rr[0]; r[3 * i + 1] = rr[1]; r[3 * i + 2] = rr[2];
-}
-// Pose3Pose3Rotation (PartialPose3.jl:212-227): z rows are rotation vectors (3); p, q rows as k_residual_pose3pose3 (only the rotations are read)
-__global__ void k_residual_pose3pose3rotation(int n, const double* z, const double* p, const double* q, int pts, double* r) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double Rp[9], Rq[9];
-  if (pts) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) { Rp[k] = p[12 * i + 3 + k]; Rq[k] = q[12 * i + 3 + k]; }
-  } else { so3_exp(p + 6 * i + 3, Rp); so3_exp(q + 6 * i + 3, Rq); }
-  double rr[3];
-  residual_pose3pose3rotation(z + 3 * i, Rp, Rq, rr);
-  r[3 * i] = rr[0]; r[3 * i + 1] = rr[1]; r[3 * i + 2] = rr[2];
-}
-__global__ void k_residual_priorpose3(int n, const double* m, const double* p, double* r) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  Se3 M, P;
-  se3_from_coords(m + 6 * i, M); se3_from_coords(p + 6 * i, P);
-  double rr[6];
-  residual_priorpose3(M, P, rr);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) r[6 * i + k] = rr[k];
+  for (int k = 0; k < R::RW; ++k) r[(size_t)R::RW * i + k] = rr[k];
 }
 
-// range residuals r = ρ − ‖lm − x‖: x rows are Point2 (dx = 2) or Pose2 coordinates (dx = 3, the heading is not read)
-__global__ void k_residual_range(int n, const double* z, const double* x, int dx, const double* l, double* r) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  r[i] = z[i] - range_norm(l[2 * i] - x[(size_t)dx * i], l[2 * i + 1] - x[(size_t)dx * i + 1]);
+// a pose row: coordinates (Pose2 (x, y, θ); Pose3 (t, ω)), or with PTS the native point (Pose2 [tx,ty,R11,R21,R12,R22]; Pose3 [t, R col-major])
+template <bool PTS>
+__device__ inline Se2 pose2_row(const double* p) {
+  if constexpr (PTS) { Se2 P; P.x = p[0]; P.y = p[1]; P.c = p[2]; P.s = p[3]; return P; }
+  else return se2_from_coords(p[0], p[1], p[2]);
 }
+template <bool PTS>
+__device__ inline void pose3_row(const double* p, Se3& P) {
+  if constexpr (PTS) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) P.t[k] = p[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) P.R[k] = p[3 + k];
+  } else se3_from_coords(p, P);
+}
+
+struct ResPose2Pose2 {
+  static constexpr int ZW = 3, AW = 3, BW = 3, RW = 3;
+  static __device__ void eval(const double* z, const double* p, const double* q, double (&r)[RW]) {
+    const Se2 P = pose2_row<false>(p), Q = pose2_row<false>(q);
+    double sz, cz; fast_sincos(z[2], &sz, &cz);
+    residual_pose2pose2(z[0], z[1], cz, sz, P, Q, r);
+  }
+};
+struct ResPriorPose2 {
+  static constexpr int ZW = 3, AW = 3, BW = 0, RW = 3;
+  static __device__ void eval(const double* m, const double* p, const double*, double (&r)[RW]) {
+    residual_priorpose2(pose2_row<false>(m), pose2_row<false>(p), r);
+  }
+};
+template <bool PTS>
+struct ResBearingRange {
+  static constexpr int ZW = 2, AW = PTS ? 6 : 3, BW = 2, RW = 2;
+  static __device__ void eval(const double* z, const double* p, const double* l, double (&r)[RW]) {
+    residual_bearingrange(z[0], z[1], pose2_row<PTS>(p), l[0], l[1], r);
+  }
+};
+template <bool PTS>
+struct ResBearing {
+  static constexpr int ZW = 1, AW = PTS ? 6 : 3, BW = 2, RW = 1;
+  static __device__ void eval(const double* z, const double* p, const double* l, double (&r)[RW]) {
+    r[0] = residual_bearing(z[0], pose2_row<PTS>(p), l[0], l[1]);
+  }
+};
+template <bool PTS>
+struct ResPose3Pose3 {
+  static constexpr int ZW = 6, AW = PTS ? 12 : 6, BW = AW, RW = 6;
+  static __device__ void eval(const double* z, const double* p, const double* q, double (&r)[RW]) {
+    Se3 P, Q;
+    pose3_row<PTS>(p, P); pose3_row<PTS>(q, Q);
+    double Z[9];
+    so3_exp(z + 3, Z);
+    residual_pose3pose3(z, Z, P, Q, r);
+  }
+};
+// Pose3Pose3XYYaw (PartialPose3.jl:116-136): z rows (x, y, θ); of p and q only t_x, t_y and R's first column are read
+template <bool PTS>
+struct ResPose3Pose3XYYaw {
+  static constexpr int ZW = 3, AW = PTS ? 12 : 6, BW = AW, RW = 3;
+  static __device__ Se2 project(const double* p) {
+    if constexpr (PTS) return se2_of_pose3(p[0], p[1], p[3], p[4]);
+    else { double c[3], u[3]; so3_col1_dz(p[3], p[4], p[5], c, u); return se2_of_pose3(p[0], p[1], c[0], c[1]); }
+  }
+  static __device__ void eval(const double* z, const double* p, const double* q, double (&r)[RW]) {
+    const Se2 P = project(p), Q = project(q);
+    double sz, cz; fast_sincos(z[2], &sz, &cz);
+    residual_pose3pose3xyyaw(z[0], z[1], cz, sz, P, Q, r);
+  }
+};
+// Pose3Pose3Rotation (PartialPose3.jl:212-227): z rows are rotation vectors; of p and q only the rotations are read
+template <bool PTS>
+struct ResPose3Pose3Rotation {
+  static constexpr int ZW = 3, AW = PTS ? 12 : 6, BW = AW, RW = 3;
+  static __device__ void rotation(const double* p, double* R) {
+    if constexpr (PTS) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) R[k] = p[3 + k];
+    } else so3_exp(p + 3, R);
+  }
+  static __device__ void eval(const double* z, const double* p, const double* q, double (&r)[RW]) {
+    double Rp[9], Rq[9];
+    rotation(p, Rp); rotation(q, Rq);
+    residual_pose3pose3rotation(z, Rp, Rq, r);
+  }
+};
+struct ResPriorPose3 {
+  static constexpr int ZW = 6, AW = 6, BW = 0, RW = 6;
+  static __device__ void eval(const double* m, const double* p, const double*, double (&r)[RW]) {
+    Se3 M, P;
+    pose3_row<false>(m, M); pose3_row<false>(p, P);
+    residual_priorpose3(M, P, r);
+  }
+};
+// range residuals r = ρ − ‖lm − x‖: x rows are Point2 (DX = 2) or Pose2 coordinates (DX = 3, the heading is not read)
+template <int DX>
+struct ResRange {
+  static constexpr int ZW = 1, AW = DX, BW = 2, RW = 1;
+  static __device__ void eval(const double* z, const double* x, const double* l, double (&r)[RW]) {
+    r[0] = z[0] - range_norm(l[0] - x[0], l[1] - x[1]);
+  }
+};
 
 // ---- native point layouts <-> coordinates (rows): Pose2 [tx,ty,R11,R21,R12,R22] <-> (x,y,θ);
 //      Pose3 [t(3), R col-major(9)] <-> (t, ω).  vee(log(ϵ,p)) / exp_ϵ(hat c) of src/variables/VariableTypes.jl:35,47.
@@ -208,32 +216,22 @@ static hipError_t launch_rows(void (*k)(int, P...), int n, hipStream_t s, A... a
   if (n > 0) hipLaunchKernelGGL(k, dim3((n + 255) / 256), dim3(256), 0, s, n, args...);
   return hipGetLastError();
 }
-hipError_t launch_residual_pose2pose2(int n, const double* z, const double* p, const double* q, double* r, hipStream_t s) {
-  return launch_rows(k_residual_pose2pose2, n, s, z, p, q, r);
-}
-hipError_t launch_residual_priorpose2(int n, const double* m, const double* p, double* r, hipStream_t s) {
-  return launch_rows(k_residual_priorpose2, n, s, m, p, r);
-}
-hipError_t launch_residual_bearingrange(int n, const double* z, const double* p, int p_is_point, const double* l, double* r, hipStream_t s) {
-  return launch_rows(k_residual_bearingrange, n, s, z, p, p_is_point, l, r);
-}
-hipError_t launch_residual_pose3pose3(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s) {
-  return launch_rows(k_residual_pose3pose3, n, s, z, p, q, pts, r);
-}
-hipError_t launch_residual_pose3pose3xyyaw(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s) {
-  return launch_rows(k_residual_pose3pose3xyyaw, n, s, z, p, q, pts, r);
-}
-hipError_t launch_residual_pose3pose3rotation(int n, const double* z, const double* p, const double* q, int pts, double* r, hipStream_t s) {
-  return launch_rows(k_residual_pose3pose3rotation, n, s, z, p, q, pts, r);
-}
-hipError_t launch_residual_priorpose3(int n, const double* m, const double* p, double* r, hipStream_t s) {
-  return launch_rows(k_residual_priorpose3, n, s, m, p, r);
-}
-hipError_t launch_residual_range(int n, const double* z, const double* x, int dx, const double* l, double* r, hipStream_t s) {
-  return launch_rows(k_residual_range, n, s, z, x, dx, l, r);
-}
-hipError_t launch_residual_bearing(int n, const double* z, const double* p, int p_is_point, const double* l, double* r, hipStream_t s) {
-  return launch_rows(k_residual_bearing, n, s, z, p, p_is_point, l, r);
+// kind: kRes* (rome_kernels.h); pts: the pose rows are native points (the kinds that read a pose's rotation or heading)
+hipError_t launch_residual(int kind, int pts, int n, const double* z, const double* a, const double* b, double* r, hipStream_t s) {
+  auto go = [&](auto R) { return launch_rows(k_residual<decltype(R)>, n, s, z, a, b, r); };
+  switch (kind) {
+    case kResPose2Pose2: if (!pts) return go(ResPose2Pose2{}); break;
+    case kResPriorPose2: if (!pts) return go(ResPriorPose2{}); break;
+    case kResBearingRange: return pts ? go(ResBearingRange<true>{}) : go(ResBearingRange<false>{});
+    case kResBearing: return pts ? go(ResBearing<true>{}) : go(ResBearing<false>{});
+    case kResPose3Pose3: return pts ? go(ResPose3Pose3<true>{}) : go(ResPose3Pose3<false>{});
+    case kResPose3Pose3XYYaw: return pts ? go(ResPose3Pose3XYYaw<true>{}) : go(ResPose3Pose3XYYaw<false>{});
+    case kResPose3Pose3Rotation: return pts ? go(ResPose3Pose3Rotation<true>{}) : go(ResPose3Pose3Rotation<false>{});
+    case kResPriorPose3: if (!pts) return go(ResPriorPose3{}); break;
+    case kResPoint2Point2Range: if (!pts) return go(ResRange<2>{}); break;
+    case kResPose2Point2Range: if (!pts) return go(ResRange<3>{}); break;
+  }
+  return hipErrorInvalidValue;
 }
 hipError_t launch_points_to_coords(int n, int dim, const double* pts, double* c, hipStream_t s) {
   return launch_rows(k_points_to_coords, n, s, dim, pts, c);

@@ -1,8 +1,14 @@
 """The entry points of include/rome_mi355.h that no other test calls by name: the device-pointer twins of the parametric linearisation and of
 getKDEMax, the thin device-memory helpers a caller without a HIP binding uses (the Julia shim), the device count and the HIP error
 accessors.  A `_dev` entry must return what its host-pointer twin returns, bit for bit -- the twin IS the same kernel behind a
-staging copy."""
+staging copy.
+
+The convolution, sampler and residual entries, which other tests call for what they compute, are held here to the bytes they returned
+before they shared one body (tests/golden/entry_bits.json), and to the return code of every input that is invalid in exactly one way."""
 import ctypes as C
+import importlib.util
+import json
+import os
 
 import numpy as np
 import pytest
@@ -100,3 +106,149 @@ def test_linearize_dev_equals_the_host_entry(env, kind):
         assert lib.rome_linearize_dev(ctx.handle, kind, F, ptr(d_mu), ptr(d_W), ptr(d_xa), None, ptr(d_r), ptr(d_Ja), ptr(d_Jb)) == _lib.ERR_INVALID_ARG
     assert lib.rome_linearize_dev(ctx.handle, 6, F, ptr(d_mu), ptr(d_W), ptr(d_xa), ptr(d_xb), ptr(d_r), ptr(d_Ja), ptr(d_Jb)) == _lib.ERR_INVALID_ARG
     assert lib.rome_linearize_dev(ctx.handle, kind, 0, ptr(d_mu), ptr(d_W), ptr(d_xa), ptr(d_xb), ptr(d_r), ptr(d_Ja), ptr(d_Jb)) == _lib.OK   # nothing to do
+
+
+# ---- the convolution, sampler and residual entries: recorded bits, and one table of refusals
+@pytest.fixture(scope="module")
+def EB():
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("entry_bits", os.path.join(root, "scripts", "entry_bits.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    m.ROOT = root
+    return m
+
+
+def test_entry_output_bits_are_the_recorded_ones(env, EB):
+    """tests/golden/entry_bits.json was written by scripts/entry_bits.py on an MI355X from the library of commit 74c2229, the last one
+    in which every host-pointer entry had a body of its own (profiles/entries_one_body.md); two recordings were equal."""
+    with open(os.path.join(EB.ROOT, "tests", "golden", "entry_bits.json")) as f:
+        want = json.load(f)["sha256"]
+    got = EB.hashes()
+    assert sorted(got) == sorted(want) and len(got) == len(list(EB.conv_cases())) + len(EB.RESIDUAL) * len(EB.RESIDUAL_N)
+    diff = [k for k in got if got[k] != want[k]]
+    assert not diff, diff
+
+
+def _host_call(EB, _lib, lib, ctx, entry, change):
+    """A valid call of a host-pointer convolution / sampler entry (C = 1, N = 10, SoA) with `change` = {argument: value} applied.
+    Arguments by name: ctx, opts, C, dir, mu, prm0, prm1, fixed, alt, hypo_w, noise, out, status; n_particles changes the options.
+    -> (return code, whether the output and status arrays are untouched)"""
+    of = EB.MULTIHYPO.get(entry)
+    dz, d1, d2, form, dirform, has_status = EB.CONV[of or entry]
+    N, rng = 10, np.random.default_rng(1)
+    o = _lib.default_opts(_lib.SOLVER_NEWTON, n_particles=change.get("n_particles", N))
+    prm = {"cov": [0.01 * np.eye(dz)[None]], "sigma": [np.full((1, dz), 0.1)], "zrp": [np.full(1, 0.1), 0.01 * np.eye(2)[None]]}[form]
+    arrays = {"mu": np.full((1, dz), 2.0), "prm0": prm[0], "out": rng.normal(size=(1, d2, N)), "hypo_w": np.array([0.5]),
+              "fixed": rng.normal(size=(1, max(d1, 1), N)), "alt": rng.normal(size=(1, d2, N)), "status": np.full((1, N), -7, np.int32)}
+    if len(prm) > 1:
+        arrays["prm1"] = prm[1]
+    arrays.update({k: v for k, v in change.items() if isinstance(v, np.ndarray)})
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    before = arrays["out"].copy()
+    names = ["ctx", "opts", "C"] + (["dir"] if dirform or of else []) + ["mu", "prm0"] + (["prm1"] if len(prm) > 1 else []) + \
+        (["fixed"] if d1 and form != "zrp" else []) + (["alt", "hypo_w"] if of else []) + ["noise", "out"] + (["status"] if has_status else [])
+    value = {"ctx": ctx.handle, "opts": C.byref(o), "C": 1, "noise": None, "dir": None if dirform == "rows" and not of else 0}
+    for k, a in arrays.items():
+        value[k] = a.ctypes.data_as(C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))
+    value.update({k: v for k, v in change.items() if not isinstance(v, np.ndarray) and k != "n_particles"})
+    assert set(change) <= set(names) | {"n_particles"}, (entry, change)
+    rc = getattr(lib, entry)(*[value[k] for k in names])
+    return rc, np.array_equal(arrays["out"], before) and (arrays["status"] == -7).all()
+
+
+def test_host_entries_refuse_each_invalid_input_with_the_documented_code(env, EB):
+    """One thing wrong per call; every refusal returns before anything is staged or launched (the output arrays stay untouched)."""
+    torch, R, _lib, api, lib, ctx = env
+    INV, POSDEF, TOO_MANY = _lib.ERR_INVALID_ARG, _lib.ERR_NOT_POSDEF, _lib.ERR_UNSUPPORTED_N
+    nan, two = np.array([[np.nan]]), np.array([2], np.int32)
+    for entry in list(EB.CONV) + list(EB.MULTIHYPO):
+        of = EB.MULTIHYPO.get(entry)
+        dz, d1, d2, form, dirform, has_status = EB.CONV[of or entry]
+        cases = [({"opts": None}, INV), ({"ctx": None}, INV), ({"C": -1}, INV), ({"C": 0}, _lib.OK), ({"n_particles": _lib.MAX_PARTICLES + 1}, TOO_MANY),
+                 ({"mu": None}, INV), ({"prm0": None}, INV), ({"out": None}, INV)]
+        if d1 and form != "zrp":
+            cases.append(({"fixed": None}, INV))
+        if of:
+            cases += [({"alt": None}, INV), ({"hypo_w": None}, INV), ({"hypo_w": np.array([1.5])}, INV), ({"hypo_w": np.array([-0.1])}, INV),
+                      ({"hypo_w": np.array([np.nan])}, INV)]
+        if dirform == "scalar" or of:
+            cases += [({"dir": 2}, INV), ({"dir": -1}, INV)]
+        elif dirform == "rows" and entry not in ("rome_conv_pose2pose2", "rome_conv_pose3pose3"):
+            cases.append(({"dir": two}, INV))
+        if form == "cov":
+            cases += [({"prm0": -np.eye(dz)[None]}, POSDEF), ({"prm0": np.full((1, dz, dz), np.nan)}, POSDEF)]
+        elif form == "sigma":
+            cases.append(({"prm0": np.full((1, dz), np.nan)}, POSDEF))
+        else:
+            cases += [({"prm1": None}, INV), ({"prm0": np.array([np.nan])}, POSDEF), ({"prm1": -np.eye(2)[None]}, POSDEF)]
+        for change, want in cases:
+            rc, untouched = _host_call(EB, _lib, lib, ctx, entry, change)
+            assert rc == want and untouched, (entry, change, rc)
+    for entry in ("rome_conv_pose2pose2", "rome_conv_pose3pose3"):     # their rows may be ROME_DIR_PRIOR (2): the column is not range-checked
+        rc, untouched = _host_call(EB, _lib, lib, ctx, entry, {"dir": two})
+        assert rc == _lib.OK and not untouched, entry
+
+
+def test_residual_entries_refuse_each_invalid_input(env, EB):
+    torch, R, _lib, api, lib, ctx = env
+    PD = C.POINTER(C.c_double)
+    for entry, (zw, aw, bw, rw) in EB.RESIDUAL.items():
+        ins = [np.ones((1, w)) for w in (zw, aw, bw) if w]
+        r = np.full((1, rw), -7.0)
+        ptrs = [a.ctypes.data_as(PD) for a in ins + [r]]
+        fn = getattr(lib, entry)
+        assert fn(None, 1, *ptrs) == _lib.ERR_INVALID_ARG, entry
+        assert fn(ctx.handle, -1, *ptrs) == _lib.ERR_INVALID_ARG, entry
+        for k in range(len(ptrs)):
+            assert fn(ctx.handle, 1, *[None if j == k else p for j, p in enumerate(ptrs)]) == _lib.ERR_INVALID_ARG, (entry, k)
+        assert fn(ctx.handle, 0, *ptrs) == _lib.OK and (r == -7.0).all(), entry      # nothing to do, nothing touched
+
+
+# _dev entry -> (alt_var / hypo_w are passed on, the direction rule, the beliefs that are required)
+DEV_ENTRIES = {
+    "rome_conv_pose2pose2_dev": (True, None, "both"), "rome_conv_pose2point2br_dev": (True, "scalar", "both"),
+    "rome_conv_pose3pose3_dev": (True, None, "both"), "rome_conv_point2point2range_dev": (False, "rows", "both"),
+    "rome_conv_pose2point2range_dev": (False, "scalar", "both"), "rome_conv_pose2point2bearing_dev": (False, "scalar", "both"),
+    "rome_conv_pose3pose3xyyaw_dev": (False, "rows", "both"), "rome_conv_pose3pose3rotation_dev": (False, "rows", "both"),
+    "rome_conv_priorpose3zrp_dev": (False, None, "target"), "rome_sample_priorpose2_dev": (True, None, None),
+    "rome_sample_priorpose3_dev": (True, None, None), "rome_sample_priorpoint2_dev": (True, None, None),
+}
+
+
+def test_dev_entries_refuse_each_invalid_table_before_any_launch(env):
+    """One thing wrong per call.  Every pointer of the table is the same zeroed device buffer, large enough for one row of any family, and
+    it is still all zeros afterwards: nothing was launched."""
+    torch, R, _lib, api, lib, ctx = env
+    INV = _lib.ERR_INVALID_ARG
+    buf = torch.zeros(4096, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    p = buf.data_ptr()
+    o = _lib.default_opts(_lib.SOLVER_NEWTON, n_particles=10)
+    big = _lib.default_opts(_lib.SOLVER_NEWTON, n_particles=_lib.MAX_PARTICLES + 1)
+
+    def table(**change):
+        t = _lib.ConvDev(n_conv=1, dir_all=0, mu=p, L=p, bel_fixed=p, bel_target=p, out=p)
+        for k, v in change.items():
+            setattr(t, k, v)
+        return t
+
+    for entry, (mh, dir_rule, beliefs) in DEV_ENTRIES.items():
+        fn = getattr(lib, entry)
+        assert fn(ctx.handle, None, C.byref(table())) == INV, entry
+        assert fn(None, C.byref(o), C.byref(table())) == INV, entry
+        assert fn(ctx.handle, C.byref(o), None) == INV, entry
+        assert fn(ctx.handle, C.byref(big), C.byref(table())) == _lib.ERR_UNSUPPORTED_N, entry
+        cases = [dict(n_conv=-1), dict(mu=None), dict(L=None), dict(out=None), dict(mirror_out=p, n_mirror=5)]
+        cases += {"both": [dict(bel_fixed=None), dict(bel_target=None)], "target": [dict(bel_target=None)], None: []}[beliefs]
+        if not mh:
+            cases += [dict(alt_var=p), dict(hypo_w=p)]
+        if dir_rule == "scalar":
+            cases += [dict(dir=p), dict(dir_all=2), dict(dir_all=-1)]
+        if dir_rule == "rows":
+            cases += [dict(dir_all=2)]
+        for change in cases:
+            assert fn(ctx.handle, C.byref(o), C.byref(table(**change))) == INV, (entry, change)
+        assert fn(ctx.handle, C.byref(o), C.byref(table(n_conv=0))) == _lib.OK, entry   # no rows: nothing to launch
+    ctx.synchronize()
+    assert not buf.any()

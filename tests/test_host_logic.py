@@ -548,3 +548,92 @@ def test_entropy_uniforms_law_independent_of_the_oracle_definition():
     # the jitter a particle receives over the three default cycles: the sum of three uniforms per coordinate (Irwin-Hall): variance 3/12
     s3 = (U[:, :, :3, :3] - 0.5).sum(axis=2).ravel()
     assert abs(s3.var() - 0.25) < 4e-3 and abs(stats.skew(s3)) < 0.02
+
+
+# ------------------------------------------------------------------ api.py: the public surface of the entry wrappers
+API_SIGNATURES = {   # str(inspect.signature(f)), written down from commit 74c2229 (every wrapper a body of its own)
+    "calcFactorResidualTemporary": "(factor, vartypes, meas, points, ctx=None)",
+    "conv_point2point2range": "(opts, mu, sigma, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None)",
+    "conv_pose2point2bearing": "(opts, direction, mu, sigma, fixed, target, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None)",
+    "conv_pose2point2br": "(opts, direction, mu, sigma, fixed, target, noise=None, want_status=False, ctx=None, alt=None, hypo_w=None)",
+    "conv_pose2point2range": "(opts, direction, mu, sigma, fixed, target, noise=None, want_status=False, ctx=None, layout=None)",
+    "conv_pose2pose2": "(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, alt=None, hypo_w=None)",
+    "conv_pose3pose3": "(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None)",
+    "conv_pose3pose3rotation": "(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None)",
+    "conv_pose3pose3xyyaw": "(opts, mu, cov, fixed, target, dirs=None, noise=None, want_status=False, ctx=None, layout=None, nullhypo=None)",
+    "conv_priorpose3zrp": "(opts, mu, sigma_z, cov_rp, target, noise=None, ctx=None, layout=None, nullhypo=None)",
+    "residual_point2point2range": "(z, xi, lm, ctx=None)",
+    "residual_pose2point2bearing": "(z, p, l, ctx=None)",
+    "residual_pose2point2bearing_pt": "(z, p_pt, l, ctx=None)",
+    "residual_pose2point2br": "(z, p, l, ctx=None)",
+    "residual_pose2point2br_pt": "(z, p_pt, l, ctx=None)",
+    "residual_pose2point2range": "(z, p, lm, ctx=None)",
+    "residual_pose2pose2": "(z, p, q, ctx=None)",
+    "residual_pose3pose3": "(z, p, q, ctx=None)",
+    "residual_pose3pose3_pt": "(z, p_pt, q_pt, ctx=None)",
+    "residual_pose3pose3rotation": "(z, p, q, ctx=None)",
+    "residual_pose3pose3rotation_pt": "(z, p_pt, q_pt, ctx=None)",
+    "residual_pose3pose3xyyaw": "(z, p, q, ctx=None)",
+    "residual_pose3pose3xyyaw_pt": "(z, p_pt, q_pt, ctx=None)",
+    "residual_priorpose2": "(m, p, ctx=None)",
+    "residual_priorpose3": "(m, p, ctx=None)",
+    "sample_priorpoint2": "(opts, mu, cov, noise=None, ctx=None)",
+    "sample_priorpose2": "(opts, mu, cov, noise=None, ctx=None)",
+    "sample_priorpose3": "(opts, mu, cov, noise=None, ctx=None)",
+}
+
+
+def test_api_wrappers_keep_their_signatures():
+    import inspect
+    from rome_jl_amd import api
+    public = {n: str(inspect.signature(f)) for n, f in vars(api).items() if inspect.isfunction(f) and f.__module__ == api.__name__ and
+              (n.startswith(("conv_", "sample_", "residual_")) or n == "calcFactorResidualTemporary")}
+    assert public == API_SIGNATURES
+
+
+def test_meas_coords_accepts_the_coordinates_and_the_tangent_container_of_every_factor():
+    """m = (1, 2, ..., n) for every accepted length n of every factor type -> the coordinates, written down from commit 74c2229; any other
+    length, and a type without a residual, raise."""
+    from rome_jl_amd import api
+    want = {
+        R.Pose2Pose2: {3: [1, 2, 3], 6: [1, 2, 4]}, R.PriorPose2: {3: [1, 2, 3], 6: [1, 2, 4]},
+        R.Pose3Pose3XYYaw: {3: [1, 2, 3], 6: [1, 2, 4]},
+        R.Pose2Point2BearingRange: {2: [1, 2], 5: [2, 5]},
+        R.Point2Point2Range: {1: [1]}, R.Pose2Point2Range: {1: [1]},
+        R.Pose2Point2Bearing: {1: [1], 4: [2]},
+        R.Pose3Pose3Rotation: {3: [1, 2, 3], 9: [6, 7, 2]},
+        R.Pose3Pose3: {6: [1, 2, 3, 4, 5, 6], 12: [1, 2, 3, 9, 10, 5]}, R.PriorPose3: {6: [1, 2, 3, 4, 5, 6], 12: [1, 2, 3, 9, 10, 5]},
+    }
+    for cls, by_len in want.items():
+        f = object.__new__(cls)                     # (only the type is read)
+        sub = object.__new__(type("Sub" + cls.__name__, (cls,), {}))
+        for n in range(0, 14):
+            m = np.arange(1.0, n + 1.0)
+            if n in by_len:
+                for factor in (f, sub):
+                    got = api._meas_coords(factor, m.reshape(1, -1))
+                    assert got.dtype == np.float64 and got.tolist() == by_len[n], (cls.__name__, n)
+            else:
+                with pytest.raises(ValueError, match="unexpected length %d for %s" % (n, cls.__name__)):
+                    api._meas_coords(f, m)
+    with pytest.raises(ValueError, match="PriorPoint2"):
+        api._meas_coords(object.__new__(R.PriorPoint2), [1.0, 2.0])
+
+
+def test_conv_wrappers_refuse_a_direction_column_of_the_wrong_length():
+    """conv_pose2pose2 and conv_pose3pose3 used to hand `dirs` to the library as it came, which then read C values from it: at commit
+    74c2229 this test fails (the call reaches the library, which refuses the NULL context here).  Now every wrapper repeats one value
+    for all rows and raises for an array that is not one value per row, before the library is called."""
+    from types import SimpleNamespace
+    from rome_jl_amd import api
+    nowhere = SimpleNamespace(handle=None)          # a library call with it returns ROME_ERR_INVALID_ARG -> RomeError
+    N, o = 4, R.make_opts(N=4)
+    for fn, d in ((api.conv_pose2pose2, 3), (api.conv_pose3pose3, 6)):
+        mu, cov, bel = np.zeros((3, d)), np.tile(np.eye(d), (3, 1, 1)), np.zeros((3, d, N))
+        for dirs in ([0, 1], [0, 1, 0, 1], np.zeros((3, 1), np.int32)):
+            with pytest.raises(ValueError):
+                fn(o, mu, cov, bel, bel, dirs=dirs, ctx=nowhere)
+        for dirs in (None, 1, [0, 1, 0]):            # accepted: these reach the library
+            with pytest.raises(R.RomeError) as e:
+                fn(o, mu, cov, bel, bel, dirs=dirs, ctx=nowhere)
+            assert e.value.code == R._lib.ERR_INVALID_ARG
