@@ -673,6 +673,32 @@ int rome_linearize_dev(rome_ctx*, int32_t kind, int32_t F, const double* mu, con
  *   dim 2 (Point2), 3 (Pose2) or 6 (Pose3, coordinates [t; rotation vector], N <= 256). */
 int rome_belief_stats_dev(rome_ctx*, int32_t dim, int32_t V, int32_t N, const double* bel, double* mean, double* std);
 int rome_belief_stats(rome_ctx*, int32_t dim, int32_t V, int32_t N, const double* bel, double* mean, double* std); /* host pointers */
+/* rome_mmd*: maximum mean discrepancy between two particle sets of one variable type -- ⚠AMP `mmd(M, a, b; bw)`, the number the
+ *   reference accepts a belief by (test/testPose3Pose3NH.jl:141-145 `mmd(M, X1ptst, X1pts, bw=[0.001]) < 0.6`,
+ *   test/testBasicPose2Conv.jl:56 `< 0.001`).  AMP is not vendored; this is the biased V-statistic of MMD² (not square-rooted):
+ *       k(x, y) = exp(-sigma * sum_c (scale_c * diff_c(x, y))^2)
+ *       S_aa = sum_{i,j} k(a_i, a_j) (all ordered pairs, i = j included),  S_ab = sum_{i,j} k(a_i, b_j),  S_bb likewise
+ *       mmd  = S_aa/Na^2 - 2 S_ab/(Na Nb) + S_bb/Nb^2
+ *   diff is the tangent difference of the variable type, as in rome_belief_stats and the products: dim 2 Point2 (x - y), dim 3 Pose2
+ *   (heading difference wrapped to (-pi, pi]), dim 6 Pose3 (t_x - t_y, Log(R_y^T R_x)), coordinates [t; rotation vector].  sigma is
+ *   AMP's bw[1] (its default 0.001); scale is a HOST array of dim entries >= 0 in both entries (NULL = ones; 0 drops a coordinate).
+ *   NOT CHECKED against AMP: whether it weighs a rotation by the geodesic angle (scale 1 on the rotation coordinates, the default
+ *   here) or by Manifolds.jl's Frobenius norm of the tangent (scale sqrt(2) on them); on the reference's sample files
+ *   (test/testdata) the two give 1.07351 and 1.07340.
+ *   Pair p of P compares block a_rows[p] of a ([.][dim][Na] SoA) with block b_rows[p] of b ([.][dim][Nb]); a NULL row table means
+ *   block p; a and b may be the same array and rows may repeat.  out [P]; sums [P][3] = (S_aa, S_ab, S_bb) or NULL.  The bits of out[p]
+ *   depend on pair p's inputs alone.  1 <= Na, Nb <= ROME_MAX_PARTICLES_MMD (beyond: ROME_ERR_UNSUPPORTED_N, nothing launched); a
+ *   negative or non-finite sigma / scale entry is ROME_ERR_INVALID_ARG; P = 0 is a no-op.  rome_mmd_dev neither synchronises nor
+ *   allocates (it can be captured into a graph).  rome_mmd: host pointers, blocks in `layout` (ROME_LAYOUT_*); n_a_blocks /
+ *   n_b_blocks = blocks in a / b, which the row tables (or P, without them) must stay inside.  rome_mmd converts and uploads ALL
+ *   n_a_blocks + n_b_blocks blocks, whatever the row tables name, and a and b separately even when they are one array: its cost
+ *   scales with n_*_blocks, not with P (pass only the blocks that are compared, or keep the sets on the device: rome_mmd_dev). */
+#define ROME_MAX_PARTICLES_MMD 512
+int rome_mmd_dev(rome_ctx*, int32_t dim, int32_t P, int32_t Na, const double* a, const int32_t* a_rows,
+                 int32_t Nb, const double* b, const int32_t* b_rows, const double* scale, double sigma, double* out, double* sums);
+int rome_mmd(rome_ctx*, int32_t layout, int32_t dim, int32_t P, int32_t Na, int32_t n_a_blocks, const double* a, const int32_t* a_rows,
+             int32_t Nb, int32_t n_b_blocks, const double* b, const int32_t* b_rows, const double* scale, double sigma, double* out,
+             double* sums);                                                                                       /* host pointers */
 /* rome_kde_bandwidth*: the bandwidth `manikde!` selects for a belief, one per coordinate, by leave-one-out likelihood
  *   cross-validation of a 1-D Gaussian KDE (golden section on the bracket of KDE.jl's ksize "lcv"; coordinate k is circular
  *   -- differences wrapped -- when bit k of circular_mask is set: Pose2 = 0b100).  bel [V][dim][N] -> bw [V][dim], dim 1..6,

@@ -223,6 +223,57 @@ def belief_stats(bel, ctx=None):
     return mean, sd
 
 
+def _mmd_call(a, b, bw, scale, want_sums, ctx):
+    """a (Va, dim, Na), b (Vb, dim, Nb) host SoA blocks, pair v = (a[v], b[v]) -> out (V,), sums (V, 3) or None: one rome_mmd call"""
+    ctx = ctx or default_context()
+    (V, d, Na), (Vb, db, Nb) = a.shape, b.shape
+    if Vb != V or db != d:
+        raise ValueError("mmd: the two sets must have the same number of blocks and coordinates, got %s and %s" % (a.shape, b.shape))
+    sc = None if scale is None else _d(scale, (d,))
+    out = np.empty(V)
+    sums = np.empty((V, 3)) if want_sums else None
+    _lib.check(_lib.load().rome_mmd(ctx.handle, _lib.LAYOUT_SOA, d, V, Na, V, _p(a), None, Nb, V, _p(b), None, _p(sc), float(bw), _p(out), _p(sums)),
+               ctx.handle)
+    return out, sums
+
+
+def mmd(a, b, bw=0.001, scale=None, return_sums=False, ctx=None):
+    """⚠AMP `mmd(M, a, b; bw=[bw])`: maximum mean discrepancy (biased V-statistic of MMD², include/rome_mi355.h rome_mmd) between two
+    particle sets of one variable type.  a (dim, Na) and b (dim, Nb) host coordinates -> a float; a (V, dim, Na) and b (V, dim, Nb) ->
+    (V,) values, block v against block v.  dim 2: Point2, 3: Pose2, 6: Pose3 coordinates (t, ω).  scale: (dim,) per-coordinate weights,
+    None = ones.  return_sums: also the three kernel sums (S_aa, S_ab, S_bb) per pair."""
+    a, b = _d(a), _d(b)
+    if a.ndim != b.ndim or a.ndim not in (2, 3):
+        raise ValueError("mmd: expected two (dim, N) or two (V, dim, N) arrays, got %s and %s" % (a.shape, b.shape))
+    single = a.ndim == 2
+    out, sums = _mmd_call(a[None] if single else a, b[None] if single else b, bw, scale, return_sums, ctx)
+    if single:
+        return (float(out[0]), sums[0]) if return_sums else float(out[0])
+    return (out, sums) if return_sums else out
+
+
+def mmdBeliefs(fg_a, fg_b, labels=None, bw=0.001, scale=None, ctx=None):
+    """{label: mmd(belief of label in fg_a, belief of label in fg_b)} for `labels` (default: every variable of fg_a), one library call
+    per variable type.  scale: None, (dim,) weights, or {vartype: (dim,) weights}.  A label that is missing or uninitialised in either
+    graph raises, by name."""
+    labels = list(fg_a.ls() if labels is None else labels)
+    by_type = {}
+    for l in labels:
+        for name, fg in (("first", fg_a), ("second", fg_b)):
+            if not fg.exists(l) or not fg.isInitialized(l):
+                raise ValueError("mmdBeliefs: variable %s is not initialised in the %s graph" % (l, name))
+        if fg_a.variables[l] is not fg_b.variables[l]:
+            raise ValueError("mmdBeliefs: variable %s has different types in the two graphs" % l)
+        by_type.setdefault(fg_a.variables[l], []).append(l)
+    res = {}
+    for vt, ls in by_type.items():
+        a = np.stack([fg_a.getVal(l) for l in ls])
+        b = np.stack([fg_b.getVal(l) for l in ls])
+        out, _ = _mmd_call(_d(a), _d(b), bw, scale.get(vt) if isinstance(scale, dict) else scale, False, ctx)
+        res.update(zip(ls, out.tolist()))
+    return {l: res[l] for l in labels}
+
+
 def kde_bandwidth(bel, circular_mask=None, tol_euclid=0.0, tol_circular=0.0, ctx=None):
     """bel (V, dim, N) host array -> (V, dim) bandwidths as `manikde!` selects them (leave-one-out likelihood
     cross-validation per coordinate), via rome_kde_bandwidth.  circular_mask: bit k set = coordinate k is an angle

@@ -87,6 +87,63 @@ int rome_belief_stats(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const doub
   ROME_HIP(c, hipStreamSynchronize(c->stream));
   return ROME_OK;
 }
+/* ---- mmd ---- */
+static int check_mmd(rome_ctx* c, int32_t dim, int32_t P, int32_t Na, const double* a, int32_t Nb, const double* b, const double* scale,
+                     double sigma, const double* out) {
+  if (!c || P < 0 || Na < 1 || Nb < 1 || (dim != 2 && dim != 3 && dim != 6)) return ROME_ERR_INVALID_ARG;
+  if (!std::isfinite(sigma) || sigma < 0.0) return ROME_ERR_INVALID_ARG;
+  if (scale) for (int k = 0; k < dim; ++k) if (!std::isfinite(scale[k]) || scale[k] < 0.0) return ROME_ERR_INVALID_ARG;
+  if (P > 0 && (!a || !b || !out)) return ROME_ERR_INVALID_ARG;
+  if (Na > ROME_MAX_PARTICLES_MMD || Nb > ROME_MAX_PARTICLES_MMD) return ROME_ERR_UNSUPPORTED_N;   /* both sets live in LDS */
+  return ROME_OK;
+}
+int rome_mmd_dev(rome_ctx* c, int32_t dim, int32_t P, int32_t Na, const double* a, const int32_t* a_rows, int32_t Nb, const double* b,
+                 const int32_t* b_rows, const double* scale, double sigma, double* out, double* sums) {
+  int rc = check_mmd(c, dim, P, Na, a, Nb, b, scale, sigma, out); if (rc) return rc;
+  if (P == 0) return ROME_OK;
+  ROME_BIND(c);
+  ROME_HIP(c, launch_mmd(dim, P, Na, a, a_rows, Nb, b, b_rows, scale, sigma, out, sums, c->stream));
+  return ROME_OK;
+}
+// rows of a host row table inside [0, n_blocks); without a table pair p reads block p
+static bool mmd_rows_ok(const int32_t* rows, int P, int n_blocks) {
+  if (!rows) return P <= n_blocks;
+  for (int p = 0; p < P; ++p) if (rows[p] < 0 || rows[p] >= n_blocks) return false;
+  return true;
+}
+int rome_mmd(rome_ctx* c, int32_t layout, int32_t dim, int32_t P, int32_t Na, int32_t n_a_blocks, const double* a, const int32_t* a_rows,
+             int32_t Nb, int32_t n_b_blocks, const double* b, const int32_t* b_rows, const double* scale, double sigma, double* out,
+             double* sums) {
+  int rc = check_mmd(c, dim, P, Na, a, Nb, b, scale, sigma, out); if (rc) return rc;
+  if (layout != ROME_LAYOUT_SOA && layout != ROME_LAYOUT_AOS && layout != ROME_LAYOUT_AOS_POINTS) return ROME_ERR_INVALID_ARG;
+  if (n_a_blocks < 0 || n_b_blocks < 0 || !mmd_rows_ok(a_rows, P, n_a_blocks) || !mmd_rows_ok(b_rows, P, n_b_blocks)) return ROME_ERR_INVALID_ARG;
+  if (P == 0) return ROME_OK;
+  ROME_HIP(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  void *d_a, *d_b, *d_o, *d_s = nullptr, *d_ar = nullptr, *d_br = nullptr;
+  const size_t np = (size_t)P;
+  if ((rc = ensure(c, 0, 8ull * n_a_blocks * dim * Na, &d_a))) return rc;
+  if ((rc = ensure(c, 1, 8ull * n_b_blocks * dim * Nb, &d_b))) return rc;
+  if ((rc = ensure(c, 2, 8 * np, &d_o))) return rc;
+  if (sums && (rc = ensure(c, 3, 24 * np, &d_s))) return rc;
+  if ((rc = stage_blocks(c, layout, n_a_blocks, dim, Na, a, (double*)d_a))) return rc;
+  if ((rc = stage_blocks(c, layout, n_b_blocks, dim, Nb, b, (double*)d_b))) return rc;
+  if (a_rows) {
+    if ((rc = ensure(c, 4, 4 * np, &d_ar))) return rc;
+    ROME_HIP(c, hipMemcpyAsync(d_ar, a_rows, 4 * np, hipMemcpyHostToDevice, s));
+  }
+  if (b_rows) {
+    if ((rc = ensure(c, 5, 4 * np, &d_br))) return rc;
+    ROME_HIP(c, hipMemcpyAsync(d_br, b_rows, 4 * np, hipMemcpyHostToDevice, s));
+  }
+  ROME_HIP(c, launch_mmd(dim, P, Na, (const double*)d_a, (const int32_t*)d_ar, Nb, (const double*)d_b, (const int32_t*)d_br, scale, sigma,
+                         (double*)d_o, (double*)d_s, s));
+  ROME_HIP(c, hipMemcpyAsync(out, d_o, 8 * np, hipMemcpyDeviceToHost, s));
+  if (sums) ROME_HIP(c, hipMemcpyAsync(sums, d_s, 24 * np, hipMemcpyDeviceToHost, s));
+  ROME_HIP(c, hipStreamSynchronize(s));
+  return ROME_OK;
+}
+
 static int check_kde(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, const double* bw) {
   if (!c || V < 0 || N < 2 || N > ROME_MAX_PARTICLES_REGISTER || dim < 1 || dim > 6 || (V > 0 && (!bel || !bw))) return ROME_ERR_INVALID_ARG;
   return ROME_OK;

@@ -75,6 +75,10 @@ hipError_t launch_linearize(int kind, int F, const double* mu, const double* W, 
                             double* r, double* Ja, double* Jb, hipStream_t s);
 
 hipError_t launch_belief_stats(int dim, int V, int N, const double* bel, double* mean, double* sdev, hipStream_t s);
+// mmd of P pairs of sets: pair p compares block a_rows[p] of a ([.][dim][Na]) with block b_rows[p] of b ([.][dim][Nb]) (null: p);
+// scale: HOST [dim] weights or null (ones), passed by value; out [P], sums [P][3] or null; Na, Nb <= 512
+hipError_t launch_mmd(int dim, int P, int Na, const double* a, const int32_t* a_rows, int Nb, const double* b, const int32_t* b_rows,
+                      const double* scale, double sigma, double* out, double* sums, hipStream_t s);
 // block_idx: optional [V] block of `bel` that belief v lives in (nullptr: v) -- the bandwidths of a scattered subset of a store
 hipError_t launch_kde_bandwidth(int dim, int V, int N, const double* bel, uint32_t circ_mask, double tol_e, double tol_c,
                                 double* bw, hipStream_t s, const int32_t* block_idx = nullptr);

@@ -7,7 +7,8 @@
 //    of the K kernel density estimates.  This is a STAND-IN for ApproxManifoldProducts.manifoldProduct
 //    (unvendored multiscale Gibbs product): the definition is the one in
 //    oracle/rome_oracle.c (ro_product, ro_product_bw) and is only claimed statistically against the reference.
-// Both are written once over a manifold policy M (Flat<2> Point2, Flat<3> Pose2, Se3M Pose3), which holds everything that
+//  * k_mmd<M>: maximum mean discrepancy between two particle sets (AMP `mmd`), one 256-thread block per pair of sets.
+// All are written once over a manifold policy M (Flat<2> Point2, Flat<3> Pose2, Se3M Pose3), which holds everything that
 // differs between the variable types.  Belief statistics: one wave (64-thread block) per variable.  Product: one 256-thread
 // block per variable (see k_product); weights are scanned in particle order so the resampling picks are the same as a
 // sequential CPU scan.
@@ -149,6 +150,114 @@ __global__ void __launch_bounds__(64) k_belief_stats(int V, int N, double inv_n,
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < D; ++k) { mean[D * v + k] = m[k]; sdev[D * v + k] = sd[k]; }
+  }
+}
+
+// ---- mmd: maximum mean discrepancy between two particle sets ------------------------------------------------------------------
+// out[p] = S_aa/Na² − 2 S_ab/(Na Nb) + S_bb/Nb² with S_xy = Σ_{i,j} exp(−σ · M::dist2(x_i, y_j, scale)) over all ordered pairs (the
+// biased V-statistic of MMD², as AMP's `mmd`).  One 256-thread block per pair p of blocks (a_rows[p], b_rows[p]).  Both sets are
+// staged once in dynamic LDS ((Na + Nb) · M::kLds doubles) by M::load / M::put: one quat_exp per point, none per pair.  Each panel's
+// pair index is flattened over the threads (at N = 100 a row per thread would idle 61 % of the block); the aa and bb panels visit
+// every UNORDERED pair i != j once -- in circulant order (r, (r + c) mod n), so both i < j and i > j occur: dist2 is symmetric --, are
+// doubled and get their exact diagonal Na / Nb.  Three per-thread sums, wave_sum_n<3>, then the four waves in
+// a fixed order: no atomics, so the bits of out[p] depend on pair p's inputs alone.
+constexpr int kMmdThreads = 256;
+constexpr int kMmdMaxN = 512;
+
+struct MmdArgs {
+  int Na, Nb;
+  const double* a;         // [rows][D][Na]
+  const int32_t* a_rows;   // [P] block of `a` of pair p, or null: p
+  const double* b;         // [rows][D][Nb]
+  const int32_t* b_rows;
+  double scale[6];         // per-coordinate weights s_c >= 0 (0 drops the coordinate)
+  double sigma;
+  double* out;             // [P]
+  double* sums;            // [P][3] = S_aa, S_ab, S_bb, or null
+};
+
+// [M::kLds][n] lines in dynamic LDS, indexed as M::put / M::get index their array
+struct LdsLines {
+  double* p; int n;
+  __device__ __forceinline__ double* operator[](int k) const { return p + k * n; }
+};
+
+// (t / n, t % n) of the flattened indices t = tid, tid + 256, ... one thread visits: one division, then additions
+struct PairWalk {
+  int q, r, dq, dr, n;
+  __device__ __forceinline__ PairWalk(int tid, int n_) : q(tid / n_), r(tid % n_), dq(kMmdThreads / n_), dr(kMmdThreads % n_), n(n_) {}
+  __device__ __forceinline__ void next() { q += dq; r += dr; if (r >= n) { r -= n; ++q; } }
+};
+
+template <class M>
+__device__ __forceinline__ void mmd_stage(const double* __restrict__ P, int N, int tid, const LdsLines& X) {
+  for (int i = tid; i < N; i += kMmdThreads) { typename M::Pt x; M::load(P, N, i, x); M::put(X, i, x); }
+}
+// Σ over the unordered pairs i != j of one set.  Pair t = (c − 1)·n + r is (r, (r + c) mod n), c = 1 .. n/2: every unordered pair
+// once (n even: the last c only for r < n/2, which is where t < n(n−1)/2 ends).
+template <class M>
+__device__ __forceinline__ double mmd_triangle(const LdsLines& X, int n, int tid, const double (&w)[M::D], double neg_sigma) {
+  double acc = 0.0;
+  const int T = n * (n - 1) / 2;
+  PairWalk pw(tid, n);
+  for (int t = tid; t < T; t += kMmdThreads, pw.next()) {
+    const int i = pw.r;
+    int j = i + pw.q + 1;
+    if (j >= n) j -= n;
+    typename M::Pt x, y;
+    M::get(X, i, x); M::get(X, j, y);
+    acc += fast_exp_neg(neg_sigma * M::dist2(x, y, w));
+  }
+  return acc;
+}
+// Σ over the full rectangle (i, j) = (t / nb, t % nb)
+template <class M>
+__device__ __forceinline__ double mmd_rectangle(const LdsLines& A, int na, const LdsLines& B, int nb, int tid, const double (&w)[M::D],
+                                                double neg_sigma) {
+  double acc = 0.0;
+  const int T = na * nb;
+  PairWalk pw(tid, nb);
+  for (int t = tid; t < T; t += kMmdThreads, pw.next()) {
+    typename M::Pt x, y;
+    M::get(A, pw.q, x); M::get(B, pw.r, y);
+    acc += fast_exp_neg(neg_sigma * M::dist2(x, y, w));
+  }
+  return acc;
+}
+
+template <class M>
+__global__ void __launch_bounds__(kMmdThreads) k_mmd(const MmdArgs g) {
+  constexpr int D = M::D;
+  extern __shared__ double mmd_pts[];
+  __shared__ double red[kMmdThreads / 64][3];
+  const int p = blockIdx.x, tid = threadIdx.x, Na = g.Na, Nb = g.Nb;
+  const LdsLines A{mmd_pts, Na}, B{mmd_pts + M::kLds * Na, Nb};
+  mmd_stage<M>(g.a + (size_t)(g.a_rows ? g.a_rows[p] : p) * D * Na, Na, tid, A);
+  mmd_stage<M>(g.b + (size_t)(g.b_rows ? g.b_rows[p] : p) * D * Nb, Nb, tid, B);
+  __syncthreads();
+  double w[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) w[k] = g.scale[k];
+  const double ns = -g.sigma;
+  double acc[3];
+  acc[0] = mmd_triangle<M>(A, Na, tid, w, ns);
+  acc[1] = mmd_rectangle<M>(A, Na, B, Nb, tid, w, ns);
+  acc[2] = mmd_triangle<M>(B, Nb, tid, w, ns);
+  wave_sum_n<3>(acc);
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) red[tid >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+    const double saa = 2.0 * s[0] + (double)Na, sab = s[1], sbb = 2.0 * s[2] + (double)Nb;
+    // IEEE divisions (one thread, once): a sum that is exactly its pair count gives exactly 1
+    const double taa = saa / ((double)Na * (double)Na), tab = sab / ((double)Na * (double)Nb), tbb = sbb / ((double)Nb * (double)Nb);
+    g.out[p] = (taa - tab) + (tbb - tab);
+    if (g.sums) { g.sums[3 * p] = saa; g.sums[3 * p + 1] = sab; g.sums[3 * p + 2] = sbb; }
   }
 }
 
@@ -377,6 +486,26 @@ hipError_t launch_belief_stats(int dim, int V, int N, const double* bel, double*
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+
+template <class M>
+static hipError_t launch_mmd_of(int P, const MmdArgs& g, hipStream_t s) {
+  const size_t lds = sizeof(double) * M::kLds * ((size_t)g.Na + (size_t)g.Nb);   // <= 56 KiB at 512 + 512 Pose3 points
+  hipLaunchKernelGGL(k_mmd<M>, dim3(P), dim3(kMmdThreads), lds, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_mmd(int dim, int P, int Na, const double* a, const int32_t* a_rows, int Nb, const double* b, const int32_t* b_rows,
+                      const double* scale, double sigma, double* out, double* sums, hipStream_t s) {
+  if (P <= 0) return hipSuccess;
+  if (Na < 1 || Nb < 1 || Na > kMmdMaxN || Nb > kMmdMaxN) return hipErrorInvalidValue;
+  MmdArgs g;
+  g.Na = Na; g.Nb = Nb; g.a = a; g.a_rows = a_rows; g.b = b; g.b_rows = b_rows; g.sigma = sigma; g.out = out; g.sums = sums;
+  for (int k = 0; k < 6; ++k) g.scale[k] = (scale && k < dim) ? scale[k] : 1.0;
+  if (dim == 2) return launch_mmd_of<Flat<2>>(P, g, s);
+  if (dim == 3) return launch_mmd_of<Flat<3>>(P, g, s);
+  if (dim == 6) return launch_mmd_of<Se3M>(P, g, s);
+  return hipErrorInvalidValue;
 }
 
 // S slots per lane from N.  A manifold that stages at every S has no S = 8 kernel (its points would not fit in LDS): N <= 256.

@@ -569,6 +569,29 @@ class DeviceGraph:
         _lib.check(self._lib.rome_belief_stats_dev(self.ctx.handle, d, V, N, b.data_ptr(), mean.data_ptr(), sd.data_ptr()), self.ctx.handle)
         return mean, sd
 
+    def mmd(self, vartype, other, bw=0.001, scale=None, out=None):
+        """[V] maximum mean discrepancies (AMP `mmd`, rome_mmd_dev) between every belief of one variable type and the same block of
+        `other`, a device tensor shaped like self.bel[vartype] -- e.g. a clone taken before a sweep: how far the sweep moved each belief
+        as a distribution.  scale: per-coordinate weights (host values) or None = ones.  One launch, no host synchronisation, capturable
+        (pass `out` to keep the result outside the graph's memory pool)."""
+        torch = self.torch
+        b = self.bel[vartype]
+        V, d, N = b.shape
+        if tuple(other.shape) != (V, d, N) or other.dtype != torch.float64 or other.device != b.device or not other.is_contiguous():
+            raise ValueError("DeviceGraph.mmd: `other` must be a contiguous float64 tensor of shape %s on %s" % ((V, d, N), b.device))
+        if out is None:
+            out = torch.empty((V,), dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (V,) or out.dtype != torch.float64 or out.device != b.device or not out.is_contiguous():
+            raise ValueError("DeviceGraph.mmd: `out` must be a contiguous float64 tensor of shape (%d,) on %s" % (V, b.device))
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64)
+        if sc is not None and sc.shape != (d,):
+            raise ValueError("DeviceGraph.mmd: scale must have %d entries" % d)
+        self._bind_stream()
+        _lib.check(self._lib.rome_mmd_dev(self.ctx.handle, d, V, N, b.data_ptr(), None, N, other.data_ptr(), None,
+                                          None if sc is None else sc.ctypes.data_as(C.POINTER(C.c_double)), float(bw), out.data_ptr(), None),
+                   self.ctx.handle)
+        return out
+
     def kde_bandwidths(self, vartype, tol_euclid=0.0, tol_circular=0.0):
         """[V, dim] leave-one-out likelihood bandwidths of every belief of one variable type (`manikde!` rule), on device."""
         self._bind_stream()

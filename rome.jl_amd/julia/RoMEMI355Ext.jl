@@ -708,6 +708,30 @@ function kde_max(X::Matrix{Float64}, bw::Vector{Float64} = kde_bandwidths(X))
   m
 end
 
+# ---- mmd on the device (rome_mmd; replaces ApproxManifoldProducts.mmd as the tests use it) ------------------------
+# a, b: vectors of the reference's native points of ONE variable type (Point2 SVector{2}: 2 doubles, Pose2 ArrayPartition: 6, Pose3: 12 --
+# isbits, so the vectors are passed as they are, ROME_LAYOUT_AOS_POINTS).  M is taken for the call shape `mmd(M, a, b; bw=[0.001])`; the
+# variable type is read off the point length (_mmd_dim; any other point type is an error that names it).  bw[1] is the kernel's σ; scale: per-coordinate weights or nothing (ones; see the header on
+# the weight of a rotation).
+function _mmd_dim(::Type{P}) where {P}
+  n = isbitstype(P) ? sizeof(P) ÷ 8 : 0
+  n == 2 ? 2 : n == 6 ? 3 : n == 12 ? 6 :
+    error("mmd: points of type $P are not supported: expected the isbits native points of Point2 (2 doubles), Pose2 (6) or Pose3 (12)")
+end
+function mmd(M, a::Vector{P}, b::Vector{P}; bw::AbstractVector{<:Real}=[0.001], scale::Union{Nothing,Vector{Float64}}=nothing) where {P}
+  d = _mmd_dim(P)
+  scale === nothing || length(scale) == d || error("mmd: scale must have $d entries for points of type $P")
+  out = Vector{Float64}(undef, 1)
+  GC.@preserve a b out begin
+    check(ccall((:rome_mmd, LIB), Cint,
+      (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Float64,
+       Ptr{Float64}, Ptr{Float64}),
+      ctx().h, 2, d, 1, length(a), 1, Ptr{Float64}(pointer(a)), C_NULL, length(b), 1, Ptr{Float64}(pointer(b)), C_NULL,
+      scale === nothing ? C_NULL : scale, Float64(bw[1]), out, C_NULL))
+  end
+  out[1]
+end
+
 # ---- stage 2 of the partial-aware product (rome_product_partial; include/rome_mi355.h, DESIGN.md §12d) -----------
 # prop: N x dim x rows, bel: N x dim x V (exactly the C side's SoA blocks [.][dim][N]); bel holds the product of the full proposals on
 # entry and is updated in place.  The task tables are 0-based, as the header defines them: task t rewrites coordinate task_coord[t] of
