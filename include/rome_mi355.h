@@ -45,7 +45,7 @@
 extern "C" {
 #endif
 
-#define ROME_MI355_VERSION 122 /* 0.1.22 (appended since, the number unchanged: the partial Pose3 entries rome_*_pose3pose3xyyaw* / rome_conv_priorpose3zrp* / rome_*_pose3pose3rotation*; ROME_BLOCKOP_COMPOSE on Pose3 blocks, ROME_BLOCKOP_ANCHOR_MEAN, p3p3_meas at the end of rome_clique_host -- solveTree as variable elimination on Pose3 graphs): ROME_BLOCKOP_COMPOSE / MIX, rome_blockop_plan_create_ex (round 6: solveTree as variable elimination in relative-factor algebra); rome_ctx_set_stream orders streams by event.  0.1.21: store-resident messages (smsg_*) in rome_clique_upsolve_host (a tree level reads its children's separator beliefs from HBM); multihypo / nullhypo / stream-id columns in rome_clique_host; rome_store + rome_upsolve_plan
+#define ROME_MI355_VERSION 122 /* 0.1.22 (appended since, the number unchanged: rome_deconv / rome_deconv_dev; rome_mmd*; the partial Pose3 entries rome_*_pose3pose3xyyaw* / rome_conv_priorpose3zrp* / rome_*_pose3pose3rotation*; ROME_BLOCKOP_COMPOSE on Pose3 blocks, ROME_BLOCKOP_ANCHOR_MEAN, p3p3_meas at the end of rome_clique_host -- solveTree as variable elimination on Pose3 graphs): ROME_BLOCKOP_COMPOSE / MIX, rome_blockop_plan_create_ex (round 6: solveTree as variable elimination in relative-factor algebra); rome_ctx_set_stream orders streams by event.  0.1.21: store-resident messages (smsg_*) in rome_clique_upsolve_host (a tree level reads its children's separator beliefs from HBM); multihypo / nullhypo / stream-id columns in rome_clique_host; rome_store + rome_upsolve_plan
                                  * (device-resident clique up-solves: beliefs stay in HBM across frontiers) */
 
 enum {
@@ -634,6 +634,60 @@ int rome_sweep_pose2_dev(rome_ctx*, const rome_opts*, const rome_conv_dev* p2p2,
 int rome_sample_priorpose2_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*); /* uses factor, mu, L, noise, out */
 int rome_sample_priorpose3_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);
 int rome_sample_priorpoint2_dev(rome_ctx*, const rome_opts*, const rome_conv_dev*);   /* L = [F][3] packed Cholesky of the 2x2 covariances */
+
+/* ---------------------------------------------------------------------------------------------
+ * rome_deconv*: the inverse of a convolution -- ⚠IIF `approxDeconv(fg, factor)`, as the reference calls it to judge a factor against
+ *   the solved beliefs (test/testBasicPose2Conv.jl:51 `pts, meas = approxDeconv(fg, :x0x1f1)`, :56 `@test mmd(M, pts, meas) < 0.001`).
+ *   IIF is not vendored: its behaviour is RESTATED from that call site and NOT CHECKED against IIF.  What is computed here: particle i
+ *   of the factor's first variable is paired with particle i of its second, and
+ *     pred[c][.][i]  the measurement (tangent coordinates, dz of them) at which the factor's residual vanishes on the pair -- a closed
+ *                    form for every relative factor this library convolves (the measurement has as many coordinates as the residual):
+ *       POSE2POSE2          3   R_pᵀ (t_q − t_p), heading atan2(sin(θ_q − θ_p), cos(θ_q − θ_p)) in (−π, π]
+ *       POSE2POINT2BR       2   pl = R_pᵀ (l − t_p): (atan2(pl_y, pl_x), ‖pl‖)
+ *       POSE2POINT2BEARING  1   atan2(pl_y, pl_x)
+ *       POINT2POINT2RANGE,
+ *       POSE2POINT2RANGE    1   ‖l − x‖ (a pose's heading is not read)
+ *       POSE3POSE3          6   R_pᵀ (t_q − t_p), Log(R_pᵀ R_q) (the principal rotation vector)
+ *       POSE3POSE3XYYAW     3   the POSE2POSE2 row on the two SE(2) projections (t_xy, first column of R)
+ *       POSE3POSE3ROTATION  3   Log(R_pᵀ R_q)
+ *                    (the landmark on the pose: the bearing is the library's atan2(0, 0) = 0, the range 0);
+ *     meas[c][.][i]  the measurement sample the CONVOLUTION of the same row draws for particle i: z = μ + Lξ (the family's rule) on the
+ *                    normals of (opts->seed, opts->stream_offset + c, i) -- the Philox counter is (particle, stream, purpose), so
+ *                    rome_conv_* with in-kernel noise on stream c draws exactly these -- or on `noise`, or `noise` itself, by
+ *                    opts->presampled as for the convolutions.
+ *   Out of scope (ROME_ERR_INVALID_ARG: no ROME_DECONV_* names them): priors (the deconvolution of a prior is the belief itself),
+ *   Point2Point2 (host side only), multihypo rows; nullhypo is ignored (a deconvolution has no null branch), as are opts->solver and
+ *   the iteration fields.
+ *   rome_deconv_dev: DEVICE pointers, SoA blocks.  rows4 [C][4] = (factor, 0, var_a, var_b) replaces the three columns; a NULL column
+ *   means c.  mu / L: the table formats of the family's rome_conv_*_dev entry.  pred, meas [C][dz][N]: either may be NULL, not both.
+ *   One launch on the context's stream; it neither synchronises nor allocates (it can be captured into a graph).  The bits of row c
+ *   depend on row c's inputs alone.
+ *   rome_deconv: HOST pointers, C rows, row c on blocks c of a and b (opts->layout; pred / meas / noise rows are coordinates: AOS for
+ *   AOS_POINTS); cov: what the family's rome_conv_* entry takes (covariances [C][dz*dz], or sigmas [C][dz]).
+ *   Checks, in the order of the convolution section: the options (N > ROME_MAX_PARTICLES: ROME_ERR_UNSUPPORTED_N, nothing launched);
+ *   the context, C >= 0, the family; required pointers (C > 0: mu, L / cov, both belief arrays, one output); C == 0 (ROME_OK, nothing
+ *   touched); the noise parameters (host entry: ROME_ERR_NOT_POSDEF). */
+enum { ROME_DECONV_POSE2POSE2 = 0, ROME_DECONV_POSE2POINT2BR = 1, ROME_DECONV_POSE2POINT2BEARING = 2, ROME_DECONV_POINT2POINT2RANGE = 3,
+       ROME_DECONV_POSE2POINT2RANGE = 4, ROME_DECONV_POSE3POSE3 = 5, ROME_DECONV_POSE3POSE3XYYAW = 6, ROME_DECONV_POSE3POSE3ROTATION = 7 };
+typedef struct rome_deconv_table {
+  int32_t n_rows;            /* C */
+  int32_t reserved;
+  const int32_t* factor;     /* [C] row of mu / L, NULL -> c                                      */
+  const int32_t* var_a;      /* [C] block of bel_a (the factor's first variable), NULL -> c       */
+  const int32_t* var_b;      /* [C] block of bel_b (the second variable), NULL -> c               */
+  const int32_t* rows4;      /* [C][4] (factor, 0, var_a, var_b), replaces the three columns; or NULL */
+  const double* mu;          /* [F][dz]                                                           */
+  const double* L;           /* the family's convolution table                                    */
+  const double* bel_a;
+  const double* bel_b;
+  const double* noise;       /* [C][dz][N] or NULL                                                */
+  double* pred;              /* [C][dz][N] or NULL                                                */
+  double* meas;              /* [C][dz][N] or NULL                                                */
+} rome_deconv_table;
+int rome_deconv_dev(rome_ctx*, const rome_opts*, int32_t family, const rome_deconv_table*);
+int rome_deconv(rome_ctx*, const rome_opts*, int32_t family, int32_t C, const double* mu, const double* cov,
+                const double* a, const double* b, const double* noise /*C*N*dz or NULL*/, double* pred /*C*N*dz or NULL*/,
+                double* meas /*C*N*dz or NULL*/);                                                                  /* host pointers */
 
 /* ---------------------------------------------------------------------------------------------
  * Parametric path: batched whitened residuals + analytic Jacobians at the

@@ -19,14 +19,14 @@ from .api import (linearize, belief_stats, mmd, mmdBeliefs, kde_bandwidth, kde_m
                   residual_point2point2range, residual_pose2point2range, conv_point2point2range, conv_pose2point2range,
                   residual_pose2point2bearing, residual_pose2point2bearing_pt, conv_pose2point2bearing,
                   residual_pose3pose3xyyaw, residual_pose3pose3xyyaw_pt, conv_pose3pose3xyyaw, conv_priorpose3zrp,
-                  residual_pose3pose3rotation, residual_pose3pose3rotation_pt, conv_pose3pose3rotation)
+                  residual_pose3pose3rotation, residual_pose3pose3rotation_pt, conv_pose3pose3rotation, deconv, deconv_family)
 from .graph import (FactorGraph, initfg, fifoFreeze, isMarginalized, importG2o, parseG2oInstruction, loadG2o, synth_manhattan,
                     synth_manhattan_edges, synth_pose2_tables, synth_helix3d, synth_mit_br, add_synthetic_landmarks, dead_reckon_init_pose3, generateGraph_Circle, generateGraph_Hexagonal,
                     PackedGraph, dead_reckon_init)
 from .canonical import (generateGraph_ZeroPose, buildGraphChain, generateGraph_TwoPoseOdo, calcHelix_T, generateGraph_Helix2D,
                         generateGraph_Helix2DSlew, generateGraph_Helix2DSpiral, generateGraph_Boxes2D, generateGraph_Beehive,
                         generateGraph_Honeycomb, synth_beehive_mh, exportG2o, stringG2o, getPPE, setPPE, accumulateFactorMeans)
-from .convolution import approxConv, approxConvBelief
+from .convolution import approxConv, approxConvBelief, approxDeconv, factorMMD
 from .clique import proposalbeliefs, predictbelief, CliqueBatch, upGibbsCliqueDensity, upGibbsCliqueFrontier
 from .serialization import loadDFG, saveDFG, packFactor, unpackFactor, packBelief, unpackBelief
 from .parametric import solveGraphParametric, initParametric

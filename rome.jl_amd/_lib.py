@@ -20,6 +20,8 @@ MAX_PARTICLES_KDE, MAX_PARTICLES_PRODUCT, MAX_PARTICLES_PRODUCT_POSE3, MAX_PARTI
 MAX_PARTICLES_MMD = 512         # ROME_MAX_PARTICLES_MMD: both sets of a pair live in LDS
 FACTOR_PRIORPOSE2, FACTOR_POSE2POSE2, FACTOR_POSE2POINT2BR, FACTOR_PRIORPOINT2, FACTOR_POSE3POSE3, FACTOR_PRIORPOSE3 = range(6)
 FACTOR_POSE2POINT2BEARING = 6
+(DECONV_POSE2POSE2, DECONV_POSE2POINT2BR, DECONV_POSE2POINT2BEARING, DECONV_POINT2POINT2RANGE, DECONV_POSE2POINT2RANGE, DECONV_POSE3POSE3,
+ DECONV_POSE3POSE3XYYAW, DECONV_POSE3POSE3ROTATION) = range(8)   # ROME_DECONV_*
 
 
 class RomeError(RuntimeError):
@@ -43,6 +45,13 @@ class ConvDev(C.Structure):
                 ("n_mirror", C.c_int32), ("mirror_row", C.c_int32 * 4), ("reserved", C.c_int32), ("mirror_out", C.c_void_p),
                 ("alt_var", C.c_void_p), ("hypo_w", C.c_void_p), ("nullhypo", C.c_void_p), ("rows4", C.c_void_p),
                 ("mirror_map", C.c_void_p)]
+
+
+class DeconvTable(C.Structure):
+    _fields_ = [("n_rows", C.c_int32), ("reserved", C.c_int32),
+                ("factor", C.c_void_p), ("var_a", C.c_void_p), ("var_b", C.c_void_p), ("rows4", C.c_void_p),
+                ("mu", C.c_void_p), ("L", C.c_void_p), ("bel_a", C.c_void_p), ("bel_b", C.c_void_p),
+                ("noise", C.c_void_p), ("pred", C.c_void_p), ("meas", C.c_void_p)]
 
 
 _PD = C.POINTER(C.c_double)
@@ -109,6 +118,8 @@ SIGNATURES = {
     "rome_sample_priorpose2_dev": (C.c_int, [_CTX, _PO, _PT]),
     "rome_sample_priorpose3_dev": (C.c_int, [_CTX, _PO, _PT]),
     "rome_sample_priorpoint2_dev": (C.c_int, [_CTX, _PO, _PT]),
+    "rome_deconv_dev": (C.c_int, [_CTX, _PO, C.c_int32, C.POINTER(DeconvTable)]),
+    "rome_deconv": (C.c_int, [_CTX, _PO, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD]),
     "rome_linearize": (C.c_int, [_CTX, C.c_int32, C.c_int32, _PD, _PD, _PD, _PD, _PD, _PD, _PD]),
     "rome_linearize_dev": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rome_belief_stats_dev": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

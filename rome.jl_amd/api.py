@@ -548,6 +548,60 @@ def conv_priorpose3zrp(opts, mu, sigma_z, cov_rp, target, noise=None, ctx=None, 
     return _conv("rome_conv_priorpose3zrp", (3, 6, 6), opts, mu, [(sigma_z, ()), (cov_rp, (2, 2))], None, target, noise, ctx, layout, nullhypo)
 
 
+# ------------------------------------------------------------------ deconvolution
+# factor class -> (ROME_DECONV_*, dz, dimension of the first / second variable, shape of one row of the noise parameters): the relative
+# factors the library convolves.  Looked up along the factor's classes; anything else is refused by name (deconv_family).
+_DECONV = {
+    Pose2Pose2: (_lib.DECONV_POSE2POSE2, 3, 3, 3, (3, 3)),
+    Pose2Point2BearingRange: (_lib.DECONV_POSE2POINT2BR, 2, 3, 2, (2,)),
+    Pose2Point2Bearing: (_lib.DECONV_POSE2POINT2BEARING, 1, 3, 2, ()),
+    Point2Point2Range: (_lib.DECONV_POINT2POINT2RANGE, 1, 2, 2, ()),
+    Pose2Point2Range: (_lib.DECONV_POSE2POINT2RANGE, 1, 3, 2, ()),
+    Pose3Pose3: (_lib.DECONV_POSE3POSE3, 6, 6, 6, (6, 6)),
+    Pose3Pose3XYYaw: (_lib.DECONV_POSE3POSE3XYYAW, 3, 6, 6, (3, 3)),
+    Pose3Pose3Rotation: (_lib.DECONV_POSE3POSE3ROTATION, 3, 6, 6, (3, 3)),
+}
+
+
+def deconv_family(family):
+    """(ROME_DECONV_*, dz, da, db, noise-parameter row shape) of a factor class, a factor, or a class name; TypeError, by name, for
+    what a deconvolution is not defined on here: priors (their deconvolution is the belief itself) and Point2Point2 (host side only)."""
+    cls = family if isinstance(family, type) else type(family)
+    if isinstance(family, str):
+        cls = next((c for c in _DECONV if c.__name__ == family), None)
+        if cls is None:
+            raise TypeError("deconv: no deconvolution for factor type %s (priors: the belief itself; Point2Point2: host side only)" % family)
+    for c in cls.__mro__:
+        if c in _DECONV:
+            return _DECONV[c]
+    raise TypeError("deconv: no deconvolution for factor type %s (priors: the belief itself; Point2Point2: host side only)" % cls.__name__)
+
+
+def deconv(family, opts, mu, cov, a, b, noise=None, want=("pred", "meas"), ctx=None):
+    """C deconvolutions of one factor family (rome_deconv; ⚠IIF approxDeconv restated, include/rome_mi355.h): row c pairs particle i of
+    block c of `a` (the factor's first variable) with particle i of block c of `b` (the second).  family: a factor class, a factor or
+    a class name; mu (C, dz) and cov as the family's conv_* wrapper takes them (covariances (C, dz, dz), or sigmas); a / b: C blocks
+    in opts.layout; noise: C blocks of standard normals, or of the samples themselves under presampled=NOISE_MEASUREMENTS.
+    -> (pred, meas), each C blocks of dz coordinates ((C, dz, N) in LAYOUT_SOA, else (C, N, dz)), None for an output not in `want`:
+    pred = the measurement each pair predicts, meas = the sample the convolution of row c (stream opts.stream_offset + c) draws."""
+    fam, dz, da, db, shape = deconv_family(family)
+    want = tuple(want)
+    if not want or any(w not in ("pred", "meas") for w in want):
+        raise ValueError("deconv: want must name 'pred', 'meas' or both, got %r" % (want,))
+    ctx = ctx or default_context()
+    mu = np.atleast_2d(_d(mu)) if dz > 1 else np.atleast_1d(_d(mu)).reshape(-1, 1)
+    C_, N = mu.shape[0], opts.n_particles
+    mu = _d(mu, (C_, dz))
+    cov = _d(cov if shape else np.atleast_1d(_d(cov)).ravel(), (C_,) + shape)
+    a, b = _blocks(a, C_, N, da, opts.layout), _blocks(b, C_, N, db, opts.layout)
+    noise = None if noise is None else _blocks(noise, C_, N, dz, opts.layout, points_ok=False)
+    oshape = (C_, dz, N) if opts.layout == _lib.LAYOUT_SOA else (C_, N, dz)
+    pred = np.empty(oshape) if "pred" in want else None
+    meas = np.empty(oshape) if "meas" in want else None
+    _lib.check(_lib.load().rome_deconv(ctx.handle, C.byref(opts), fam, C_, _p(mu), _p(cov), _p(a), _p(b), _p(noise), _p(pred), _p(meas)), ctx.handle)
+    return pred, meas
+
+
 def _sample_prior(fn, d, opts, mu, cov, noise, ctx):
     ctx = ctx or default_context()
     mu = np.atleast_2d(_d(mu)); C_ = mu.shape[0]; N = opts.n_particles

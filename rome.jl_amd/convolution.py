@@ -69,3 +69,69 @@ def approxConv(fg, flabel, target, solver=_lib.SOLVER_NEWTON, seed=None, ctx=Non
 
 
 approxConvBelief = approxConv
+
+
+def _deconv_rows(fg, flabels, who):
+    """(factor, mu row, noise-parameter row, first / second variable's label) of each factor label; refusals by name, before any device
+    call: priors and Point2Point2 (api.deconv_family), multihypo factors, variables without a belief"""
+    rows = []
+    for flabel in flabels:
+        _, labels, f = fg.getFactor(flabel)
+        api.deconv_family(f)
+        if fg.multihypo.get(flabel) is not None:
+            raise TypeError("%s: factor %s carries multihypo; a deconvolution pairs one first with one second variable" % (who, flabel))
+        for l in labels[:2]:
+            if not fg.isInitialized(l):
+                raise ValueError("%s: variable %s has no belief yet" % (who, l))
+        if isinstance(f, Pose2Point2BearingRange):
+            mu, prm = [f.bearing.mu, f.range.mu], [f.bearing.sigma, f.range.sigma]
+        elif isinstance(f, (Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing)):
+            mu, prm = f.Z.mu, f.Z.sigma
+        else:
+            mu, prm = f.Z.mu, f.Z.cov
+        rows.append((f, mu, prm, labels[0], labels[1]))
+    return rows
+
+
+def approxDeconv(fg, flabel, seed=None, ctx=None, **optkw):
+    """⚠IIF `approxDeconv(fg, flabel)` as the reference calls it (test/testBasicPose2Conv.jl:51; restated from that call site, not checked
+    against IIF): -> (pred, meas), each (dz, N) measurement coordinates.  pred[:, i] is the measurement at which the factor's residual
+    vanishes on particle i of its first and particle i of its second variable; meas holds N samples of the measurement the factor
+    carries, drawn as approxConv draws them.  nullhypo is ignored (a deconvolution has no null branch).  TypeError, by name: priors,
+    Point2Point2, multihypo factors."""
+    (f, mu, prm, a, b), = _deconv_rows(fg, [flabel], "approxDeconv")
+    opts = api.make_opts(N=fg.N, seed=seed, **optkw)
+    opts.layout = _lib.LAYOUT_SOA
+    pred, meas = api.deconv(f, opts, [mu], [prm], fg.getVal(a)[None], fg.getVal(b)[None], ctx=ctx)
+    return pred[0], meas[0]
+
+
+_MMD_FAMILIES = (Pose2Pose2, Pose3Pose3XYYaw, Pose3Pose3)   # measurement manifolds rome_mmd serves: SE(2) (dim 3), SE(3) (dim 6)
+
+
+def factorMMD(fg, labels=None, bw=0.001, seed=None, ctx=None, **optkw):
+    """{flabel: mmd(pred, meas)} of approxDeconv for the factors `labels`: how well each factor's measurement model agrees with the
+    current beliefs of its variables (the reference accepts a convolution at < 0.001, test/testBasicPose2Conv.jl:56); a factor at odds
+    with the solve stands out.  labels None: every Pose2Pose2, Pose3Pose3XYYaw and Pose3Pose3 factor of the graph without multihypo.
+    A named factor of another family raises TypeError: its measurement manifold (R, the circle, circle x R, SO(3)) is not one `mmd`
+    serves.  One deconv and one mmd call per family; factor k of a family draws Philox stream stream_offset + k."""
+    if labels is None:
+        labels = [fl for fl, _, f in fg.factors if isinstance(f, _MMD_FAMILIES) and fg.multihypo.get(fl) is None]
+    labels = list(labels)
+    for fl in labels:   # (the family first: a refusal does not depend on what has a belief)
+        f = fg.getFactor(fl)[2]
+        api.deconv_family(f)
+        if not isinstance(f, _MMD_FAMILIES):
+            raise TypeError("factorMMD: the measurement manifold of %s (factor %s) is not one mmd serves" % (type(f).__name__, fl))
+    rows = _deconv_rows(fg, labels, "factorMMD")
+    opts = api.make_opts(N=fg.N, seed=seed, **optkw)
+    opts.layout = _lib.LAYOUT_SOA
+    res = {}
+    for cls in _MMD_FAMILIES:
+        sel = [(fl, r) for fl, r in zip(labels, rows) if next(c for c in type(r[0]).__mro__ if c in _MMD_FAMILIES) is cls]
+        if not sel:
+            continue
+        pred, meas = api.deconv(cls, opts, [r[1] for _, r in sel], [r[2] for _, r in sel], np.stack([fg.getVal(r[3]) for _, r in sel]),
+                                np.stack([fg.getVal(r[4]) for _, r in sel]), ctx=ctx)
+        res.update(zip([fl for fl, _ in sel], api.mmd(pred, meas, bw=bw, ctx=ctx).tolist()))
+    return {fl: res[fl] for fl in labels}

@@ -619,6 +619,87 @@ int rome_sweep_pose2_dev(rome_ctx* c, const rome_opts* o, const rome_conv_dev* p
   return ROME_OK;
 }
 
+/* ---- approxDeconv: ROME_DECONV_* -> the convolution family whose table formats it shares, the unit that owns its policy ---- */
+typedef hipError_t (*DeconvLaunch)(int, const DeconvArgs&, hipStream_t);
+struct DeconvFamily { FactorKind kind; int kfam; DeconvLaunch launch; };
+static const DeconvFamily kDeconv[] = {
+    /* ROME_DECONV_POSE2POSE2         */ {kP2P2, kDeconvPose2Pose2, launch_deconv_pose2},
+    /* ROME_DECONV_POSE2POINT2BR      */ {kBR, kDeconvBearingRange, launch_deconv_pose2},
+    /* ROME_DECONV_POSE2POINT2BEARING */ {kPB, kDeconvBearing, launch_deconv_range},
+    /* ROME_DECONV_POINT2POINT2RANGE  */ {kP2R, kDeconvPoint2Point2Range, launch_deconv_range},
+    /* ROME_DECONV_POSE2POINT2RANGE   */ {kPPR, kDeconvPose2Point2Range, launch_deconv_range},
+    /* ROME_DECONV_POSE3POSE3         */ {kP3P3, kDeconvPose3Pose3, launch_deconv_pose3},
+    /* ROME_DECONV_POSE3POSE3XYYAW    */ {kP3XYY, kDeconvPose3Pose3XYYaw, launch_deconv_pose3_partial},
+    /* ROME_DECONV_POSE3POSE3ROTATION */ {kP3ROT, kDeconvPose3Pose3Rotation, launch_deconv_pose3_partial},
+};
+static_assert(sizeof(kDeconv) / sizeof(kDeconv[0]) == ROME_DECONV_POSE3POSE3ROTATION + 1, "one row per ROME_DECONV_*, in its order");
+static bool deconv_family_ok(int32_t family) { return family >= 0 && family <= ROME_DECONV_POSE3POSE3ROTATION; }
+static void deconv_args(DeconvArgs& a, const rome_opts* o, const rome_deconv_table* t) {
+  std::memset(&a, 0, sizeof(a));
+  a.n_rows = t->n_rows; a.N = o->n_particles;
+  a.rows4 = t->rows4; a.factor = t->factor; a.var_a = t->var_a; a.var_b = t->var_b;
+  a.mu = t->mu; a.L = t->L; a.bel_a = t->bel_a; a.bel_b = t->bel_b; a.noise = t->noise;
+  a.noise_is_meas = o->presampled == ROME_NOISE_MEASUREMENTS;
+  a.pred = t->pred; a.meas = t->meas;
+  a.seed = o->seed; a.stream_offset = o->stream_offset;
+}
+int rome_deconv_dev(rome_ctx* c, const rome_opts* o, int32_t family, const rome_deconv_table* t) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!c || !t || t->n_rows < 0 || !deconv_family_ok(family)) return ROME_ERR_INVALID_ARG;
+  if (t->n_rows > 0 && (!t->mu || !t->L || !t->bel_a || !t->bel_b || (!t->pred && !t->meas))) return ROME_ERR_INVALID_ARG;
+  if (t->n_rows == 0) return ROME_OK;
+  ROME_BIND(c);
+  DeconvArgs a; deconv_args(a, o, t);
+  ROME_HIP(c, kDeconv[family].launch(kDeconv[family].kfam, a, c->stream));
+  return ROME_OK;
+}
+int rome_deconv(rome_ctx* ctx, const rome_opts* o, int32_t family, int32_t C, const double* mu, const double* cov, const double* a,
+                const double* b, const double* noise, double* pred, double* meas) {
+  int rc = check_opts(o); if (rc) return rc;
+  if (!ctx || C < 0 || !deconv_family_ok(family)) return ROME_ERR_INVALID_ARG;
+  if (C > 0 && (!mu || !cov || !a || !b || (!pred && !meas))) return ROME_ERR_INVALID_ARG;
+  if (C == 0) return ROME_OK;
+  const Family& f = kFamily[kDeconv[family].kind];
+  std::vector<double> L;
+  const double* Ltab; int nL;
+  if ((rc = pack_noise(f, C, cov, nullptr, L, &Ltab, &nL))) return rc;
+  ROME_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DrainOnExit drain{s};
+  const int N = o->n_particles, dz = f.dz;
+  const int lz = o->layout == ROME_LAYOUT_AOS_POINTS ? ROME_LAYOUT_AOS : o->layout;   // measurement rows are coordinates, never points
+  const size_t n_a = (size_t)C * N * f.d1, n_b = (size_t)C * N * f.d2, n_z = (size_t)C * N * dz;
+  double *h_a, *h_b, *h_noise = nullptr, *h_out;
+  void *d_mu, *d_L, *d_a, *d_b, *d_noise = nullptr, *d_pred = nullptr, *d_meas = nullptr;
+  if ((rc = ensure(ctx, 0, sizeof(double) * C * dz, &d_mu))) return rc;
+  if ((rc = ensure(ctx, 1, sizeof(double) * C * nL, &d_L))) return rc;
+  if ((rc = ensure(ctx, 3, sizeof(double) * n_a, &d_a))) return rc;
+  if ((rc = ensure(ctx, 4, sizeof(double) * n_b, &d_b))) return rc;
+  if ((rc = ensure_host(ctx, 0, sizeof(double) * n_a, &h_a))) return rc;
+  if ((rc = ensure_host(ctx, 1, sizeof(double) * n_b, &h_b))) return rc;
+  if ((rc = ensure_host(ctx, 3, sizeof(double) * n_z, &h_out))) return rc;
+  if (pred && (rc = ensure(ctx, 2, sizeof(double) * n_z, &d_pred))) return rc;
+  if (meas && (rc = ensure(ctx, 6, sizeof(double) * n_z, &d_meas))) return rc;
+  ROME_HIP(ctx, hipMemcpyAsync(d_mu, mu, sizeof(double) * C * dz, hipMemcpyHostToDevice, s));
+  ROME_HIP(ctx, hipMemcpyAsync(d_L, Ltab, sizeof(double) * C * nL, hipMemcpyHostToDevice, s));
+  if ((rc = stage_blocks(ctx, o->layout, C, f.d1, N, a, (double*)d_a, h_a))) return rc;
+  if ((rc = stage_blocks(ctx, o->layout, C, f.d2, N, b, (double*)d_b, h_b))) return rc;
+  if (noise) {
+    if ((rc = ensure_host(ctx, 2, sizeof(double) * n_z, &h_noise))) return rc;
+    if ((rc = ensure(ctx, 5, sizeof(double) * n_z, &d_noise))) return rc;
+    if ((rc = stage_blocks(ctx, lz, C, dz, N, noise, (double*)d_noise, h_noise))) return rc;
+  }
+  rome_deconv_table t;
+  std::memset(&t, 0, sizeof(t));
+  t.n_rows = C; t.mu = (const double*)d_mu; t.L = (const double*)d_L; t.bel_a = (const double*)d_a; t.bel_b = (const double*)d_b;
+  t.noise = (const double*)d_noise; t.pred = (double*)d_pred; t.meas = (double*)d_meas;
+  DeconvArgs da; deconv_args(da, o, &t);
+  ROME_HIP(ctx, kDeconv[family].launch(kDeconv[family].kfam, da, s));
+  if (pred && (rc = fetch_blocks(ctx, lz, C, dz, N, (const double*)d_pred, pred, h_out))) return rc;   // (synchronises)
+  if (meas && (rc = fetch_blocks(ctx, lz, C, dz, N, (const double*)d_meas, meas, h_out))) return rc;
+  return ROME_OK;
+}
+
 /* ---- native point containers <-> coordinates ---- */
 int rome_points_to_coords(rome_ctx* c, int32_t dim, int32_t n, const double* pts, double* coords) {
   if (!c || n < 0 || (dim != 2 && dim != 3 && dim != 6) || (n > 0 && (!pts || !coords))) return ROME_ERR_INVALID_ARG;

@@ -696,6 +696,121 @@ __global__ void __launch_bounds__(64 * ROME_WPB) k_conv_big(const ConvArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// k_deconv -- approxDeconv of a table of relative factors: for row c = (factor, var_a, var_b), particle i of the first variable is
+// paired with particle i of the second, and
+//   pred[c][.][i] = FP::predict(a_i, b_i)   the measurement (tangent coordinates) at which the factor's residual vanishes on the pair;
+//   meas[c][.][i] = what the convolution of row c draws for particle i: FP::measurement on the normals of (seed, stream_offset + c, i)
+//                   (rng_normals: the counter is the particle id, so the draw is the one rng_normals_pair hands the sweeps), or on
+//                   the caller's noise rows, or those rows themselves (noise_is_meas).
+// PRED / MEAS are compiled in or out (either output may be absent).  thread = one particle of one row: the reads run along N in the SoA
+// blocks.  Rows of fewer than 256 particles are packed RPB = 256 / N to a block (N = 100: two rows, 200 of 256 threads; at most 16),
+// longer rows are cut into chunks of 256 along gridDim.y.  The constants [μ(DZ), L(NL)] of a block's rows are staged once per row
+// through LDS by the block's threads (one entry each).  FP is a policy in its dir-0 form: DF / DT are the dimensions of the factor's
+// first / second variable.  No atomics, nothing is shared between rows but the staging barrier: the bits of row c depend on row c alone.
+// ------------------------------------------------------------------------------------------
+constexpr int kDeconvThreads = 256;
+constexpr int kDeconvMaxRows = 16;
+
+// the Pose2Pose2 measurement of two SE(2) points: R_pᵀ (t_q − t_p) and the angle of R_pᵀ R_q, read as residual_pose2pose2 reads its own
+__device__ __forceinline__ void predict_se2(const Se2& P, const Se2& Q, double (&z)[3]) {
+  const double dx = Q.x - P.x, dy = Q.y - P.y;
+  z[0] = P.c * dx + P.s * dy;
+  z[1] = P.c * dy - P.s * dx;
+  const double U11 = P.c * Q.c + P.s * Q.s, U21 = P.c * Q.s - P.s * Q.c;
+  z[2] = fast_atan2(U21, U11);
+}
+
+template <class FP, bool PRED, bool MEAS>
+__global__ void __launch_bounds__(kDeconvThreads) k_deconv(const DeconvArgs a, int H, int RPB, uint32_t magic) {
+  static_assert(PRED || MEAS, "an output");
+  static_assert(FP::NK == FP::DZ + FP::NL, "the staged image is [mu, L]");
+  constexpr int SLP = FP::NK | 1;   // (odd: the rows of a block start in different banks)
+  __shared__ double s_K[MEAS ? kDeconvMaxRows * SLP : 1];
+  const int tid = threadIdx.x;
+  const int N = a.N;
+  const int c0 = blockIdx.x * RPB;
+  // ---- this thread's (row, particle): idle threads shadow the block's last row / particle 0 and store nothing
+  const int lr_raw = (int)(((uint32_t)tid * magic) >> 16);   // tid / H
+  const int j = tid - lr_raw * H;
+  const int i = (int)blockIdx.y * kDeconvThreads + j;
+  const bool live = lr_raw < RPB && c0 + lr_raw < a.n_rows && i < N;
+  const int lr = lr_raw < RPB ? lr_raw : RPB - 1;
+  const int c = min(c0 + lr, a.n_rows - 1);
+  const int ii = i < N ? i : 0;
+  [[maybe_unused]] int va, vb;
+  if (a.rows4) {
+    const int4 row = *row_ptr(reinterpret_cast<const int4*>(a.rows4), c, 16u);
+    va = row.z; vb = row.w;
+  } else {
+    va = a.var_a ? a.var_a[c] : c;
+    vb = a.var_b ? a.var_b[c] : c;
+  }
+  if constexpr (MEAS) {
+    const bool given = a.noise != nullptr && a.noise_is_meas != 0;   // (uniform) the rows ARE the samples: no constants are read
+    if (!given) {
+      for (int e = tid; e < RPB * FP::NK; e += kDeconvThreads) {
+        const int r = e / FP::NK, q = e - r * FP::NK;
+        const int cr = min(c0 + r, a.n_rows - 1);
+        const int fr = a.rows4 ? a.rows4[4 * (size_t)cr] : (a.factor ? a.factor[cr] : cr);
+        s_K[r * SLP + q] = q < FP::DZ ? a.mu[(size_t)fr * FP::DZ + q] : a.L[(size_t)fr * FP::NL + (q - FP::DZ)];
+      }
+    }
+    double xi[FP::DZ], z[FP::DZ];
+    if (a.noise) {
+      const double* __restrict__ nb = a.noise + (size_t)c * FP::DZ * N;
+#pragma unroll
+      for (int d = 0; d < FP::DZ; ++d) xi[d] = nb[(size_t)d * N + ii];
+    } else {
+      rng_normals<FP::DZ>(a.seed, a.stream_offset + (uint64_t)(uint32_t)c, (uint32_t)ii, xi);
+    }
+    __syncthreads();
+    if (given) {
+#pragma unroll
+      for (int d = 0; d < FP::DZ; ++d) z[d] = xi[d];
+    } else {
+      const typename FP::Consts K = FP::from_lds(s_K + lr * SLP, 0);
+      FP::measurement(K, xi, z);
+    }
+    if (live) {
+      double* __restrict__ mb = a.meas + (size_t)c * FP::DZ * N;
+#pragma unroll
+      for (int d = 0; d < FP::DZ; ++d) mb[(size_t)d * N + i] = z[d];
+    }
+  }
+  if constexpr (PRED) {
+    const double* __restrict__ ab = a.bel_a + (size_t)va * FP::DF * N;
+    const double* __restrict__ bb = a.bel_b + (size_t)vb * FP::DT * N;
+    double pa[FP::DF], pb[FP::DT], z[FP::DZ];
+#pragma unroll
+    for (int d = 0; d < FP::DF; ++d) pa[d] = ab[(size_t)d * N + ii];
+#pragma unroll
+    for (int d = 0; d < FP::DT; ++d) pb[d] = bb[(size_t)d * N + ii];
+    FP::predict(pa, pb, z);
+    if (live) {
+      double* __restrict__ pr = a.pred + (size_t)c * FP::DZ * N;
+#pragma unroll
+      for (int d = 0; d < FP::DZ; ++d) pr[(size_t)d * N + i] = z[d];
+    }
+  }
+}
+
+template <class FP>
+static hipError_t launch_deconv_t(const DeconvArgs& a, hipStream_t s) {
+  if (a.n_rows <= 0) return hipSuccess;
+  if (a.N < 1 || (!a.pred && !a.meas)) return hipErrorInvalidValue;
+  const int H = a.N < kDeconvThreads ? a.N : kDeconvThreads;
+  int RPB = kDeconvThreads / H;
+  if (RPB > kDeconvMaxRows) RPB = kDeconvMaxRows;
+  const uint32_t magic = (65536u + (uint32_t)H - 1u) / (uint32_t)H;   // tid / H == (tid * magic) >> 16 for tid < 256 (checked below)
+  for (int t = 0; t < kDeconvThreads; ++t) if ((int)(((uint32_t)t * magic) >> 16) != t / H) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)((a.n_rows + RPB - 1) / RPB), (unsigned)((a.N + kDeconvThreads - 1) / kDeconvThreads));
+  if (a.pred && a.meas) hipLaunchKernelGGL((k_deconv<FP, true, true>), grid, dim3(kDeconvThreads), 0, s, a, H, RPB, magic);
+  else if (a.pred)      hipLaunchKernelGGL((k_deconv<FP, true, false>), grid, dim3(kDeconvThreads), 0, s, a, H, RPB, magic);
+  else                  hipLaunchKernelGGL((k_deconv<FP, false, true>), grid, dim3(kDeconvThreads), 0, s, a, H, RPB, magic);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
 template <class FP, int SOLVER, bool LEAN>

@@ -46,6 +46,16 @@ struct BR {
       else z[k] = K.mu[k] - K.sg[k] * (erfc(-xi[k] * 0.70710678118654752440) - 1.0);
     }
   }
+  // the (bearing, range) at which the residual vanishes on the pair (pose, landmark) (k_deconv; DIR 0 names the pair in that order):
+  // atan2 and norm of pl = R(θp)ᵀ (l − p.t), in the expressions of residual_bearingrange.  l == p.t: (fast_atan2(0, 0), 0)
+  __device__ static __forceinline__ void predict(const double (&p)[3], const double (&l)[2], double (&z)[2]) {
+    const Se2 P = se2_from_coords(p[0], p[1], p[2]);
+    const double dx = l[0] - P.x, dy = l[1] - P.y;
+    const double plx = P.c * dx + P.s * dy;
+    const double ply = P.c * dy - P.s * dx;
+    z[0] = fast_atan2(ply, plx);
+    z[1] = fast_sqrt(plx * plx + ply * ply);
+  }
   __device__ static __forceinline__ void canonical(double (&t)[DT]) { if constexpr (DT == 3) t[2] = wrap_pi(t[2]); }
   // landmark direction: unique root, only the start-dependent solvers cycle; pose direction: every solver starts from the belief point
   __device__ static __forceinline__ bool needs_cycles(int solver, const Consts&) {

@@ -59,6 +59,18 @@ struct P3P3 {
       z[k] = s;
     }
   }
+  // the measurement at which the residual vanishes on the pair (k_deconv): z_t = R_pᵀ (q.t − p.t), z_ω = Log(R_pᵀ R_q), the principal
+  // rotation vector; R_p is formed once, as a unit quaternion, and serves both parts
+  __device__ static __forceinline__ void predict(const double (&p)[6], const double (&q)[6], double (&z)[6]) {
+    double qp[4], qq[4], e[4], v[3];
+    quat_exp(&p[3], qp); quat_exp(&q[3], qq);
+    const double cp[4] = {qp[0], -qp[1], -qp[2], -qp[3]};
+    const double d[3] = {q[0] - p[0], q[1] - p[1], q[2] - p[2]};
+    quat_rot(cp, d, v);
+    z[0] = v[0]; z[1] = v[1]; z[2] = v[2];
+    quat_cmul(qp, qq, e);
+    quat_log(e, &z[3]);
+  }
   __device__ static __forceinline__ void canonical(double (&)[6]) {}   // finalize() writes the principal rotation vector
   __device__ static __forceinline__ bool needs_cycles(int solver, const Consts& K) {
     return solver == kSolverNelderMead && K.dir != kDirPrior;

@@ -55,6 +55,10 @@ struct P2P2 {
     z[1] = K.mu[1] + K.L[1] * xi[0] + K.L[2] * xi[1];
     z[2] = K.mu[2] + K.L[3] * xi[0] + K.L[4] * xi[1] + K.L[5] * xi[2];
   }
+  // the measurement at which r(z; p, q) vanishes (k_deconv): z = vee(log(p⁻¹ ∘ q)) in the uncoupled chart the residual uses
+  __device__ static __forceinline__ void predict(const double (&p)[3], const double (&q)[3], double (&z)[3]) {
+    predict_se2(se2_from_coords(p[0], p[1], p[2]), se2_from_coords(q[0], q[1], q[2]), z);
+  }
   __device__ static __forceinline__ void canonical(double (&t)[3]) { t[2] = wrap_pi(t[2]); }
   // do the inflation cycles (entropy + re-solve) apply?  Only to Nelder-Mead, whose answer (to its g_tol of 1e-8 on the simplex spread)
   // depends on where it starts.  CLOSED_FORM and NEWTON return the unique root directly; GAUSS_NEWTON iterates on the residual functor
@@ -291,6 +295,12 @@ hipError_t launch_sweep_pose2(const ConvArgs* p2p2, const ConvArgs* br1, const C
     else      hipLaunchKernelGGL((k_sweep_fused<false, kSolverClosedForm>), dim3(nb), dim3(256), 0, s, f);
   }
   return hipGetLastError();
+}
+// approxDeconv of the two families of this unit (k_deconv, rome_conv.hpp)
+hipError_t launch_deconv_pose2(int family, const DeconvArgs& a, hipStream_t s) {
+  if (family == kDeconvPose2Pose2) return launch_deconv_t<P2P2>(a, s);
+  if (family == kDeconvBearingRange) return launch_deconv_t<BR<0>>(a, s);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace rome

@@ -4,5 +4,8 @@
 namespace rome {
 
 hipError_t launch_conv_pose3pose3(const ConvArgs& a, int solver, hipStream_t s) { return launch_solver<P3P3>(a, solver, s); }
+hipError_t launch_deconv_pose3(int family, const DeconvArgs& a, hipStream_t s) {
+  return family == kDeconvPose3Pose3 ? launch_deconv_t<P3P3>(a, s) : hipErrorInvalidValue;
+}
 
 }  // namespace rome

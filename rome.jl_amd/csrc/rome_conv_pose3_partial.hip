@@ -75,6 +75,22 @@ struct P3XYY : P3Partial<0, 1, 5> {
     z[1] = K.mu[1] + K.L[1] * xi[0] + K.L[2] * xi[1];
     z[2] = K.mu[2] + K.L[3] * xi[0] + K.L[4] * xi[1] + K.L[5] * xi[2];
   }
+  __device__ static __forceinline__ Consts from_lds(const double* sk, int dr) {   // (k_deconv)
+    Consts K;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) K.mu[k] = sk[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) K.L[k] = sk[3 + k];
+    K.dir = dr;
+    return K;
+  }
+  // the measurement at which the residual vanishes on the pair (k_deconv): the Pose2Pose2 measurement of the two SE(2) projections
+  __device__ static __forceinline__ void predict(const double (&p)[6], const double (&q)[6], double (&z)[3]) {
+    double cp[3], cq[3], u[3];
+    so3_col1_dz(p[3], p[4], p[5], cp, u);
+    so3_col1_dz(q[3], q[4], q[5], cq, u);
+    predict_se2(se2_of_pose3(p[0], p[1], cp[0], cp[1]), se2_of_pose3(q[0], q[1], cq[0], cq[1]), z);
+  }
   __device__ static __forceinline__ bool needs_cycles(int solver, const Consts&) { return solver == kSolverNelderMead; }
   // F = the fixed pose's projection; ψ*; a = t* (dir 0) or q.t_xy (dir 1: t* follows the iterate's own yaw)
   struct Prep { Se2 F; double psi, ax, ay; };
@@ -233,6 +249,22 @@ struct P3ROT : P3Partial<3, 4, 5> {
     z[1] = K.mu[1] + K.L[1] * xi[0] + K.L[2] * xi[1];
     z[2] = K.mu[2] + K.L[3] * xi[0] + K.L[4] * xi[1] + K.L[5] * xi[2];
   }
+  __device__ static __forceinline__ Consts from_lds(const double* sk, int dr) {   // (k_deconv)
+    Consts K;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) K.mu[k] = sk[k];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) K.L[k] = sk[3 + k];
+    K.dir = dr;
+    return K;
+  }
+  // the measurement at which the residual vanishes on the pair (k_deconv): Log(R_pᵀ R_q), the principal rotation vector
+  __device__ static __forceinline__ void predict(const double (&p)[6], const double (&q)[6], double (&z)[3]) {
+    double qp[4], qq[4], e[4];
+    quat_exp(&p[3], qp); quat_exp(&q[3], qq);
+    quat_cmul(qp, qq, e);
+    quat_log(e, z);
+  }
   __device__ static __forceinline__ bool needs_cycles(int solver, const Consts&) { return solver == kSolverNelderMead; }
   struct Prep { double qa[4]; };
   __device__ static __forceinline__ Prep prepare(const Consts& K, const double (&z)[3], const double (&fxc)[6]) {
@@ -305,5 +337,10 @@ struct P3ROT : P3Partial<3, 4, 5> {
 hipError_t launch_conv_pose3pose3xyyaw(const ConvArgs& a, int solver, hipStream_t s) { return launch_solver<P3XYY>(a, solver, s); }
 hipError_t launch_conv_pose3pose3rotation(const ConvArgs& a, int solver, hipStream_t s) { return launch_solver<P3ROT>(a, solver, s); }
 hipError_t launch_conv_priorpose3zrp(const ConvArgs& a, hipStream_t s) { return launch_ppl<P3ZRP, kSolverClosedForm>(a, s); }
+hipError_t launch_deconv_pose3_partial(int family, const DeconvArgs& a, hipStream_t s) {
+  if (family == kDeconvPose3Pose3XYYaw) return launch_deconv_t<P3XYY>(a, s);
+  if (family == kDeconvPose3Pose3Rotation) return launch_deconv_t<P3ROT>(a, s);
+  return hipErrorInvalidValue;
+}
 
 }  // namespace rome

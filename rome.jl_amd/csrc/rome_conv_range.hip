@@ -47,6 +47,11 @@ struct RangeBase {
     if (K.sg >= 0.0) z[0] = K.mu + K.sg * xi[0];
     else z[0] = K.mu - K.sg * (erfc(-xi[0] * 0.70710678118654752440) - 1.0);
   }
+  __device__ static __forceinline__ Consts from_lds(const double* sk, int) { Consts K; K.mu = sk[0]; K.sg = sk[1]; return K; }   // (k_deconv)
+  // the range at which the residual vanishes on the pair (k_deconv): ‖lm − x‖, a pose's heading is not read
+  __device__ static __forceinline__ void predict(const double (&x)[DF], const double (&lm)[DT], double (&z)[1]) {
+    z[0] = range_norm(lm[0] - x[0], lm[1] - x[1]);
+  }
   __device__ static __forceinline__ void canonical(double (&)[DT]) {}   // (a Pose2 target's heading is passed through bit for bit)
   __device__ static __forceinline__ bool needs_cycles(int, const Consts&) { return true; }
   struct Aux {};
@@ -147,6 +152,12 @@ struct PB : RangeBase<DIR == 0 ? 3 : 2, DIR == 0 ? 2 : 3> {
   using typename Base::Consts;
   using typename Base::Aux;
   static constexpr int DF = Base::DF, DT = Base::DT;
+  // the bearing at which the residual vanishes on the pair (pose, landmark) (k_deconv): the bearing row of BR<0>::predict
+  __device__ static __forceinline__ void predict(const double (&p)[3], const double (&l)[2], double (&z)[1]) {
+    const Se2 P = se2_from_coords(p[0], p[1], p[2]);
+    const double dx = l[0] - P.x, dy = l[1] - P.y;
+    z[0] = fast_atan2(P.c * dy - P.s * dx, P.c * dx + P.s * dy);
+  }
   __device__ static __forceinline__ void canonical(double (&t)[DT]) { BR<DIR>::canonical(t); }
   __device__ static __forceinline__ void add_entropy(double (&t)[DT], Aux&, double spread, const double (&u)[DT]) {
     typename BR<DIR>::Aux none;
@@ -214,6 +225,12 @@ hipError_t launch_conv_pose2point2range(const ConvArgs& a, int solver, hipStream
 // bearing-only factor: a ray / a two-parameter family of roots (kUniqueRoot = false) -> k_conv / k_conv_big only
 hipError_t launch_conv_pose2point2bearing(const ConvArgs& a, int solver, hipStream_t s) {
   return a.dir_all == 0 ? launch_solver<PB<0>>(a, solver, s) : launch_solver<PB<1>>(a, solver, s);
+}
+hipError_t launch_deconv_range(int family, const DeconvArgs& a, hipStream_t s) {
+  if (family == kDeconvBearing) return launch_deconv_t<PB<0>>(a, s);
+  if (family == kDeconvPoint2Point2Range) return launch_deconv_t<P2R>(a, s);
+  if (family == kDeconvPose2Point2Range) return launch_deconv_t<PPR<0>>(a, s);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace rome

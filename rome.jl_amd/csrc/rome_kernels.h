@@ -63,6 +63,33 @@ hipError_t launch_sample_priorpose2(const ConvArgs& a, hipStream_t s);
 hipError_t launch_sample_priorpose3(const ConvArgs& a, hipStream_t s);
 hipError_t launch_sample_priorpoint2(const ConvArgs& a, hipStream_t s);
 
+// approxDeconv (k_deconv, rome_conv.hpp): row c pairs particle i of block var_a[c] of bel_a with particle i of block var_b[c] of bel_b.
+// pred [C][dz][N] = the measurement the pair predicts (Policy::predict), meas [C][dz][N] = what the convolution of row c draws
+// (Policy::measurement on the normals of (seed, stream_offset + c, i)); either may be null, not both.  All pointers are DEVICE pointers.
+struct DeconvArgs {
+  int n_rows, N;
+  const int32_t* rows4;       // [C][4] (factor, unused, var_a, var_b), or nullptr -> the three columns
+  const int32_t* factor;      // [C] row of mu / L, or nullptr (identity)
+  const int32_t* var_a;       // [C] block of bel_a, or nullptr (identity)
+  const int32_t* var_b;       // [C] block of bel_b, or nullptr (identity)
+  const double* mu;           // [F][dz]
+  const double* L;            // the convolution's table of the family
+  const double* bel_a;
+  const double* bel_b;
+  const double* noise;        // [C][dz][N] as ConvArgs::noise, or nullptr -> in-kernel Philox
+  int noise_is_meas;
+  double* pred;
+  double* meas;
+  uint64_t seed, stream_offset;
+};
+enum { kDeconvPose2Pose2, kDeconvBearingRange, kDeconvBearing, kDeconvPoint2Point2Range, kDeconvPose2Point2Range, kDeconvPose3Pose3,
+       kDeconvPose3Pose3XYYaw, kDeconvPose3Pose3Rotation, kDeconvFamilies };
+// one per family unit (the unit that owns the policy instantiates k_deconv on it); a family of another unit: hipErrorInvalidValue
+hipError_t launch_deconv_pose2(int family, const DeconvArgs& a, hipStream_t s);           // Pose2Pose2, bearing-range
+hipError_t launch_deconv_range(int family, const DeconvArgs& a, hipStream_t s);           // bearing, both range factors
+hipError_t launch_deconv_pose3(int family, const DeconvArgs& a, hipStream_t s);           // Pose3Pose3
+hipError_t launch_deconv_pose3_partial(int family, const DeconvArgs& a, hipStream_t s);   // Pose3Pose3XYYaw, Pose3Pose3Rotation
+
 // residual-only rows (the KAT entry points): r[i] = residual of kind `kind` at (z[i], a[i], b[i]); b is not read by the priors; pts: the
 // pose rows of a / b are native points (Pose2: 6, Pose3: 12 doubles), not coordinates -- the kinds that read a heading or a rotation only
 enum { kResPose2Pose2, kResPriorPose2, kResBearingRange, kResBearing, kResPose3Pose3, kResPose3Pose3XYYaw, kResPose3Pose3Rotation,

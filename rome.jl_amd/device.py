@@ -592,6 +592,92 @@ class DeviceGraph:
                    self.ctx.handle)
         return out
 
+    # ---- deconvolution (rome_deconv_dev): each factor of a family ONCE, whichever of its `to` / `from` records is named ----
+    # record name -> (packed table, record holding its mu / L, columns of the first / second variable, their types, ROME_DECONV_*, dz,
+    # whether rome_mmd_dev serves the measurement manifold: dim 3 = SE(2) coordinates, dim 6 = SE(3) coordinates)
+    _DECONV = {
+        "p2p2": ("p2p2", "p2p2", "var_from", "var_to", Pose2, Pose2, _lib.DECONV_POSE2POSE2, 3, True),
+        "br1": ("br", "br1", "pose", "point", Pose2, Point2, _lib.DECONV_POSE2POINT2BR, 2, False),
+        "pb1": ("pbear", "pb1", "pose", "point", Pose2, Point2, _lib.DECONV_POSE2POINT2BEARING, 1, False),
+        "p2rng": ("p2rng", "p2rng", "from", "to", Point2, Point2, _lib.DECONV_POINT2POINT2RANGE, 1, False),
+        "pprng1": ("pprng", "pprng1", "pose", "point", Pose2, Point2, _lib.DECONV_POSE2POINT2RANGE, 1, False),
+        "p3p3": ("p3p3", "p3p3", "var_from", "var_to", Pose3, Pose3, _lib.DECONV_POSE3POSE3, 6, True),
+        "p3xyy": ("p3xyy", "p3xyy", "var_from", "var_to", Pose3, Pose3, _lib.DECONV_POSE3POSE3XYYAW, 3, True),
+        "p3rot": ("p3rot", "p3rot", "var_from", "var_to", Pose3, Pose3, _lib.DECONV_POSE3POSE3ROTATION, 3, False),
+    }
+    _DECONV.update(br0=_DECONV["br1"], pb0=_DECONV["pb1"], pprng0=_DECONV["pprng1"])
+
+    def _deconv_family(self, kind, who):
+        if kind not in self.fams:
+            raise KeyError("%s: the graph has no family record %r (it has %s)" % (who, kind, ", ".join(self.fams) or "none"))
+        if kind not in self._DECONV:
+            raise TypeError("%s: family %r holds prior rows; the deconvolution of a prior is the belief itself" % (who, kind))
+        spec = self._DECONV[kind]
+        tab = getattr(self.packed, spec[0])
+        if "alt" in tab and (np.asarray(tab["alt"]) >= 0).any():
+            raise ValueError("%s: family %r has multihypo rows; a deconvolution pairs one first with one second variable" % (who, kind))
+        return spec, tab
+
+    def deconv_labels(self, kind):
+        """the factor labels of DeviceGraph.deconv(opts, kind)'s rows, in row order"""
+        return list(self._deconv_family(kind, "DeviceGraph.deconv_labels")[1]["labels"])
+
+    def deconv(self, opts, kind, pred=None, meas=None):
+        """rome_deconv_dev over the factors of the family record `kind` of self.fams, each factor once (row f = factor f of the family's
+        table; the `to` and `from` records of a family name the same factors): -> (pred, meas), each [F, dz, N] on the device.
+        pred[f] = the measurement that particle pair i of the factor's two beliefs predicts, meas[f] = the sample the convolution of
+        stream opts.stream_offset + f draws (include/rome_mi355.h).  pred / meas: a tensor to write into, None to allocate one, False
+        to skip that output.  One launch, no synchronisation, capturable (with both tensors passed).  Raises on a family of prior
+        rows (TypeError) and on one with multihypo rows (ValueError)."""
+        torch = self.torch
+        (_, rname, ca, cb, vta, vtb, fam, dz, _), tab = self._deconv_family(kind, "DeviceGraph.deconv")
+        if pred is False and meas is False:
+            raise ValueError("DeviceGraph.deconv: one of pred / meas must be asked for")
+        F = tab["F"]
+        cache = self.__dict__.setdefault("_deconv_rows", {})
+        if rname not in cache:
+            rows = np.stack([np.arange(F, dtype=np.int32), np.zeros(F, np.int32), np.asarray(tab[ca], np.int32), np.asarray(tab[cb], np.int32)], axis=1)
+            cache[rname] = torch.as_tensor(np.ascontiguousarray(rows), dtype=torch.int32, device=self.device)
+        rows4, rec = cache[rname], self.fams[rname]
+        outs = []
+        for name, x in (("pred", pred), ("meas", meas)):
+            if x is None:
+                x = torch.empty((F, dz, self.N), dtype=torch.float64, device=self.device)
+            elif x is not False and (tuple(x.shape) != (F, dz, self.N) or x.dtype != torch.float64 or x.device != self.device or not x.is_contiguous()):
+                raise ValueError("DeviceGraph.deconv: `%s` must be a contiguous float64 tensor of shape %s on %s" % (name, (F, dz, self.N), self.device))
+            outs.append(x)
+        ptr = lambda x: None if x is None or x is False else x.data_ptr()
+        t = _lib.DeconvTable(n_rows=F, rows4=rows4.data_ptr(), mu=rec["mu"].data_ptr(), L=rec["L"].data_ptr(), bel_a=self.bel[vta].data_ptr(),
+                             bel_b=self.bel[vtb].data_ptr(), pred=ptr(outs[0]), meas=ptr(outs[1]))
+        self._bind_stream()
+        _lib.check(self._lib.rome_deconv_dev(self.ctx.handle, C.byref(opts), fam, C.byref(t)), self.ctx.handle)
+        return tuple(None if x is False else x for x in outs)
+
+    def factor_mmd(self, opts, kind, bw=0.001, out=None):
+        """[F] consistency scores of the factors of family record `kind`: rome_mmd_dev between what each factor's two beliefs predict
+        for its measurement and N samples of the measurement it carries (deconv, then mmd on the measurement manifold; the reference's
+        test/testBasicPose2Conv.jl:51-56 accepts a factor at < 0.001).  A factor at odds with the solved beliefs -- a wrong loop
+        closure -- stands out.  Two launches, no host round trip, capturable (pass `out`; the two [F, dz, N] work tensors are kept with
+        the graph).  Families whose measurement manifold rome_mmd_dev does not serve (R, the circle, circle x R, SO(3): the range,
+        bearing, bearing-range and rotation factors) raise TypeError."""
+        torch = self.torch
+        spec, tab = self._deconv_family(kind, "DeviceGraph.factor_mmd")
+        rname, dz, ok = spec[1], spec[7], spec[8]
+        if not ok:
+            raise TypeError("DeviceGraph.factor_mmd: the measurement manifold of family %r (dz = %d) is not one rome_mmd_dev serves" % (kind, dz))
+        F = tab["F"]
+        buf = self.__dict__.setdefault("_deconv_buf", {})
+        if rname not in buf:
+            buf[rname] = tuple(torch.empty((F, dz, self.N), dtype=torch.float64, device=self.device) for _ in range(2))
+        pred, meas = self.deconv(opts, kind, *buf[rname])
+        if out is None:
+            out = torch.empty((F,), dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (F,) or out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous():
+            raise ValueError("DeviceGraph.factor_mmd: `out` must be a contiguous float64 tensor of shape (%d,) on %s" % (F, self.device))
+        _lib.check(self._lib.rome_mmd_dev(self.ctx.handle, dz, F, self.N, pred.data_ptr(), None, self.N, meas.data_ptr(), None, None, float(bw),
+                                          out.data_ptr(), None), self.ctx.handle)
+        return out
+
     def kde_bandwidths(self, vartype, tol_euclid=0.0, tol_circular=0.0):
         """[V, dim] leave-one-out likelihood bandwidths of every belief of one variable type (`manikde!` rule), on device."""
         self._bind_stream()

@@ -732,6 +732,36 @@ function mmd(M, a::Vector{P}, b::Vector{P}; bw::AbstractVector{<:Real}=[0.001], 
   out[1]
 end
 
+# ---- approxDeconv on the device (rome_deconv; IIF's approxDeconv(fg, flabel) as test/testBasicPose2Conv.jl:51 calls it, restated: the
+# header says what is unchecked) --------------------------------------------------------------------------------------
+# -> (pred, meas), each dz x N measurement coordinates: pred[:, i] is the measurement at which the factor's residual vanishes on particle
+# i of its first and particle i of its second variable, meas the N samples the convolution of the factor draws (Philox stream
+# stream_offset).  family: ROME_DECONV_* of the header; the two variables' points are passed as they are (ROME_LAYOUT_AOS_POINTS).
+const _DECONV_FAMILY = Dict{Any,Tuple{Int32,Int}}(Pose2Pose2 => (Int32(0), 3), Pose3Pose3 => (Int32(5), 6))
+function deconv(fg, f::Union{Pose2Pose2,Pose3Pose3}, apts::Vector{P}, bpts::Vector{P}; stream_offset::Integer=0) where {P}
+  fam, dz = _DECONV_FAMILY[typeof(f).name.wrapper]
+  d0 = default_opts(fg; stream_offset)
+  o = RomeOpts(d0.n_particles, d0.solver, d0.max_iters, d0.inflate_cycles, d0.tol, d0.inflation, d0.seed, d0.stream_offset, 2, 0, d0.spread_nh, d0.nullhypo)
+  N = length(apts)
+  N == length(bpts) == o.n_particles || error("approxDeconv: both variables need $(o.n_particles) points")
+  μ = collect(Float64, mean(f.Z)); Σ = collect(Float64, cov(f.Z))'
+  pred = Matrix{Float64}(undef, dz, N); meas = Matrix{Float64}(undef, dz, N)
+  GC.@preserve μ Σ apts bpts pred meas begin
+    check(ccall((:rome_deconv, LIB), Cint,
+      (Ptr{Cvoid}, Ref{RomeOpts}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+      ctx().h, o, fam, 1, μ, Σ, Ptr{Float64}(pointer(apts)), Ptr{Float64}(pointer(bpts)), C_NULL, pred, meas))
+  end
+  pred, meas
+end
+function approxDeconv(dfg::AbstractDFG, flabel::Symbol; solveKey::Symbol=:default)
+  fc = getFactor(dfg, flabel)
+  f = getFactorType(fc)
+  f isa Union{Pose2Pose2,Pose3Pose3} || error("approxDeconv: factor type $(typeof(f)) is not served by this shim (Pose2Pose2, Pose3Pose3)")
+  vars = getVariableOrder(fc)
+  length(vars) == 2 || error("approxDeconv: multihypo factors are not served")
+  deconv(dfg, f, getVal(dfg, vars[1]; solveKey), getVal(dfg, vars[2]; solveKey))
+end
+
 # ---- stage 2 of the partial-aware product (rome_product_partial; include/rome_mi355.h, DESIGN.md §12d) -----------
 # prop: N x dim x rows, bel: N x dim x V (exactly the C side's SoA blocks [.][dim][N]); bel holds the product of the full proposals on
 # entry and is updated in place.  The task tables are 0-based, as the header defines them: task t rewrites coordinate task_coord[t] of
