@@ -191,10 +191,9 @@ __device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {  // (0,1]
 }
 
 // The radius argument h = -ln u1 of box_muller (below) for the radius word wa; its own function so that tests/hip/sqrt32_check.hip can
-// walk every wa.
-__device__ __forceinline__ float box_muller_h(uint32_t wa) {
+// walk every wa; box_muller_h_of_x takes x = float(wa) + 1 (box_muller_field below forms it in one conversion).
+__device__ __forceinline__ float box_muller_h_of_x(float x) {
 #pragma clang fp contract(off)
-  const float x = (float)wa + 1.0f;
   const uint32_t xb = __float_as_uint(x);
   const float ke = (float)(int32_t)(159u - (xb >> 23));
   const float t = __uint_as_float((xb & 0x007FFFFFu) | 0x3F800000u) - 1.5f;
@@ -207,6 +206,25 @@ __device__ __forceinline__ float box_muller_h(uint32_t wa) {
   p = __builtin_fmaf(p, t, 0x1.555544p-1f);
   p = __builtin_fmaf(p, t, 0x1.9f324cp-2f);
   return __builtin_fmaf(ke, 0x1.62e43p-1f, -p);
+}
+__device__ __forceinline__ float box_muller_h(uint32_t wa) {
+#pragma clang fp contract(off)
+  return box_muller_h_of_x((float)wa + 1.0f);
+}
+// The direction and sign half of box_muller (below): a = the angle in [-π/4, π/4), rr the radius, bits 31 / 30 of sb the two signs.
+__device__ __forceinline__ void box_muller_finish(float rr, float a, uint32_t sb, double* n0, double* n1) {
+#pragma clang fp contract(off)
+  const float z = a * a;
+  float sp = __builtin_fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f);
+  sp = __builtin_fmaf(z, sp, -1.6666654611e-1f);
+  const float sn = __builtin_fmaf(z * a, sp, a);
+  float cp = __builtin_fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f);
+  cp = __builtin_fmaf(z, cp, 4.166664568298827e-2f);
+  const float cs = __builtin_fmaf(z * z, cp, __builtin_fmaf(z, -0.5f, 1.0f));
+  // single-precision products, signs by bit 31 of sb -> n0 and bit 30 -> n1, converted once: the draws are floats
+  const float m0 = rr * (cs - sn), m1 = rr * (cs + sn);
+  *n0 = (double)__uint_as_float(__float_as_uint(m0) ^ (sb & 0x80000000u));
+  *n1 = (double)__uint_as_float(__float_as_uint(m1) ^ ((sb << 1) & 0x80000000u));
 }
 
 // One Box-Muller pair from two Philox words.  The transform is defined in IEEE single-precision operations (explicit fmaf
@@ -225,19 +243,41 @@ __device__ __forceinline__ void box_muller(uint32_t wa, uint32_t wb, double* n0,
   // 2.7e-7 of 2^32: the polynomial's error) or at least 2^-47 (ke·ln2 and p are multiples of 2^-47): where the select takes the root
   // its argument is normal, far above 2^-96 (the second pass of tests/hip/sqrt32_check.hip runs every radius word through this h)
   const float rr = h > 0.0f ? sqrt32_rn_normal(h) : 0.0f;
-  const float a = (float)(int32_t)(wb << 2) * 0x1.921fb6p-32f;
-  const float z = a * a;
-  float sp = __builtin_fmaf(z, -1.9515295891e-4f, 8.3321608736e-3f);
-  sp = __builtin_fmaf(z, sp, -1.6666654611e-1f);
-  const float sn = __builtin_fmaf(z * a, sp, a);
-  float cp = __builtin_fmaf(z, 2.443315711809948e-5f, -1.388731625493765e-3f);
-  cp = __builtin_fmaf(z, cp, 4.166664568298827e-2f);
-  const float cs = __builtin_fmaf(z * z, cp, __builtin_fmaf(z, -0.5f, 1.0f));
-  // single-precision products, signs by bit 31 of wb -> n0 and bit 30 -> n1, converted once: the draws are floats
-  const float m0 = rr * (cs - sn), m1 = rr * (cs + sn);
-  *n0 = (double)__uint_as_float(__float_as_uint(m0) ^ (wb & 0x80000000u));
-  *n1 = (double)__uint_as_float(__float_as_uint(m1) ^ ((wb << 1) & 0x80000000u));
+  box_muller_finish(rr, (float)(int32_t)(wb << 2) * 0x1.921fb6p-32f, wb, n0, n1);
 }
+
+// box_muller on the 21-bit fields of the Pose2 draw (rng_normals<3> below).  A field f enters box_muller as the word (f << 11) | 0x400,
+// so on this path the radius and the angle are functions of 2^21 inputs each, and any sequence that returns the same bits on all of
+// them IS the same function.  Every replacement below was decided by running all 2^21 fields, not by an error bound: on the host for
+// the IEEE operations (tests/test_field_draw_host.py), in one launch for the whole pair and the root (tests/hip/field_draw_check.hip).
+//
+// sqrt32_field: the radius root for the h = box_muller_h((f << 11) | 0x400) of those fields.  No `h > 0` select: h is positive for every
+// field, smallest 2^-24 at f = 2^21 - 1, largest 15.25 (enumerated) -- normal and far above sqrt32_rn_normal's 2^-96.  The hardware
+// reciprocal root and ONE residual step: on 0 of the 2^21 fields does it differ from sqrt32_rn_normal(h) (on 604 816 without the step);
+// five instructions for nine.  NOT a square root for other arguments.
+__device__ __forceinline__ float sqrt32_field(float h) {
+#pragma clang fp contract(off)
+  const float y = __builtin_amdgcn_rsqf(h);
+  const float s = h * y;
+  const float r = __builtin_fmaf(-s, s, h);
+  return __builtin_fmaf(r, 0.5f * y, s);
+}
+// ra / aa: words whose TOP 21 bits are the radius / angle field (the low 11 bits are ignored): the same bits as
+// box_muller((ra & 0xFFFFF800) | 0x400, (aa & 0xFFFFF800) | 0x400, n0, n1).
+//   radius  float(word) + 1 with word = (f << 11) | 0x400 exact in single precision is ONE rounding of f·2^11 + 1025: the conversion of
+//           (f << 11) | 0x401 -- one instruction less per pair;
+//   angle   int32(word << 2) = sf·2^13 + 2^12 with sf the signed low 19 bits of the field, so a = (π/4)·2^-31·(sf·2^13 + 2^12) rounded
+//           once = (float(sf) + 0.5)·(π/4)·2^-18 (sf + 0.5 is exact, the scale is the same float times a power of two): a signed bit-field
+//           extract instead of shift, mask and or.
+__device__ __forceinline__ void box_muller_field(uint32_t ra, uint32_t aa, double* n0, double* n1) {
+#pragma clang fp contract(off)
+  const float h = box_muller_h_of_x((float)((ra & 0xFFFFF800u) | 0x401u));
+  const float sf = (float)((int32_t)(aa << 2) >> 13);
+  box_muller_finish(sqrt32_field(h), (sf + 0.5f) * 0x1.921fb6p-19f, aa, n0, n1);
+}
+// Pair C of the Pose2 draw as such a word: hi = x (z), lo = y (w) -> the low 11 bits of hi, then bits 10..1 of lo, on top (one
+// v_alignbit_b32 of (hi, lo << 21); bit 10 of the result is bit 0 of lo, ignored by box_muller_field)
+__device__ __forceinline__ uint32_t field_word_c(uint32_t hi, uint32_t lo) { return __builtin_amdgcn_alignbit(hi, lo << 21, 11); }
 __device__ __forceinline__ u32x4 noise_words(uint64_t seed, uint64_t stream, uint32_t particle, uint32_t b) {
   return philox4x32_10(u32x4{particle, (uint32_t)stream, (uint32_t)(stream >> 32), (kDomainNoise << 16) | b},
                        (uint32_t)seed, (uint32_t)(seed >> 32));
@@ -259,13 +299,7 @@ __device__ __forceinline__ u32x4 noise_words(uint64_t seed, uint64_t stream, uin
 //        by < 2e-6 in Kolmogorov distance (tests/test_host_logic.py); a Pose2 convolution of N = 100 particles costs 50 Philox calls.
 //   D = 1 (range measurements):       the oracle's rule for any other d -- the particle's OWN call (counter = the particle id itself,
 //                                     not the even neighbour), words 0 / 1 -> one Box-Muller pair, its first output
-template <int D>
-__device__ __forceinline__ void normals3_fields(const u32x4& w, uint32_t (&r)[3], uint32_t (&a)[3]) {
-  r[0] = (w.x & 0xFFFFF800u) | 0x400u; a[0] = (w.y & 0xFFFFF800u) | 0x400u;
-  r[1] = (w.z & 0xFFFFF800u) | 0x400u; a[1] = (w.w & 0xFFFFF800u) | 0x400u;
-  r[2] = (w.x << 21) | ((w.y & 0x7FEu) << 10) | 0x400u;
-  a[2] = (w.z << 21) | ((w.w & 0x7FEu) << 10) | 0x400u;
-}
+//        (box_muller_field takes the fields where they lie: on top of x, y, z, w and of the two field_word_c)
 // the normals of particles p_even (even) and p_even + 1 together
 template <int D>
 __device__ __forceinline__ void rng_normals_pair(uint64_t seed, uint64_t stream, uint32_t p_even, double (&oe)[D], double (&oo)[D]) {
@@ -277,11 +311,9 @@ __device__ __forceinline__ void rng_normals_pair(uint64_t seed, uint64_t stream,
     box_muller(wo.x, wo.y, &oo[0], &unused);
   } else if constexpr (D == 3) {
     const u32x4 w = noise_words(seed, stream, p_even, 0u);
-    uint32_t r[3], a[3];
-    normals3_fields<3>(w, r, a);
-    box_muller(r[0], a[0], &oe[0], &oe[1]);
-    box_muller(r[1], a[1], &oo[0], &oo[1]);
-    box_muller(r[2], a[2], &oe[2], &oo[2]);
+    box_muller_field(w.x, w.y, &oe[0], &oe[1]);
+    box_muller_field(w.z, w.w, &oo[0], &oo[1]);
+    box_muller_field(field_word_c(w.x, w.y), field_word_c(w.z, w.w), &oe[2], &oo[2]);
   } else {
     uint32_t ww[2 * D];
 #pragma unroll
@@ -308,11 +340,9 @@ __device__ __forceinline__ void rng_normals(uint64_t seed, uint64_t stream, uint
     box_muller(w.x, w.y, &out[0], &unused);
   } else if constexpr (D == 3) {
     const u32x4 w = noise_words(seed, stream, pe, 0u);
-    uint32_t r[3], a[3];
-    normals3_fields<3>(w, r, a);
-    box_muller(odd ? r[1] : r[0], odd ? a[1] : a[0], &out[0], &out[1]);
+    box_muller_field(odd ? w.z : w.x, odd ? w.w : w.y, &out[0], &out[1]);
     double c, s;
-    box_muller(r[2], a[2], &c, &s);
+    box_muller_field(field_word_c(w.x, w.y), field_word_c(w.z, w.w), &c, &s);
     out[2] = odd ? s : c;
   } else if constexpr (D == 2) {
     const u32x4 w = noise_words(seed, stream, pe, 0u);
