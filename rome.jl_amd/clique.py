@@ -14,7 +14,7 @@ import numpy as np
 from . import _lib, api
 from .device import DeviceGraph
 from .factors import (Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange, Pose3Pose3, PriorPose3, PriorPoint2,
-                      refuse_range, refuse_bearing, refuse_partial3)
+                      refuse_unserved)
 
 # Philox offsets of the families of rome_clique_proposals: DeviceGraph's ("prpt2" is this layer's name for its priorpt2)
 FAMILY_STREAM = {"p2p2": DeviceGraph.STREAM_P2P2, "br1": DeviceGraph.STREAM_BR1, "br0": DeviceGraph.STREAM_BR0, "p3p3": DeviceGraph.STREAM_P3P3,
@@ -47,6 +47,7 @@ class SampledPose2Pose2:
     accepts any SamplableBelief as `Z`): `meas` = label of the Pose2 block with the tangent coordinates (x, y, theta).  This is what the
     relative up-message of a child clique is to its parent (tree.TreeSolver, messages="relative"); only plans over a store take it."""
     variable_types = (Pose2, Pose2)
+    kind, spread = "p2p2", np.eye(3)     # its factor table in CliqueBatch and the identity spread of its rows there
 
     def __init__(self, meas):
         self.meas = meas
@@ -56,6 +57,7 @@ class SampledPose3Pose3:
     """The same for Pose3: `meas` = label of the Pose3 block with the six tangent coordinates (t, omega) of the relative pose (exp_eps is
     uncoupled here, so the coordinates of a composed relative pose are the tangent coordinates the row consumes)."""
     variable_types = (Pose3, Pose3)
+    kind, spread = "p3p3", np.eye(6)
 
     def __init__(self, meas):
         self.meas = meas
@@ -64,6 +66,7 @@ class SampledPose3Pose3:
 class SampledBearingRange:
     """The same for a pose -> landmark relation: `meas` = label of a POINT2 block whose N (x, y) entries are (bearing, range) samples."""
     variable_types = (Pose2, Point2)
+    kind, spread = "br", np.ones(2)
 
     def __init__(self, meas):
         self.meas = meas
@@ -82,10 +85,12 @@ class CliqueBatch:
     stream_ids: {(factor_label, target_label): Philox stream id of the row within its family}: a clique that is a subset of a larger
                table draws what the whole table draws (partition-independent results); default: the row's index."""
 
+    # the families of rome_clique_host as make_fams (csrc/rome_capi_clique.hip) lists them: field prefix, factor-table key, measurement
+    # dimension, spread width (covariance entries; br: the two sigmas), target dimension
+    FAMILIES = (("p2p2", "p2p2", 3, 9, 3), ("br1", "br", 2, 2, 3), ("br0", "br", 2, 2, 2), ("p3p3", "p3p3", 6, 36, 6), ("prpt2", "prpt2", 2, 4, 2))
+
     def __init__(self, fg, pairs, var_index=None, stream_ids=None):
-        refuse_range([fg.getFactor(fl)[2] for fl, _ in pairs], "CliqueBatch")
-        refuse_bearing([fg.getFactor(fl)[2] for fl, _ in pairs], "CliqueBatch")
-        refuse_partial3([fg.getFactor(fl)[2] for fl, _ in pairs], "CliqueBatch")
+        refuse_unserved([fg.getFactor(fl)[2] for fl, _ in pairs], "CliqueBatch")
         self.fg, self.N = fg, fg.N
         self.vars = {Pose2: [], Point2: [], Pose3: []}
         self.vidx = {}
@@ -119,7 +124,7 @@ class CliqueBatch:
             if target not in labels:
                 raise KeyError("%s is not connected to factor %s" % (target, flabel))
             mh = fg.multihypo.get(flabel)
-            alt, hw = -1, 1.0
+            alt, hw, meas, key = -1, 1.0, -1, flabel
             if mh is not None:   # [first, cand1, cand2] with P(cand1) = mh[0], P(cand2) = mh[1]
                 first, c1, c2 = labels
                 if target == first:
@@ -127,48 +132,28 @@ class CliqueBatch:
                 else:
                     own, oth, hw = (c1, c2, mh[0]) if target == c1 else (c2, c1, mh[1])
                     d, other, alt = 0, first, var(oth)
-            meas = -1
-            if isinstance(f, SampledPose2Pose2):
+            elif len(labels) == 1:   # a prior row: its samples are the proposal
+                d, other = 2, target
+            else:
+                d = 0 if labels[1] == target else 1
+                other = labels[d]
+            if isinstance(f, (SampledPose2Pose2, SampledPose3Pose3, SampledBearingRange)):
                 if mh is not None:
                     raise TypeError("a sampled-measurement factor carries no multihypo")
-                d = 0 if labels[1] == target else 1
-                other = labels[0] if d == 0 else labels[1]
-                fam, meas = "p2p2", (var_index[f.meas] if var_index is not None else -2)   # (-2: no store -- only the oracle-side restatement)
-                row = (fac(fam, "<sampled>", np.zeros(3), np.eye(3)), d, var(other), var(target))
-            elif isinstance(f, SampledPose3Pose3):
-                if mh is not None:
-                    raise TypeError("a sampled-measurement factor carries no multihypo")
-                d = 0 if labels[1] == target else 1
-                other = labels[0] if d == 0 else labels[1]
-                fam, meas = "p3p3", (var_index[f.meas] if var_index is not None else -2)
-                row = (fac(fam, "<sampled>", np.zeros(6), np.eye(6)), d, var(other), var(target))
-            elif isinstance(f, SampledBearingRange):
-                if mh is not None:
-                    raise TypeError("a sampled-measurement factor carries no multihypo")
-                d = 0 if labels[1] == target else 1
-                other = labels[0] if d == 0 else labels[1]
-                fam, meas = ("br0" if d == 0 else "br1"), (var_index[f.meas] if var_index is not None else -2)
-                row = (fac("br", "<sampled>", [0.0, 0.0], [1.0, 1.0]), d, var(other), var(target))
-            elif isinstance(f, (Pose2Pose2, Pose3Pose3)):
-                fam = "p2p2" if isinstance(f, Pose2Pose2) else "p3p3"
-                if mh is None:
-                    d = 0 if labels[1] == target else 1
-                    other = labels[0] if d == 0 else labels[1]
-                row = (fac(fam, flabel, f.Z.mu, f.Z.cov), d, var(other), var(target))
-            elif isinstance(f, (PriorPose2, PriorPose3)):
-                fam = "p2p2" if isinstance(f, PriorPose2) else "p3p3"
-                row = (fac(fam, flabel, f.Z.mu, f.Z.cov), 2, var(target), var(target))
-            elif isinstance(f, PriorPoint2):   # landmark prior: its samples are the proposal
-                fam = "prpt2"
-                row = (fac(fam, flabel, f.Z.mu, f.Z.cov), 2, var(target), var(target))
+                meas = var_index[f.meas] if var_index is not None else -2   # (-2: no store -- only the oracle-side restatement)
+                kind, key, mu, spread = f.kind, "<sampled>", np.zeros(len(f.spread)), f.spread
+            elif isinstance(f, (Pose2Pose2, PriorPose2)):
+                kind, mu, spread = "p2p2", f.Z.mu, f.Z.cov
+            elif isinstance(f, (Pose3Pose3, PriorPose3)):
+                kind, mu, spread = "p3p3", f.Z.mu, f.Z.cov
+            elif isinstance(f, PriorPoint2):
+                kind, mu, spread = "prpt2", f.Z.mu, f.Z.cov
             elif isinstance(f, Pose2Point2BearingRange):
-                if mh is None:
-                    d = 0 if labels[1] == target else 1
-                    other = labels[0] if d == 0 else labels[1]
-                fam = "br0" if d == 0 else "br1"
-                row = (fac("br", flabel, [f.bearing.mu, f.range.mu], [f.bearing.sigma, f.range.sigma]), d, var(other), var(target))
+                kind, mu, spread = "br", [f.bearing.mu, f.range.mu], [f.bearing.sigma, f.range.sigma]
             else:
                 raise TypeError("factor type %s is outside the hot path" % type(f).__name__)
+            fam = kind if kind != "br" else "br0" if d == 0 else "br1"
+            row = (fac(kind, key, mu, spread), d, var(other), var(target))
             self.rows[(flabel, target)] = (fam, len(self.fam_rows[fam]))
             self.fam_rows[fam].append(row)
             self.fam_hyp[fam].append((alt, hw, float(nullh.get(flabel, 0.0)) if row[1] != 2 else 0.0))
@@ -199,24 +184,14 @@ class CliqueBatch:
         else:                        # the tables address a device-resident store (UpsolvePlan)
             q.n_pose2 = q.n_point2 = q.n_pose3 = 0
         out = {}
-        for fam, dt in (("p2p2", 3), ("br1", 3), ("br0", 2), ("p3p3", 6), ("prpt2", 2)):
-            out[fam] = np.zeros((len(self.fam_rows[fam]) if with_out else 0, dt, self.N))
-        t = self.tabs
-        q.n_p2p2, q.f_p2p2 = len(self.fam_rows["p2p2"]), len(t["p2p2"]["mu"])
-        q.p2p2_rows4 = ptr(np.array(self.fam_rows["p2p2"], dtype=np.int32).reshape(-1, 4), np.int32)
-        q.p2p2_mu, q.p2p2_cov = ptr(np.array(t["p2p2"]["mu"]).reshape(-1, 3)), ptr(np.array(t["p2p2"]["spread"]).reshape(-1, 9))
-        q.n_br1, q.n_br0, q.f_br = len(self.fam_rows["br1"]), len(self.fam_rows["br0"]), len(t["br"]["mu"])
-        q.br1_rows4 = ptr(np.array(self.fam_rows["br1"], dtype=np.int32).reshape(-1, 4), np.int32)
-        q.br0_rows4 = ptr(np.array(self.fam_rows["br0"], dtype=np.int32).reshape(-1, 4), np.int32)
-        q.br_mu, q.br_sigma = ptr(np.array(t["br"]["mu"]).reshape(-1, 2)), ptr(np.array(t["br"]["spread"]).reshape(-1, 2))
-        q.n_p3p3, q.f_p3p3 = len(self.fam_rows["p3p3"]), len(t["p3p3"]["mu"])
-        q.p3p3_rows4 = ptr(np.array(self.fam_rows["p3p3"], dtype=np.int32).reshape(-1, 4), np.int32)
-        q.p3p3_mu, q.p3p3_cov = ptr(np.array(t["p3p3"]["mu"]).reshape(-1, 6)), ptr(np.array(t["p3p3"]["spread"]).reshape(-1, 36))
-        q.n_prpt2, q.f_prpt2 = len(self.fam_rows["prpt2"]), len(t["prpt2"]["mu"])
-        q.prpt2_rows4 = ptr(np.array(self.fam_rows["prpt2"], dtype=np.int32).reshape(-1, 4), np.int32)
-        q.prpt2_mu, q.prpt2_cov = ptr(np.array(t["prpt2"]["mu"]).reshape(-1, 2)), ptr(np.array(t["prpt2"]["spread"]).reshape(-1, 4))
-        q.out_p2p2, q.out_br1, q.out_br0, q.out_p3p3, q.out_prpt2 = (out[f].ctypes.data_as(C.c_void_p) if out[f].size else None
-                                                                    for f in ("p2p2", "br1", "br0", "p3p3", "prpt2"))
+        for fam, key, dm, ds, dt in self.FAMILIES:   # (br1 and br0 share the factor table `br`: written twice, the same bytes)
+            tb, rows = self.tabs[key], self.fam_rows[fam]
+            out[fam] = np.zeros((len(rows) if with_out else 0, dt, self.N))
+            setattr(q, "n_" + fam, len(rows)); setattr(q, "f_" + key, len(tb["mu"]))
+            setattr(q, fam + "_rows4", ptr(np.array(rows, dtype=np.int32).reshape(-1, 4), np.int32))
+            setattr(q, key + "_mu", ptr(np.array(tb["mu"]).reshape(-1, dm)))
+            setattr(q, key + ("_sigma" if key == "br" else "_cov"), ptr(np.array(tb["spread"]).reshape(-1, ds)))
+            setattr(q, "out_" + fam, out[fam].ctypes.data_as(C.c_void_p) if out[fam].size else None)
         for fam in ("p2p2", "br1", "br0", "p3p3"):
             if any(m == -2 for m in self.fam_meas[fam]):
                 raise TypeError("a sampled-measurement factor needs a device-resident store (UpsolvePlan / tree.TreeLevelPlan)")
@@ -344,9 +319,7 @@ class DeviceStore(LibHandle):
     _destroy = "rome_store_destroy"
 
     def __init__(self, fg, ctx=None, wrap=None, upload=True):
-        refuse_range([f for _, _, f in fg.factors], "DeviceStore")
-        refuse_bearing([f for _, _, f in fg.factors], "DeviceStore")
-        refuse_partial3([f for _, _, f in fg.factors], "DeviceStore")
+        refuse_unserved([f for _, _, f in fg.factors], "DeviceStore")
         self.ctx = ctx or api.default_context()
         self._lib = _lib.load()
         self.fg, self.N = fg, fg.N

@@ -9,7 +9,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .factors import Pose2, Point2, Pose3, Pose2Point2Range, Pose3Pose3XYYaw, PriorPose3ZRP, Pose3Pose3Rotation, partial_coverage
+from .factors import (Pose2, Point2, Pose3, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP,
+                      Pose3Pose3Rotation, partial_coverage)
 from .graph import PackedGraph
 from .api import cholesky_lower
 
@@ -124,7 +125,7 @@ class DeviceGraph:
             # multihypo factors (Pose2Pose2 over two candidates of the second pose): alternative / probability per row, and one
             # more row per such factor -- the proposal of the second candidate -- BEHIND the prior rows (rows 2f+dir and 2F+p keep
             # their meaning).  A table with hypotheses runs on the general kernel, one without on the lean one.
-            hyp = PackedGraph.conv_hypotheses(tab) if "alt" in tab else None
+            hyp = PackedGraph.conv_hypotheses(tab)
             E = 0
             alt = w = None
             if hyp is not None:
@@ -134,10 +135,8 @@ class DeviceGraph:
                 factor = np.concatenate([factor, ex["factor"]]); dr = np.concatenate([dr, ex["dir"]])
                 fixed = np.concatenate([fixed, ex["fixed"]]); target = np.concatenate([target, ex["target"]])
             # nullhypo=p factors: one probability per row (both directions and the extra row of the factor; prior rows 0)
-            nhf = tab.get("nh")
-            nh = None
-            if nhf is not None and np.any(nhf > 0):
-                nh = np.concatenate([np.repeat(nhf, 2), np.zeros(P)] + ([nhf[ex["factor"]]] if E else []))
+            nhf = tab["nh"]
+            nh = nh_or_none(np.concatenate([np.repeat(nhf, 2), np.zeros(P)] + ([nhf[ex["factor"]]] if E else [])))
             # rows4: the four table columns interleaved (one 16-byte scalar load per convolution; selects the lean kernel)
             rec = add(name, entry, vt, vt, 0, stream, target, t(mu, f64), t(cholesky_lower(cov), f64),
                       rows4=np.stack([factor, dr, fixed, target], axis=1), alt=alt, w=w, nh=nh)
@@ -148,15 +147,37 @@ class DeviceGraph:
             if tab["F"]:
                 add(name, entry, None, vt, 0, stream, tab["var"], t(tab["mu"], f64), t(cholesky_lower(tab["cov"]), f64), in_step=in_step)
 
+        def two_way(name, entry, vt, stream, tab, cls):
+            """a relative family launched on its own: both directions of every factor interleaved in ONE record (conv_table), the same
+            coordinates solved towards either variable.  Point2Point2Range: L = the [F][1] sigmas; the others: the packed Cholesky"""
+            F, ranges = tab["F"], cls is Point2Point2Range
+            if F:
+                factor, dr, fixed, target = PackedGraph.range_conv_table(tab) if ranges else PackedGraph.conv_table(tab)
+                add(name, entry, vt, vt, 0, stream, target, t(tab["mu"], f64), t(tab["sigma"] if ranges else cholesky_lower(tab["cov"]), f64),
+                    rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(tab["nh"], 2)), partial=partial_coverage(cls, 0))
+                self.tab[name] = dict(C=2 * F) if ranges else dict(F=F, C=2 * F)
+
+        def pose_point(name1, name0, entry, stream1, stream0, tab, key, cls):
+            """a pose-to-point family of one scalar belief per factor (L = the [F][1] sigmas): dir 1 (landmark -> pose, variable 0 of the
+            factor) then dir 0, two records over the same mu / sigma / nullhypo"""
+            F = tab["F"]
+            if F:
+                fac = np.arange(F, dtype=np.int32)
+                mu, sigma, nh = t(tab["mu"], f64), t(tab["sigma"], f64), dev(nh_or_none(tab["nh"]), f64)
+                for name, d, stream, vf, vt, fx, tg in ((name1, 1, stream1, Point2, Pose2, tab["point"], tab["pose"]),
+                                                        (name0, 0, stream0, Pose2, Point2, tab["pose"], tab["point"])):
+                    add(name, entry, vf, vt, d, stream, tg, mu, sigma, rows4=np.stack([fac, col(d, F), fx, tg], axis=1), nh=nh,
+                        partial=partial_coverage(cls, 1 - d))
+                self.tab[key] = dict(F=F)
+
         col = lambda v, n: np.full(n, v, np.int32)
+        nh_or_none = lambda nh: nh if np.any(nh > 0) else None
         relative("p2p2", "rome_conv_pose2pose2_dev", Pose2, self.STREAM_P2P2, pk.p2p2, pk.prior2)
         if pk.br["F"]:
             b, r0 = pk.br, pk.br["rows0"]
             F, F0 = b["F"], len(r0["factor"])
             mh = bool((b["alt"] >= 0).any())
-            nhb = b.get("nh")
-            if nhb is None or not np.any(nhb > 0):
-                nhb = None
+            nhb = nh_or_none(b["nh"])
             mu, sigma = t(b["mu"], f64), t(b["sigma"], f64)
             br1 = add("br1", "rome_conv_pose2point2br_dev", Point2, Pose2, 1, self.STREAM_BR1, b["pose"], mu, sigma,
                       rows4=np.stack([np.arange(F, dtype=np.int32), col(1, F), b["point"], b["pose"]], axis=1),
@@ -169,62 +190,25 @@ class DeviceGraph:
         if "priorpt2" in self.fams:
             self.tab["priorpt2"] = dict(F=pk.priorpt2["F"])
         relative("p3p3", "rome_conv_pose3pose3_dev", Pose3, self.STREAM_P3P3, pk.p3p3, pk.prior3)
-        # range-only factors (Range2D.jl): their own tables, launched after every other family; L = the [F][1] sigmas
-        nh_or_none = lambda nh: nh if np.any(nh > 0) else None
-        r2 = getattr(pk, "p2rng", None)
-        if r2 is not None and r2["F"]:
-            factor, dr, fixed, target = PackedGraph.range_conv_table(r2)
-            add("p2rng", "rome_conv_point2point2range_dev", Point2, Point2, 0, self.STREAM_P2RNG, target, t(r2["mu"], f64), t(r2["sigma"], f64),
-                rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(r2["nh"], 2)))
-            self.tab["p2rng"] = dict(C=2 * r2["F"])
-        rp = getattr(pk, "pprng", None)
-        if rp is not None and rp["F"]:
-            F = rp["F"]
-            fac = np.arange(F, dtype=np.int32)
-            mu, sigma, nh = t(rp["mu"], f64), t(rp["sigma"], f64), dev(nh_or_none(rp["nh"]), f64)
-            for name, d, stream, vf, vt, fx, tg in (("pprng1", 1, self.STREAM_PPRNG1, Point2, Pose2, rp["point"], rp["pose"]),
-                                                    ("pprng0", 0, self.STREAM_PPRNG0, Pose2, Point2, rp["pose"], rp["point"])):
-                add(name, "rome_conv_pose2point2range_dev", vf, vt, d, stream, tg, mu, sigma, rows4=np.stack([fac, col(d, F), fx, tg], axis=1), nh=nh,
-                    partial=partial_coverage(Pose2Point2Range, 1 - d))   # (dir 1 solves the pose, variable 0 of the factor)
-            self.tab["pprng"] = dict(F=F)
-        # bearing-only factors (Bearing2D.jl): behind the range families; L = the [F][1] bearing sigmas
-        pb = getattr(pk, "pbear", None)
-        if pb is not None and pb["F"]:
-            F = pb["F"]
-            fac = np.arange(F, dtype=np.int32)
-            mu, sigma, nh = t(pb["mu"], f64), t(pb["sigma"], f64), dev(nh_or_none(pb["nh"]), f64)
-            for name, d, stream, vf, vt, fx, tg in (("pb1", 1, self.STREAM_PB1, Point2, Pose2, pb["point"], pb["pose"]),
-                                                    ("pb0", 0, self.STREAM_PB0, Pose2, Point2, pb["pose"], pb["point"])):
-                add(name, "rome_conv_pose2point2bearing_dev", vf, vt, d, stream, tg, mu, sigma, rows4=np.stack([fac, col(d, F), fx, tg], axis=1), nh=nh)
-            self.tab["pbear"] = dict(F=F)
+        # range-only factors (Range2D.jl): their own tables, launched after every other family; then the bearing-only factor (Bearing2D.jl)
+        two_way("p2rng", "rome_conv_point2point2range_dev", Point2, self.STREAM_P2RNG, pk.p2rng, Point2Point2Range)
+        pose_point("pprng1", "pprng0", "rome_conv_pose2point2range_dev", self.STREAM_PPRNG1, self.STREAM_PPRNG0, pk.pprng, "pprng", Pose2Point2Range)
+        pose_point("pb1", "pb0", "rome_conv_pose2point2bearing_dev", self.STREAM_PB1, self.STREAM_PB0, pk.pbear, "pbear", Pose2Point2Bearing)
         sampler("prior2", "rome_sample_priorpose2_dev", Pose2, None, pk.prior2)
         sampler("prior3", "rome_sample_priorpose3_dev", Pose3, None, pk.prior3)
-        # partial Pose3 factors (PartialPose3.jl): the last two families, their proposal rows behind every other Pose3 row.  p3xyy: both
-        # directions in one table (L = [F][6] packed Cholesky); zrp3: prior rows that READ the target belief (fixed = target,
-        # L = [F][4] = (σ_z, packed 2x2 Cholesky of the roll / pitch covariance))
-        xy = getattr(pk, "p3xyy", None)
-        if xy is not None and xy["F"]:
-            factor, dr, fixed, target = PackedGraph.conv_table(xy)
-            add("p3xyy", "rome_conv_pose3pose3xyyaw_dev", Pose3, Pose3, 0, self.STREAM_P3XYY, target, t(xy["mu"], f64), t(cholesky_lower(xy["cov"]), f64),
-                rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(xy["nh"], 2)),
-                partial=partial_coverage(Pose3Pose3XYYaw, 0))   # (the same coordinates towards either pose)
-            self.tab["p3xyy"] = dict(F=xy["F"], C=2 * xy["F"])
-        zr = getattr(pk, "zrp3", None)
-        if zr is not None and zr["F"]:
+        # partial Pose3 factors (PartialPose3.jl): the last families, their proposal rows behind every other Pose3 row.  zrp3: prior rows
+        # that READ the target belief (fixed = target, L = [F][4] = (σ_z, packed 2x2 Cholesky of the roll / pitch covariance))
+        two_way("p3xyy", "rome_conv_pose3pose3xyyaw_dev", Pose3, self.STREAM_P3XYY, pk.p3xyy, Pose3Pose3XYYaw)
+        zr = pk.zrp3
+        if zr["F"]:
             F = zr["F"]
             L = np.concatenate([zr["sigma_z"].reshape(F, 1), cholesky_lower(zr["cov_rp"]).reshape(F, 3)], axis=1)
             add("zrp3", "rome_conv_priorpose3zrp_dev", Pose3, Pose3, 0, self.STREAM_ZRP3, zr["var"], t(zr["mu"], f64), t(L, f64),
                 rows4=np.stack([np.arange(F, dtype=np.int32), col(0, F), zr["var"], zr["var"]], axis=1), nh=nh_or_none(zr["nh"]),
                 partial=partial_coverage(PriorPose3ZRP, 0))
             self.tab["zrp3"] = dict(F=F)
-        # p3rot: Pose3Pose3Rotation, the shape of p3xyy; the last record, so a graph without it keeps its launches, rows and streams
-        ro = getattr(pk, "p3rot", None)
-        if ro is not None and ro["F"]:
-            factor, dr, fixed, target = PackedGraph.conv_table(ro)
-            add("p3rot", "rome_conv_pose3pose3rotation_dev", Pose3, Pose3, 0, self.STREAM_P3ROT, target, t(ro["mu"], f64), t(cholesky_lower(ro["cov"]), f64),
-                rows4=np.stack([factor, dr, fixed, target], axis=1), nh=nh_or_none(np.repeat(ro["nh"], 2)),
-                partial=partial_coverage(Pose3Pose3Rotation, 0))   # (the same coordinates towards either pose)
-            self.tab["p3rot"] = dict(F=ro["F"], C=2 * ro["F"])
+        # p3rot: the last record, so a graph without it keeps its launches, rows and streams
+        two_way("p3rot", "rome_conv_pose3pose3rotation_dev", Pose3, self.STREAM_P3ROT, pk.p3rot, Pose3Pose3Rotation)
 
         # one conv_step: the fused Pose2 / Point2 call for its three records when all three have rows, then every other record that
         # owns proposal rows, in list order
@@ -614,7 +598,7 @@ class DeviceGraph:
             raise TypeError("%s: family %r holds prior rows; the deconvolution of a prior is the belief itself" % (who, kind))
         spec = self._DECONV[kind]
         tab = getattr(self.packed, spec[0])
-        if "alt" in tab and (np.asarray(tab["alt"]) >= 0).any():
+        if "alt" in tab and (tab["alt"] >= 0).any():   # (the scalar-belief tables p2rng / pprng / pbear have no hypothesis columns)
             raise ValueError("%s: family %r has multihypo rows; a deconvolution pairs one first with one second variable" % (who, kind))
         return spec, tab
 

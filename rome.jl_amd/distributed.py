@@ -15,13 +15,14 @@ import numpy as np
 
 
 def _refuse_range_tables(dg, where):
-    """the multi-rank drivers plan the DeviceGraph.families() tables only: a graph with range-only factors is refused"""
-    if getattr(dg, "has_range", None) is not None and dg.has_range():
+    """the multi-rank drivers plan the DeviceGraph.families() tables only: a graph with range-only factors is refused (asked of the
+    packed graph, which a stand-in for DeviceGraph holds too)"""
+    if dg.packed.has_range():
         names = [n for n, k in (("Point2Point2Range", "p2rng"), ("Pose2Point2Range", "pprng")) if k in dg.tab]
         raise TypeError("%s: %s factors are not supported by the multi-rank drivers" % (where, " / ".join(names)))
-    if getattr(dg, "has_bearing", None) is not None and dg.has_bearing():
+    if dg.packed.has_bearing():
         raise TypeError("%s: Pose2Point2Bearing factors are not supported by the multi-rank drivers" % where)
-    if getattr(dg, "has_partial3", None) is not None and dg.has_partial3():
+    if dg.packed.has_partial3():
         names = [n for n, k in (("Pose3Pose3XYYaw", "p3xyy"), ("PriorPose3ZRP", "zrp3"), ("Pose3Pose3Rotation", "p3rot")) if k in dg.tab]
         raise TypeError("%s: %s factors are not supported by the multi-rank drivers" % (where, " / ".join(names)))
 

@@ -295,6 +295,13 @@ def refuse_partial3(factors, where):
                             % (where, type(f).__name__))
 
 
+def refuse_unserved(factors, where):
+    """the three refusals of the paths that serve none of these families: range, bearing-only, partial Pose3, in that order"""
+    refuse_range(factors, where)
+    refuse_bearing(factors, where)
+    refuse_partial3(factors, where)
+
+
 def getMeasurementParametric(f):
     """(μ, iΣ) as IIF.getMeasurementParametric; BearingRange override at BearingRange2D.jl:30-37."""
     if isinstance(f, Pose2Point2Bearing):

@@ -451,6 +451,11 @@ def dead_reckon_init_pose3(fg, seed=1, sigma=(0.1, 0.1, 0.1, 0.01, 0.01, 0.01)):
 class PackedGraph:
     """Flat tables for the device sweep.  Variables are numbered per type in insertion order."""
 
+    # factor class -> its table, in the precedence of the isinstance checks (no class here derives from another)
+    FAMILIES = ((Pose2Pose2, "p2p2"), (Pose2Point2BearingRange, "br"), (Pose3Pose3, "p3p3"), (PriorPose2, "prior2"), (PriorPose3, "prior3"),
+                (PriorPoint2, "priorpt2"), (Point2Point2Range, "p2rng"), (Pose2Point2Range, "pprng"), (Pose2Point2Bearing, "pbear"),
+                (Pose3Pose3XYYaw, "p3xyy"), (PriorPose3ZRP, "zrp3"), (Pose3Pose3Rotation, "p3rot"))
+
     def __init__(self, fg):
         self.N = fg.N
         self.labels = {Pose2: [], Point2: [], Pose3: []}
@@ -458,99 +463,73 @@ class PackedGraph:
         for l, t in fg.variables.items():
             self.index[l] = len(self.labels[t])
             self.labels[t].append(l)
-        p2, br, p3, pr2, pr3, prpt, p2r, ppr, pb, xyy, zrp, rot = [], [], [], [], [], [], [], [], [], [], [], []
-        nullh = getattr(fg, "nullhypo", {})
+        items = {name: [] for _, name in self.FAMILIES}
         for flabel, labels, f in fg.factors:
-            ids = [self.index[l] for l in labels]
-            if isinstance(f, Pose2Pose2): p2.append((ids, f, flabel, fg.multihypo.get(flabel)))
-            elif isinstance(f, Pose2Point2BearingRange): br.append((ids, f, flabel, fg.multihypo.get(flabel)))
-            elif isinstance(f, Pose3Pose3): p3.append((ids, f, flabel, None))
-            elif isinstance(f, PriorPose2): pr2.append((ids, f, flabel))
-            elif isinstance(f, PriorPose3): pr3.append((ids, f, flabel))
-            elif isinstance(f, PriorPoint2): prpt.append((ids, f, flabel))
-            elif isinstance(f, Point2Point2Range): p2r.append((ids, f, flabel))
-            elif isinstance(f, Pose2Point2Range): ppr.append((ids, f, flabel))
-            elif isinstance(f, Pose2Point2Bearing): pb.append((ids, f, flabel))
-            elif isinstance(f, Pose3Pose3XYYaw): xyy.append((ids, f, flabel))
-            elif isinstance(f, PriorPose3ZRP): zrp.append((ids, f, flabel))
-            elif isinstance(f, Pose3Pose3Rotation): rot.append((ids, f, flabel))
-            else: raise TypeError("factor type %s is outside the hot path" % type(f).__name__)
+            for cls, name in self.FAMILIES:
+                if isinstance(f, cls):
+                    items[name].append(([self.index[l] for l in labels], f, flabel))
+                    break
+            else:
+                raise TypeError("factor type %s is outside the hot path" % type(f).__name__)
+        self._pack(items, getattr(fg, "nullhypo", {}), fg.multihypo)
 
-        def rel_tables(items, d):
-            F = len(items)
-            mu = np.zeros((F, d)); cov = np.zeros((F, d, d))
-            vfrom = np.zeros(F, dtype=np.int32); vto = np.zeros(F, dtype=np.int32)
-            alt = np.full(F, -1, dtype=np.int32); w = np.ones(F); w2 = np.zeros(F); nh = np.zeros(F)
-            for k, (ids, f, fl, mh) in enumerate(items):
-                mu[k] = f.Z.mu; cov[k] = f.Z.cov; vfrom[k], vto[k] = ids[:2]
-                nh[k] = nullh.get(fl, 0.0)      # IIF nullhypo= of the factor: every row of the factor carries it
-                if mh is not None:   # multihypo over the second pose: var_to with probability w, else alt
-                    alt[k] = ids[2]; w[k], w2[k] = mh
-            return dict(F=F, mu=mu, cov=cov, var_from=vfrom, var_to=vto, alt=alt, w=w, w2=w2, nh=nh, labels=[it[2] for it in items])
+    def _pack(self, items, nullh, multihypo):
+        """the twelve tables from the classified factors {table: [(variable ids, factor, label)]}.  One builder per row shape; every
+        builder returns every column, correctly shaped and typed, for no items too.  nh: IIF nullhypo= of the factor."""
+        arr = lambda vals, *shape: np.array(vals, dtype=np.float64).reshape((len(vals),) + shape)
+        var = lambda its, k: np.array([ids[k] for ids, _, _ in its], dtype=np.int32)
+        labels = lambda its: [fl for _, _, fl in its]
+        common = lambda its: dict(F=len(its), nh=arr([nullh.get(fl, 0.0) for fl in labels(its)]), labels=labels(its))
 
-        self.p2p2 = rel_tables(p2, 3)
-        self.p3p3 = rel_tables(p3, 6)
-        Fb = len(br)
-        # dir 1 (landmark -> pose): one row per factor, `point` = primary landmark, `alt` = other candidate (-1), `w` = P(primary)
-        # dir 0 (pose -> landmark): `rows0`, one row per (factor, candidate landmark)
-        r0 = dict(factor=[], pose=[], point=[], alt=[], w=[])
-        for k, (ids, f, _, mh) in enumerate(br):
-            cands = [(ids[1], -1, 1.0)] if mh is None else [(ids[1], ids[2], mh[0]), (ids[2], ids[1], mh[1])]
-            for pt, al, w in cands:
-                r0["factor"].append(k); r0["pose"].append(ids[0]); r0["point"].append(pt); r0["alt"].append(al); r0["w"].append(w)
-        self.br = dict(F=Fb, mu=np.array([[f.bearing.mu, f.range.mu] for _, f, _, _ in br]).reshape(Fb, 2),
-                       sigma=np.array([[f.bearing.sigma, f.range.sigma] for _, f, _, _ in br]).reshape(Fb, 2),
-                       pose=np.array([ids[0] for ids, _, _, _ in br], dtype=np.int32),
-                       point=np.array([ids[1] for ids, _, _, _ in br], dtype=np.int32),
-                       alt=np.array([(-1 if mh is None else ids[2]) for ids, _, _, mh in br], dtype=np.int32),
-                       w=np.array([(1.0 if mh is None else mh[0]) for _, _, _, mh in br], dtype=np.float64),
-                       nh=np.array([nullh.get(fl, 0.0) for _, _, fl, _ in br], dtype=np.float64),
-                       rows0={k: np.asarray(v, dtype=(np.float64 if k == "w" else np.int32)) for k, v in r0.items()},
-                       labels=[it[2] for it in br])
+        def relative(its, d, mh={}):
+            """an MvNormal of dimension d over [from, to]; multihypo over the second variable: var_to with probability w, else alt"""
+            F = len(its)
+            alt = np.full(F, -1, dtype=np.int32); w = np.ones(F); w2 = np.zeros(F)
+            for k, (ids, _, fl) in enumerate(its):
+                if fl in mh:
+                    alt[k] = ids[2]; w[k], w2[k] = mh[fl]
+            return dict(common(its), mu=arr([f.Z.mu for _, f, _ in its], d), cov=arr([f.Z.cov for _, f, _ in its], d, d),
+                        var_from=var(its, 0), var_to=var(its, 1), alt=alt, w=w, w2=w2)
 
-        def prior_tables(items, d):
-            F = len(items)
-            return dict(F=F, mu=np.array([f.Z.mu for _, f, _ in items]).reshape(F, d),
-                        cov=np.array([f.Z.cov for _, f, _ in items]).reshape(F, d, d),
-                        var=np.array([ids[0] for ids, _, _ in items], dtype=np.int32),
-                        labels=[it[2] for it in items])
+        def prior(its, d):
+            """an MvNormal of dimension d on one variable (a prior row carries no nullhypo)"""
+            return dict(F=len(its), mu=arr([f.Z.mu for _, f, _ in its], d), cov=arr([f.Z.cov for _, f, _ in its], d, d), var=var(its, 0), labels=labels(its))
 
-        self.prior2 = prior_tables(pr2, 3)
-        self.prior3 = prior_tables(pr3, 6)
-        self.priorpt2 = prior_tables(prpt, 2)   # landmark priors: parametric rows AND one proposal row each in the solve loop
+        def scalar(its, a, b):
+            """one scalar belief per factor over [a, b] (mu, sigma < 0: Uniform)"""
+            return dict(common(its), mu=arr([f.Z.mu for _, f, _ in its]), sigma=arr([f.Z.sigma for _, f, _ in its]), **{a: var(its, 0), b: var(its, 1)})
 
-        # range-only factors (Range2D.jl): one range belief per factor (mu, sigma < 0: Uniform), nullhypo per factor
-        def range_tables(items, a, b):
-            F = len(items)
-            return {"F": F, "mu": np.array([f.Z.mu for _, f, _ in items], dtype=np.float64).reshape(F),
-                    "sigma": np.array([f.Z.sigma for _, f, _ in items], dtype=np.float64).reshape(F),
-                    a: np.array([ids[0] for ids, _, _ in items], dtype=np.int32).reshape(F),
-                    b: np.array([ids[1] for ids, _, _ in items], dtype=np.int32).reshape(F),
-                    "nh": np.array([nullh.get(fl, 0.0) for _, _, fl in items], dtype=np.float64).reshape(F),
-                    "labels": [it[2] for it in items]}
+        def bearing_range(its, mh):
+            """dir 1 (landmark -> pose): one row per factor, `point` = primary landmark, `alt` = other candidate (-1), `w` = P(primary);
+            dir 0 (pose -> landmark): `rows0`, one row per (factor, candidate landmark)"""
+            r0 = dict(factor=[], pose=[], point=[], alt=[], w=[])
+            for k, (ids, f, fl) in enumerate(its):
+                cands = [(ids[1], ids[2], mh[fl][0]), (ids[2], ids[1], mh[fl][1])] if fl in mh else [(ids[1], -1, 1.0)]
+                for pt, al, w in cands:
+                    r0["factor"].append(k); r0["pose"].append(ids[0]); r0["point"].append(pt); r0["alt"].append(al); r0["w"].append(w)
+            return dict(common(its), mu=arr([(f.bearing.mu, f.range.mu) for _, f, _ in its], 2),
+                        sigma=arr([(f.bearing.sigma, f.range.sigma) for _, f, _ in its], 2), pose=var(its, 0), point=var(its, 1),
+                        alt=np.array([ids[2] if fl in mh else -1 for ids, _, fl in its], dtype=np.int32),
+                        w=arr([mh[fl][0] if fl in mh else 1.0 for fl in labels(its)]),
+                        rows0={k: np.asarray(v, dtype=(np.float64 if k == "w" else np.int32)) for k, v in r0.items()})
 
-        self.p2rng = range_tables(p2r, "from", "to")      # Point2Point2Range over [xi, lm]
-        self.pprng = range_tables(ppr, "pose", "point")   # Pose2Point2Range over [x, lm]
-        self.pbear = range_tables(pb, "pose", "point")    # Pose2Point2Bearing over [p, l] (Bearing2D.jl): one bearing belief per factor
-        # partial Pose3 factors (PartialPose3.jl), nullhypo per factor.  p3xyy: Pose3Pose3XYYaw over [p, q], one 3-dimensional normal belief
-        # per factor (p3rot: Pose3Pose3Rotation, the same shape); zrp3: PriorPose3ZRP, mu = (μ_z, μ_roll, μ_pitch), sigma_z, cov_rp the 2x2
-        # roll / pitch covariance
-        Fz = len(zrp)
-        nhs = lambda items: np.array([nullh.get(fl, 0.0) for _, _, fl in items], dtype=np.float64)
+        def zrp(its):
+            """PriorPose3ZRP: mu = (μ_z, μ_roll, μ_pitch), sigma_z, cov_rp the 2x2 roll / pitch covariance"""
+            return dict(common(its), mu=arr([(f.z.mu, f.rp.mu[0], f.rp.mu[1]) for _, f, _ in its], 3), sigma_z=arr([f.z.sigma for _, f, _ in its]),
+                        cov_rp=arr([f.rp.cov for _, f, _ in its], 2, 2), var=var(its, 0))
 
-        def rel3_tables(items):
-            F = len(items)
-            return dict(F=F, mu=np.array([f.Z.mu for _, f, _ in items], dtype=np.float64).reshape(F, 3),
-                        cov=np.array([f.Z.cov for _, f, _ in items], dtype=np.float64).reshape(F, 3, 3),
-                        var_from=np.array([ids[0] for ids, _, _ in items], dtype=np.int32), var_to=np.array([ids[1] for ids, _, _ in items], dtype=np.int32),
-                        nh=nhs(items), labels=[it[2] for it in items])
-
-        self.p3xyy = rel3_tables(xyy)
-        self.p3rot = rel3_tables(rot)
-        self.zrp3 = dict(F=Fz, mu=np.array([[f.z.mu, f.rp.mu[0], f.rp.mu[1]] for _, f, _ in zrp], dtype=np.float64).reshape(Fz, 3),
-                         sigma_z=np.array([f.z.sigma for _, f, _ in zrp], dtype=np.float64).reshape(Fz),
-                         cov_rp=np.array([f.rp.cov for _, f, _ in zrp], dtype=np.float64).reshape(Fz, 2, 2),
-                         var=np.array([ids[0] for ids, _, _ in zrp], dtype=np.int32), nh=nhs(zrp), labels=[it[2] for it in zrp])
+        self.p2p2 = relative(items["p2p2"], 3, multihypo)
+        self.p3p3 = relative(items["p3p3"], 6)
+        self.br = bearing_range(items["br"], multihypo)
+        self.prior2 = prior(items["prior2"], 3)
+        self.prior3 = prior(items["prior3"], 6)
+        self.priorpt2 = prior(items["priorpt2"], 2)   # landmark priors: parametric rows AND one proposal row each in the solve loop
+        self.p2rng = scalar(items["p2rng"], "from", "to")       # Point2Point2Range over [xi, lm] (Range2D.jl)
+        self.pprng = scalar(items["pprng"], "pose", "point")    # Pose2Point2Range over [x, lm]
+        self.pbear = scalar(items["pbear"], "pose", "point")    # Pose2Point2Bearing over [p, l] (Bearing2D.jl): one bearing belief per factor
+        self.p3xyy = relative(items["p3xyy"], 3)                # partial Pose3 factors (PartialPose3.jl): Pose3Pose3XYYaw over [p, q]
+        self.p3rot = relative(items["p3rot"], 3)                # Pose3Pose3Rotation, the same shape
+        self.zrp3 = zrp(items["zrp3"])
 
     @classmethod
     def from_pose2_tables(cls, N, n_poses, mu, cov, var_from, var_to, prior_mu=None, prior_cov=None, prior_var=None):
@@ -560,26 +539,15 @@ class PackedGraph:
         self.N = int(N)
         self.labels = {Pose2: ["x%d" % k for k in range(n_poses)], Point2: [], Pose3: []}
         self.index = {}   # labels -> index is the identity here; not materialised for large graphs
+        self._pack({name: [] for _, name in cls.FAMILIES}, {}, {})   # every table but the two below: its builder's empty one
         F = len(var_from)
         self.p2p2 = dict(F=F, mu=np.asarray(mu, dtype=np.float64).reshape(F, 3), cov=np.asarray(cov, dtype=np.float64).reshape(F, 3, 3),
-                         var_from=np.asarray(var_from, dtype=np.int32), var_to=np.asarray(var_to, dtype=np.int32), labels=[])
-        e3 = dict(F=0, mu=np.zeros((0, 6)), cov=np.zeros((0, 6, 6)), var_from=np.zeros(0, np.int32), var_to=np.zeros(0, np.int32), labels=[])
-        self.p3p3 = e3
-        z32 = np.zeros(0, np.int32)
-        self.br = dict(F=0, mu=np.zeros((0, 2)), sigma=np.zeros((0, 2)), pose=z32, point=z32, alt=z32, w=np.zeros(0),
-                       rows0=dict(factor=z32, pose=z32, point=z32, alt=z32, w=np.zeros(0)), labels=[])
+                         var_from=np.asarray(var_from, dtype=np.int32), var_to=np.asarray(var_to, dtype=np.int32),
+                         alt=np.full(F, -1, dtype=np.int32), w=np.ones(F), w2=np.zeros(F), nh=np.zeros(F), labels=[])
         P = 0 if prior_var is None else len(prior_var)
-        self.prior2 = dict(F=P, mu=np.asarray(prior_mu if P else np.zeros((0, 3)), dtype=np.float64).reshape(P, 3),
-                           cov=np.asarray(prior_cov if P else np.zeros((0, 3, 3)), dtype=np.float64).reshape(P, 3, 3),
-                           var=np.asarray(prior_var if P else np.zeros(0), dtype=np.int32), labels=[])
-        self.prior3 = dict(F=0, mu=np.zeros((0, 6)), cov=np.zeros((0, 6, 6)), var=np.zeros(0, np.int32), labels=[])
-        self.priorpt2 = dict(F=0, mu=np.zeros((0, 2)), cov=np.zeros((0, 2, 2)), var=np.zeros(0, np.int32), labels=[])
-        self.p2rng = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "from": z32, "to": z32, "nh": np.zeros(0), "labels": []}
-        self.pprng = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "pose": z32, "point": z32, "nh": np.zeros(0), "labels": []}
-        self.pbear = {"F": 0, "mu": np.zeros(0), "sigma": np.zeros(0), "pose": z32, "point": z32, "nh": np.zeros(0), "labels": []}
-        self.p3xyy = dict(F=0, mu=np.zeros((0, 3)), cov=np.zeros((0, 3, 3)), var_from=z32, var_to=z32, nh=np.zeros(0), labels=[])
-        self.p3rot = dict(F=0, mu=np.zeros((0, 3)), cov=np.zeros((0, 3, 3)), var_from=z32, var_to=z32, nh=np.zeros(0), labels=[])
-        self.zrp3 = dict(F=0, mu=np.zeros((0, 3)), sigma_z=np.zeros(0), cov_rp=np.zeros((0, 2, 2)), var=z32, nh=np.zeros(0), labels=[])
+        if P:
+            self.prior2 = dict(F=P, mu=np.asarray(prior_mu, dtype=np.float64).reshape(P, 3), cov=np.asarray(prior_cov, dtype=np.float64).reshape(P, 3, 3),
+                               var=np.asarray(prior_var, dtype=np.int32), labels=[])
         return self
 
     @staticmethod
@@ -615,13 +583,13 @@ class PackedGraph:
         return PackedGraph.conv_table({"F": tab["F"], "var_from": tab["from"], "var_to": tab["to"]})
 
     def has_range(self):
-        return bool(getattr(self, "p2rng", {"F": 0})["F"] or getattr(self, "pprng", {"F": 0})["F"])
+        return bool(self.p2rng["F"] or self.pprng["F"])
 
     def has_bearing(self):
-        return bool(getattr(self, "pbear", {"F": 0})["F"])
+        return bool(self.pbear["F"])
 
     def has_partial3(self):
-        return bool(getattr(self, "p3xyy", {"F": 0})["F"] or getattr(self, "zrp3", {"F": 0})["F"] or getattr(self, "p3rot", {"F": 0})["F"])
+        return bool(self.p3xyy["F"] or self.zrp3["F"] or self.p3rot["F"])
 
     def beliefs(self, fg, vartype):
         """(V, dim, N) SoA blocks from fg.vals (all variables of the type must be initialised)."""

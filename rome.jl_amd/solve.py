@@ -8,7 +8,7 @@ on a whole-graph Jacobi schedule instead of the Bayes tree --, 
 import numpy as np
 
 from .convolution import approxConv
-from .factors import _PriorFactor, refuse_range, refuse_bearing, refuse_partial3
+from .factors import _PriorFactor, refuse_unserved
 
 
 def initAll(fg, seed=1, solver=None):
@@ -45,9 +45,7 @@ def initAllOrdered(fg, seed=1, ctx=None, sweeps=0, kind="colour", solver=None):
     the variables that are initialised already (`schedule.OrderedSolve`: beliefs resident in a `DeviceStore`, one up-solve plan per
     independent group); then `sweeps` ordered Gauss-Seidel sweeps over the whole graph.  Beliefs are written back to `fg`.
     -> the OrderedSolve (its store keeps the beliefs on the device for further sweeps)."""
-    refuse_range([f for _, _, f in fg.factors], "initAllOrdered")
-    refuse_bearing([f for _, _, f in fg.factors], "initAllOrdered")
-    refuse_partial3([f for _, _, f in fg.factors], "initAllOrdered")
+    refuse_unserved([f for _, _, f in fg.factors], "initAllOrdered")
     from .api import make_opts
     from .clique import DeviceStore
     from .schedule import OrderedSolve
@@ -111,9 +109,7 @@ def solveTree(fg, tree=None, messages="auto", passes=1, seed=0x524F4D45, ctx=Non
     of the MAP in one pass from the factors alone, no init pass).  "auto" chooses "elimination" for the Pose2 scope only; a Pose3 graph
     gets "marginal" unless messages="elimination" is asked for.
     -> the TreeSolver (its store keeps the beliefs on the device; pass it back as `tree=` after adding nothing to the graph)."""
-    refuse_range([f for _, _, f in fg.factors], "solveTree")
-    refuse_bearing([f for _, _, f in fg.factors], "solveTree")
-    refuse_partial3([f for _, _, f in fg.factors], "solveTree")
+    refuse_unserved([f for _, _, f in fg.factors], "solveTree")
     from .api import make_opts
     from .canonical import setPPE
     from .tree import TreeSolver

@@ -33,7 +33,7 @@ import numpy as np
 
 from . import _lib
 from .clique import DeviceStore, LibHandle, UpsolvePlan, plan_level
-from .factors import refuse_range, refuse_bearing, refuse_partial3
+from .factors import refuse_unserved
 from .levels import ZERO, LevelSpec, LevelGraph, LevelSolver, split_products   # noqa: F401  (ZERO, LevelSpec: importable from here as before)
 
 
@@ -242,9 +242,7 @@ class TreeSolver(LevelSolver):
                 shard: a factory `store -> distributed.FrontierShard` (the store exists only once the lifted universe is known): every level is
         then dealt to the ranks by clique -- share up-solve, ONE all-gather of the level's written blocks, one scatter; the block
         operations between levels run on every rank (each holds the whole store)."""
-        refuse_range([f for _, _, f in fg.factors], "TreeSolver")
-        refuse_bearing([f for _, _, f in fg.factors], "TreeSolver")
-        refuse_partial3([f for _, _, f in fg.factors], "TreeSolver")
+        refuse_unserved([f for _, _, f in fg.factors], "TreeSolver")
         if messages not in ("relative", "marginal"):
             raise ValueError("messages must be 'relative' or 'marginal'")
         if message_tree not in ("hop", "star"):
