@@ -352,7 +352,7 @@ __device__ __forceinline__ void conv_wave_body(const ConvArgs& a, int blk) {
                                        (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
         t[k][0] += nh_spread * (((double)hw.y + 0.5) * (1.0 / 4294967296.0) - 0.5);
         t[k][1] += nh_spread * (((double)hw.z + 0.5) * (1.0 / 4294967296.0) - 0.5);
-        if constexpr (FP::DT == 3) t[k][2] += nh_spread * (((double)hw.w + 0.5) * (1.0 / 4294967296.0) - 0.5);   // a pose: the heading too
+        if constexpr (FP::DT == 3) t[k][2] = wrap_pi(t[k][2] + nh_spread * (((double)hw.w + 0.5) * (1.0 / 4294967296.0) - 0.5));   // a pose: the heading too, stored in (-π, π]
       }
     }
   }

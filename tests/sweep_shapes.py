@@ -8,7 +8,10 @@ Two ways into the library for the same rows, same streams (stream_offset + row),
   packed  -- `rows4` table, in-kernel noise: launch_ppl's plain sweep, the packed kernel k_conv_flat for 16 <= N <= 512
   wave    -- the four table columns as separate arrays and no `rows4`: not a plain sweep, so one wavefront per row (k_conv), the
              feature-complete instantiation
-Every output buffer has a guard block before and after the table, pre-filled with NaN (status: -7), checked after the launch."""
+Every output buffer has a guard block before and after the table, pre-filled with NaN (status: -7), checked after the launch.
+
+Hypothesis tables (tests/hypo_ref.py) carry `alt_var`, `hypo_w` and `nullhypo` columns: Dev uploads them where the table has them and
+launch(hypo=...) attaches the named ones; noise=... hands the launch its normals (or, with presampled=1, its measurement samples)."""
 import ctypes as C
 import functools
 import hashlib
@@ -19,6 +22,7 @@ import conv_ref as CR
 
 ENTRY = {CR.P2P2: "rome_conv_pose2pose2_dev", CR.BR0: "rome_conv_pose2point2br_dev", CR.P3P3: "rome_conv_pose3pose3_dev"}
 ST_GUARD = -7
+HYPO_COLUMNS = {"alt_var": 4, "hypo_w": 8, "nullhypo": 8}                                # column -> bytes per row
 CF, NEWTON, GN = 0, 1, 3
 SHAPE_N = (16, 18, 100, 101, 512)            # H = 8 (< NK: two staging passes), H = 9 (= NK of Pose2: one), CPB = 5, the odd N, one row per block
 
@@ -51,6 +55,7 @@ class Dev:
         rows = np.ascontiguousarray(t["rows4"], dtype=np.int32)
         self.rows4 = self._up(rows)
         self.cols = [self._up(np.ascontiguousarray(rows[:, k])) for k in range(4)]       # factor, dir, fixed_var, target_var
+        self.hypo = {k: self._up(t[k]) for k in HYPO_COLUMNS if k in t}                  # per-row hypothesis columns of a hypo_ref table
 
     def _up(self, a, off=0):
         torch = self.torch
@@ -61,12 +66,15 @@ class Dev:
         return buf[off:]
 
 
-def launch(env, d, n_conv, solver, how="packed", status=False, row0=0, shift=False, mirror=None, **opts):
+def launch(env, d, n_conv, solver, how="packed", status=False, row0=0, shift=False, mirror=None, hypo=(), noise=None, dir_all=0,
+           refused=False, **opts):
     """rows [row0, row0 + n_conv) of the device table -> (out (n_conv, dt, N), status (n_conv, N) or None, mirror blocks or None).
     how: "packed" (rows4) or "wave" (column arrays).  shift: `out` and the mirror buffer one double off their 16-byte alignment.
-    mirror: ("map", slots per row) or ("rows", up to four row indices)."""
+    mirror: ("map", slots per row) or ("rows", up to four row indices).  hypo: names of the hypothesis columns of d to attach.
+    noise: (n_conv, dz, N) host array for the `noise` field.  dir_all: the direction of a bearing-range table.
+    refused=True: the entry point must return an error and store nothing -> its error code."""
     torch, _lib, lib, ctx = env
-    dt, N = CR.DIMS[d.kind][2], d.N
+    dt, N = (3 if d.kind == CR.BR0 and dir_all == 1 else CR.DIMS[d.kind][2]), d.N     # bearing-range towards the pose: the target is a Pose2
     blk = dt * N
     assert 0 <= row0 and row0 + n_conv <= len(d.t["rows4"]), "rows beyond the table"
     o = _lib.default_opts(solver, n_particles=N, seed=d.t["seed"], stream_offset=d.t["stream_offset"] + row0, **opts)
@@ -74,7 +82,7 @@ def launch(env, d, n_conv, solver, how="packed", status=False, row0=0, shift=Fal
     out = torch.full(((n_conv + 2) * blk + 2,), float("nan"), dtype=torch.float64, device="cuda")
     st = torch.full(((n_conv + 2) * N,), ST_GUARD, dtype=torch.int32, device="cuda") if status else None
     T = _lib.ConvDev()
-    T.n_conv, T.dir_all = n_conv, 0
+    T.n_conv, T.dir_all = n_conv, dir_all
     T.mu, T.L, T.bel_fixed, T.bel_target = d.mu.data_ptr(), d.L.data_ptr(), d.bel_fixed.data_ptr(), d.bel_target.data_ptr()
     if how == "packed":
         T.rows4 = d.rows4.data_ptr() + 16 * row0
@@ -83,6 +91,12 @@ def launch(env, d, n_conv, solver, how="packed", status=False, row0=0, shift=Fal
         if d.kind == CR.BR0:
             T.dir = None                                                              # the direction of a bearing-range table is dir_all
     T.out = out.data_ptr() + 8 * (blk + off)
+    for name in hypo:
+        setattr(T, name, d.hypo[name].data_ptr() + HYPO_COLUMNS[name] * row0)
+    if noise is not None:
+        assert noise.shape == (n_conv, CR.DIMS[d.kind][0], N)
+        hold = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float64)).cuda()
+        T.noise = hold.data_ptr()
     if status:
         T.status = st.data_ptr() + 4 * N
     keep, mout, nslot = None, None, 0
@@ -100,7 +114,13 @@ def launch(env, d, n_conv, solver, how="packed", status=False, row0=0, shift=Fal
         mout = torch.full(((nslot + 2) * blk + 2,), float("nan"), dtype=torch.float64, device="cuda")
         T.mirror_out = mout.data_ptr() + 8 * (blk + off)
     torch.cuda.synchronize()
-    _lib.check(getattr(lib, ENTRY[d.kind])(ctx.handle, C.byref(o), C.byref(T)), ctx.handle)
+    rc = getattr(lib, ENTRY[d.kind])(ctx.handle, C.byref(o), C.byref(T))
+    if refused:
+        ctx.synchronize()
+        assert rc != 0, "the entry point accepted the table"
+        assert np.isnan(out.cpu().numpy()).all() and (st is None or (st.cpu().numpy() == ST_GUARD).all()), "a refused launch stored something"
+        return rc
+    _lib.check(rc, ctx.handle)
     ctx.synchronize()
     h = out.cpu().numpy()
     lo, hi = blk + off, blk + off + n_conv * blk

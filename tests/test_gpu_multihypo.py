@@ -41,6 +41,7 @@ def test_multihypo_vs_oracle(direction, solver):
         ref, rst = ro.conv_pose2point2br(oo, 1, mu, sigma, np.concatenate([l1, l2]), pose, np.arange(C_), np.arange(C_),
                                          alt_var=C_ + np.arange(C_), hypo_w=w, want_status=True)
         assert np.abs(_wd(out, ref)).max() < 1e-8 and (st == rst).all()
+        assert ((out[:, 2] > -np.pi) & (out[:, 2] <= np.pi)).all() and ((ref[:, 2] > -np.pi) & (ref[:, 2] <= np.pi)).all()   # stored headings are canonical
         # each pose proposal satisfies the sighting against ONE of the two landmarks, in proportion ~w
         d1 = np.hypot(out[:, 0] - l1[:, 0], out[:, 1] - l1[:, 1]); d2 = np.hypot(out[:, 0] - l2[:, 0], out[:, 1] - l2[:, 1])
         near1 = np.abs(d1 - mu[:, 1:2]) < 6 * sigma[:, 1:2]; near2 = np.abs(d2 - mu[:, 1:2]) < 6 * sigma[:, 1:2]
@@ -122,6 +123,7 @@ def test_nullhypo_vs_oracle_and_fraction(kind):
                                  np.arange(C_), C_ + np.arange(C_), dirs)
         d = out - ref; d[:, 2] = np.arctan2(np.sin(d[:, 2]), np.cos(d[:, 2]))
         assert np.abs(d).max() < 1e-9
+        assert ((out[:, 2] > -np.pi) & (out[:, 2] <= np.pi)).all() and ((ref[:, 2] > -np.pi) & (ref[:, 2] <= np.pi)).all()   # direction 0: null particles too
         follows = np.abs(out[:, 0] - 15.0) < 6.0           # 50 - 35 = 15 along x
     else:
         mu = np.tile([-35.0, 0, 0, 0, 0, 0], (C_, 1)); cov = np.tile(np.diag([0.5] * 3 + [0.01] * 3), (C_, 1, 1))

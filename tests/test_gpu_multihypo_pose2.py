@@ -54,6 +54,9 @@ def test_device_equals_oracle_both_directions(solver, N):
     solved = moved < 1.0                                                           # (the entropy box is ±nh/2 ≈ ±9.6 wide)
     assert abs(solved.mean() - 0.7) < 4 * np.sqrt(0.21 / N) + 0.05
     assert np.abs(got0[:2] - b1[:2]).max() <= nh / 2 + 1e-9
+    # the heading of every stored particle is canonical, the entropy-only ones included (±nh/2 ≈ ±9.6 rad before the wrap), on both sides
+    for th in (got0[2], ref0[2], got[2], ref[2]):
+        assert ((th > -np.pi) & (th <= np.pi)).all(), float(np.abs(th).max())
 
 
 def test_approxconv_on_a_graph():
