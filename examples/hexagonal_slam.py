@@ -26,3 +26,11 @@ for label, m, s in zip(dg.packed.labels[R.Point2], meanl.cpu().numpy(), stdl.cpu
 dg.download_beliefs(fg)
 pts = R.approxConv(fg, "x0x1f1", "x1", seed=3)
 print("approxConv(x0x1f1 -> x1): mean", np.round(pts.mean(axis=1), 2))
+# the log-likelihood of the generator's true poses and landmark under the solved beliefs (examples/RangesExampleTwo.jl:388-400 prints
+# the posterior likelihood of the true position after every solve): the belief called as a function, one call per variable type
+truth, pose = {"l1": [20.0, 0.0]}, np.zeros(3)
+for k in range(7):
+    truth["x%d" % k] = [pose[0], pose[1], np.arctan2(np.sin(pose[2]), np.cos(pose[2]))]
+    pose = pose + [10.0 * np.cos(pose[2]), 10.0 * np.sin(pose[2]), np.pi / 3]
+for label, lp in R.beliefLogLikelihood(fg, truth).items():
+    print("%-3s  log p(truth) = %8.3f   at the joint mode %8.3f" % (label, lp, R.kde_mode(fg.getVal(label))[1]))

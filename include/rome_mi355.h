@@ -753,6 +753,33 @@ int rome_mmd_dev(rome_ctx*, int32_t dim, int32_t P, int32_t Na, const double* a,
 int rome_mmd(rome_ctx*, int32_t layout, int32_t dim, int32_t P, int32_t Na, int32_t n_a_blocks, const double* a, const int32_t* a_rows,
              int32_t Nb, int32_t n_b_blocks, const double* b, const int32_t* b_rows, const double* scale, double sigma, double* out,
              double* sums);                                                                                       /* host pointers */
+/* rome_kde_eval*: the log-density of a belief's kernel density estimate at query points -- ⚠the belief called as a function
+ *   (`getBelief(fg, :x)(pts)`, AMP `evaluateDualTree`; examples/RangesExampleTwo.jl:388-400, KDE.jl `kld`).  For belief block B
+ *   (N particles y_j), bandwidths h[dim] and query x:
+ *       q_j     = sum_k (diff_k(x, y_j) / h_k)^2
+ *       logp(x) = -q_min/2 + log sum_j exp(-(q_j - q_min)/2) - log N' - sum_k log h_k - (dim/2) log 2 pi
+ *   diff is the tangent difference of the variable type, as in rome_mmd and the products: dim 2 Point2, dim 3 Pose2 (heading difference
+ *   wrapped), dim 6 Pose3 (t_x - t_y, Log(R_y^T R_x)), coordinates [t; rotation vector].  j runs in particle order; q_j is saturated at
+ *   1e300, so the result is finite for every finite input however far the query lies.  N' = N; with leave_one_out, which is valid only
+ *   for self-evaluation, j = i is skipped and N' = N - 1.  This is the density in TANGENT coordinates: exactly normalised on Euclidean
+ *   coordinates; on a heading or a rotation it is the truncated Gaussian kernel the products weigh by (one term per particle, no sum
+ *   over the 2 pi images, no volume factor of the exponential map).  NOT CHECKED against AMP (not vendored): its normalisation of a
+ *   circular or rotation coordinate, and whether it evaluates in these coordinates.
+ *   Pair p of P evaluates block bel_rows[p] of bel ([.][dim][N] SoA) with bandwidth row bw[bel_rows[p]][dim] at the Q points of block
+ *   query_rows[p] of queries ([.][dim][Q] SoA); a NULL row table means block p; rows may repeat.  queries == NULL is self-evaluation:
+ *   Q must equal N and the queries are the pair's own belief block.  out [P][Q].  The bits of out[p][q] depend on the belief block, its
+ *   bandwidth row and the query point alone, not on Q, P or the query's place.  1 <= N <= ROME_MAX_PARTICLES_KDE_EVAL (beyond:
+ *   ROME_ERR_UNSUPPORTED_N, nothing launched); Q is unbounded; dim other than 2, 3, 6, or leave_one_out != 0 with queries or with
+ *   N < 2, is ROME_ERR_INVALID_ARG; P = 0 or Q = 0 is a no-op.  rome_kde_eval_dev neither synchronises nor allocates (it can be captured
+ *   into a graph) and trusts its device arrays (bandwidths must be finite and > 0).  rome_kde_eval: host pointers, blocks in `layout`
+ *   (ROME_LAYOUT_*), bw [n_bel_blocks][dim]; n_bel_blocks / n_query_blocks = blocks in bel / queries, which the row tables (or P,
+ *   without them) must stay inside; a bandwidth that is not finite and > 0 is ROME_ERR_INVALID_ARG.  It converts and uploads ALL blocks. */
+#define ROME_MAX_PARTICLES_KDE_EVAL 512
+int rome_kde_eval_dev(rome_ctx*, int32_t dim, int32_t P, int32_t N, const double* bel, const int32_t* bel_rows, const double* bw, int32_t Q,
+                      const double* queries, const int32_t* query_rows, int32_t leave_one_out, double* out);
+int rome_kde_eval(rome_ctx*, int32_t layout, int32_t dim, int32_t P, int32_t N, int32_t n_bel_blocks, const double* bel,
+                  const int32_t* bel_rows, const double* bw, int32_t Q, int32_t n_query_blocks, const double* queries,
+                  const int32_t* query_rows, int32_t leave_one_out, double* out);                                  /* host pointers */
 /* rome_kde_bandwidth*: the bandwidth `manikde!` selects for a belief, one per coordinate, by leave-one-out likelihood
  *   cross-validation of a 1-D Gaussian KDE (golden section on the bracket of KDE.jl's ksize "lcv"; coordinate k is circular
  *   -- differences wrapped -- when bit k of circular_mask is set: Pose2 = 0b100).  bel [V][dim][N] -> bw [V][dim], dim 1..6,

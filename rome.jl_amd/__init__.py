@@ -8,11 +8,11 @@ host-side mirror of the reference interface; it contains no compute and no CPU f
 """
 from . import _lib
 from ._lib import (Context, Opts, RomeError, SOLVER_CLOSED_FORM, SOLVER_NEWTON, SOLVER_NELDER_MEAD, SOLVER_GAUSS_NEWTON,
-                   LAYOUT_SOA, LAYOUT_AOS, LAYOUT_AOS_POINTS, MAX_PARTICLES, MAX_PARTICLES_REGISTER, MAX_PARTICLES_MMD)
+                   LAYOUT_SOA, LAYOUT_AOS, LAYOUT_AOS_POINTS, MAX_PARTICLES, MAX_PARTICLES_REGISTER, MAX_PARTICLES_MMD, MAX_PARTICLES_KDE_EVAL)
 from .factors import (MvNormal, Normal, Uniform, Pose2, Point2, Pose3, Pose2Pose2, PriorPose2, Pose2Point2BearingRange,
                       Pose3Pose3, PriorPose3, PriorPoint2, Point2Point2, Point2Point2Range, Pose2Point2Range, Pose2Point2Bearing, Pose3Pose3XYYaw, PriorPose3ZRP, Pose3Pose3Rotation, getMeasurementParametric, getPoint, getCoordinates, pack_factor,
                       unpack_factor)
-from .api import (linearize, belief_stats, mmd, mmdBeliefs, kde_bandwidth, kde_max, manifoldProduct, product_partial, calcPPE, points_to_coords, coords_to_points, calcFactorResidualTemporary, make_opts, cholesky_lower, default_context,
+from .api import (linearize, belief_stats, mmd, mmdBeliefs, kde_logpdf, kde_mode, kld, evalBelief, beliefLogLikelihood, kldBeliefs, kde_bandwidth, kde_max, manifoldProduct, product_partial, calcPPE, points_to_coords, coords_to_points, calcFactorResidualTemporary, make_opts, cholesky_lower, default_context,
                   residual_pose2pose2, residual_priorpose2, residual_pose2point2br, residual_pose2point2br_pt,
                   residual_pose3pose3, residual_pose3pose3_pt, residual_priorpose3,
                   conv_pose2pose2, conv_pose2point2br, conv_pose3pose3, sample_priorpose2, sample_priorpose3, sample_priorpoint2,

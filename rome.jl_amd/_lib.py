@@ -18,6 +18,7 @@ MAX_PARTICLES = 4096            # ROME_MAX_PARTICLES (the register-resident kern
 MAX_PARTICLES_REGISTER = 512
 MAX_PARTICLES_KDE, MAX_PARTICLES_PRODUCT, MAX_PARTICLES_PRODUCT_POSE3, MAX_PARTICLES_GIBBS = 512, 512, 256, 256   # per-stage limits (header)
 MAX_PARTICLES_MMD = 512         # ROME_MAX_PARTICLES_MMD: both sets of a pair live in LDS
+MAX_PARTICLES_KDE_EVAL = 512    # ROME_MAX_PARTICLES_KDE_EVAL: the belief lives in LDS
 FACTOR_PRIORPOSE2, FACTOR_POSE2POSE2, FACTOR_POSE2POINT2BR, FACTOR_PRIORPOINT2, FACTOR_POSE3POSE3, FACTOR_PRIORPOSE3 = range(6)
 FACTOR_POSE2POINT2BEARING = 6
 (DECONV_POSE2POSE2, DECONV_POSE2POINT2BR, DECONV_POSE2POINT2BEARING, DECONV_POINT2POINT2RANGE, DECONV_POSE2POINT2RANGE, DECONV_POSE3POSE3,
@@ -128,6 +129,10 @@ SIGNATURES = {
                                C.c_void_p, C.c_void_p]),
     "rome_mmd": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _PD, _PI, C.c_int32, C.c_int32, _PD, _PI, _PD, C.c_double,
                            _PD, _PD]),
+    "rome_kde_eval_dev": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                    C.c_int32, C.c_void_p]),
+    "rome_kde_eval": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _PD, _PI, _PD, C.c_int32, C.c_int32, _PD, _PI,
+                                C.c_int32, _PD]),
     "rome_kde_bandwidth_dev": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_void_p]),
     "rome_kde_bandwidth": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, _PD, C.c_uint32, C.c_double, C.c_double, _PD]),
     "rome_kde_max_dev": (C.c_int, [_CTX, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),

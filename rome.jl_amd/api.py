@@ -274,6 +274,136 @@ def mmdBeliefs(fg_a, fg_b, labels=None, bw=0.001, scale=None, ctx=None):
     return {l: res[l] for l in labels}
 
 
+def _kde_eval_call(name, bel, pts, bw, leave_one_out, ctx):
+    """bel (V, dim, N), pts (V, dim, Q) or None (self-evaluation), bw (V, dim), (dim,) or None (kde_bandwidth) -> (V, Q) log-densities:
+    one rome_kde_eval call.  Everything the library would refuse is refused here first, by name and without a device."""
+    V, d, N = bel.shape
+    if d not in (2, 3, 6):
+        raise ValueError("%s: beliefs must have 2 (Point2), 3 (Pose2) or 6 (Pose3) coordinates, got %d" % (name, d))
+    if N < 1 or N > _lib.MAX_PARTICLES_KDE_EVAL:
+        raise ValueError("%s: 1 <= N <= %d particles, got %d" % (name, _lib.MAX_PARTICLES_KDE_EVAL, N))
+    if pts is not None and (pts.shape[0] != V or pts.shape[1] != d):
+        raise ValueError("%s: the query points must be (%d, %d, Q) like the beliefs %s, got %s" % (name, V, d, bel.shape, pts.shape))
+    if leave_one_out and (pts is not None or N < 2):
+        raise ValueError("%s: leave_one_out applies to self-evaluation (pts=None) of at least 2 particles" % name)
+    if bw is not None:
+        bw = _d(bw)
+        if bw.shape not in ((d,), (V, d)):
+            raise ValueError("%s: bandwidths must be (%d,) or (%d, %d), got %s" % (name, d, V, d, bw.shape))
+        bw = np.ascontiguousarray(np.broadcast_to(bw, (V, d)))
+        if not (np.isfinite(bw) & (bw > 0.0)).all():
+            raise ValueError("%s: bandwidths must be finite and positive" % name)
+    ctx = ctx or default_context()
+    if bw is None:
+        bw = kde_bandwidth(bel, ctx=ctx)
+    Q = N if pts is None else pts.shape[2]
+    out = np.empty((V, Q))
+    _lib.check(_lib.load().rome_kde_eval(ctx.handle, _lib.LAYOUT_SOA, d, V, N, V, _p(bel), None, _p(bw), Q, 0 if pts is None else V, _p(pts), None,
+                                         1 if leave_one_out else 0, _p(out)), ctx.handle)
+    return out
+
+
+def _eval_blocks(name, a, what):
+    a = _d(a)
+    if a.ndim not in (2, 3):
+        raise ValueError("%s: %s must be (dim, N) or (V, dim, N), got %s" % (name, what, a.shape))
+    return (a[None], True) if a.ndim == 2 else (a, False)
+
+
+def kde_logpdf(bel, pts=None, bw=None, leave_one_out=False, ctx=None):
+    """⚠the belief called as a function (`getBelief(fg, :x)(pts)`, AMP `evaluateDualTree`): log-density of the kernel density estimate
+    of bel at pts (include/rome_mi355.h rome_kde_eval: tangent coordinates, normalisation not checked against AMP).  bel (dim, N) and pts
+    (dim, Q) -> (Q,); bel (V, dim, N) and pts (V, dim, Q) -> (V, Q), block v at block v.  pts=None: at the belief's own particles;
+    leave_one_out then leaves each particle out of its own density.  bw (dim,) or (V, dim) kernel bandwidths; None selects them with
+    kde_bandwidth, as kde_max does."""
+    bel, single = _eval_blocks("kde_logpdf", bel, "bel")
+    if pts is not None:
+        pts, psingle = _eval_blocks("kde_logpdf", pts, "pts")
+        if psingle != single:
+            raise ValueError("kde_logpdf: bel and pts must both be one block or both be stacks of blocks")
+    out = _kde_eval_call("kde_logpdf", bel, pts, bw, leave_one_out, ctx)
+    return out[0] if single else out
+
+
+def kde_mode(bel, bw=None, ctx=None):
+    """Joint mode estimate of V beliefs: each belief's own particle of highest joint density (first on ties), the argmax of the
+    self-evaluation without leave-one-out -- unlike kde_max (getKDEMax), which works coordinate by coordinate and can return a point
+    that belongs to no mode.  bel (V, dim, N) -> (V, dim) points, (V,) log-densities; bel (dim, N) -> (dim,), float."""
+    bel, single = _eval_blocks("kde_mode", bel, "bel")
+    lp = _kde_eval_call("kde_mode", bel, None, bw, False, ctx)
+    k = np.argmax(lp, axis=1)
+    v = np.arange(bel.shape[0])
+    pts, best = bel[v, :, k], lp[v, k]
+    return (pts[0], float(best[0])) if single else (pts, best)
+
+
+def kld(a, b, bw_a=None, bw_b=None, leave_one_out=False, ctx=None):
+    """⚠unvendored: KDE.jl's direct estimate of the Kullback-Leibler divergence, written from recollection and NOT CHECKED against
+    KDE.jl: kld(a, b) = mean_i [log p_a(a_i) − log p_b(a_i)] with both densities evaluated by kde_logpdf, each with its own
+    bandwidths (bw_a, bw_b; None = kde_bandwidth).  leave_one_out leaves a_i out of p_a.  a (dim, Na), b (dim, Nb) -> float;
+    (V, dim, Na), (V, dim, Nb) -> (V,).  Not symmetric; an estimate, so it can be slightly negative."""
+    a, single = _eval_blocks("kld", a, "a")
+    b, bsingle = _eval_blocks("kld", b, "b")
+    if bsingle != single or b.shape[:2] != a.shape[:2]:
+        raise ValueError("kld: the two sets must have the same number of blocks and coordinates, got %s and %s" % (a.shape, b.shape))
+    la = _kde_eval_call("kld", a, None, bw_a, leave_one_out, ctx)
+    lb = _kde_eval_call("kld", b, a, bw_b, False, ctx)
+    out = np.mean(la - lb, axis=1)
+    return float(out[0]) if single else out
+
+
+def _initialised(name, fg, label, which=""):
+    if not fg.exists(label) or not fg.isInitialized(label):
+        raise ValueError("%s: variable %s is not initialised%s" % (name, label, which))
+
+
+def evalBelief(fg, label, pts, log=True):
+    """The belief of `label` called as a function, `getBelief(fg, label)(pts)`: its density at pts (dim, Q) -> (Q,); log=True returns
+    the log-density (kde_logpdf, bandwidths by kde_bandwidth), which does not underflow far from the particles."""
+    _initialised("evalBelief", fg, label)
+    lp = kde_logpdf(fg.getVal(label), pts)
+    return lp if log else np.exp(lp)
+
+
+def beliefLogLikelihood(fg, truth):
+    """{label: log-density of the belief of label at truth[label]} for truth = {label: coordinates (dim,)} -- what
+    examples/RangesExampleTwo.jl:388-400 prints after every solve.  One kde_bandwidth and one rome_kde_eval call per variable type.
+    A label that is missing or uninitialised raises, by name."""
+    by_type = {}
+    for l in truth:
+        _initialised("beliefLogLikelihood", fg, l)
+        vt = fg.variables[l]
+        x = _d(truth[l]).reshape(-1)
+        if x.shape != (vt.dim,):
+            raise ValueError("beliefLogLikelihood: truth[%s] must have %d coordinates, got %s" % (l, vt.dim, x.shape))
+        by_type.setdefault(vt, []).append((l, x))
+    res = {}
+    for vt, items in by_type.items():
+        bel = _d(np.stack([fg.getVal(l) for l, _ in items]))
+        pts = _d(np.stack([x for _, x in items])[:, :, None])
+        lp = _kde_eval_call("beliefLogLikelihood", bel, pts, None, False, None)
+        res.update((l, float(v)) for (l, _), v in zip(items, lp[:, 0]))
+    return {l: res[l] for l in truth}
+
+
+def kldBeliefs(fg_a, fg_b, labels=None):
+    """{label: kld(belief of label in fg_a, belief of label in fg_b)} for `labels` (default: every variable of fg_a), by variable type.
+    A label that is missing or uninitialised in either graph raises, by name."""
+    labels = list(fg_a.ls() if labels is None else labels)
+    by_type = {}
+    for l in labels:
+        _initialised("kldBeliefs", fg_a, l, " in the first graph")
+        _initialised("kldBeliefs", fg_b, l, " in the second graph")
+        if fg_a.variables[l] is not fg_b.variables[l]:
+            raise ValueError("kldBeliefs: variable %s has different types in the two graphs" % l)
+        by_type.setdefault(fg_a.variables[l], []).append(l)
+    res = {}
+    for vt, ls in by_type.items():
+        out = kld(np.stack([fg_a.getVal(l) for l in ls]), np.stack([fg_b.getVal(l) for l in ls]))
+        res.update(zip(ls, out.tolist()))
+    return {l: res[l] for l in labels}
+
+
 def kde_bandwidth(bel, circular_mask=None, tol_euclid=0.0, tol_circular=0.0, ctx=None):
     """bel (V, dim, N) host array -> (V, dim) bandwidths as `manikde!` selects them (leave-one-out likelihood
     cross-validation per coordinate), via rome_kde_bandwidth.  circular_mask: bit k set = coordinate k is an angle

@@ -143,6 +143,59 @@ int rome_mmd(rome_ctx* c, int32_t layout, int32_t dim, int32_t P, int32_t Na, in
   ROME_HIP(c, hipStreamSynchronize(s));
   return ROME_OK;
 }
+/* ---- kde_eval ---- */
+static int check_kde_eval(rome_ctx* c, int32_t dim, int32_t P, int32_t N, const double* bel, const double* bw, int32_t Q, const double* queries,
+                          int32_t leave_one_out, const double* out) {
+  if (!c || P < 0 || Q < 0 || N < 1 || (dim != 2 && dim != 3 && dim != 6)) return ROME_ERR_INVALID_ARG;
+  if (!queries && Q != N) return ROME_ERR_INVALID_ARG;                           /* self-evaluation: the queries are the N particles */
+  if (leave_one_out && (queries || N < 2)) return ROME_ERR_INVALID_ARG;
+  if (P > 0 && Q > 0 && (!bel || !bw || !out)) return ROME_ERR_INVALID_ARG;
+  if ((int64_t)P * ((Q + 255) / 256) > INT32_MAX) return ROME_ERR_INVALID_ARG;   /* one block per (pair, 256 queries) on a 1-D grid */
+  if (N > ROME_MAX_PARTICLES_KDE_EVAL) return ROME_ERR_UNSUPPORTED_N;            /* the belief lives in LDS */
+  return ROME_OK;
+}
+int rome_kde_eval_dev(rome_ctx* c, int32_t dim, int32_t P, int32_t N, const double* bel, const int32_t* bel_rows, const double* bw, int32_t Q,
+                      const double* queries, const int32_t* query_rows, int32_t leave_one_out, double* out) {
+  int rc = check_kde_eval(c, dim, P, N, bel, bw, Q, queries, leave_one_out, out); if (rc) return rc;
+  if (P == 0 || Q == 0) return ROME_OK;
+  ROME_BIND(c);
+  ROME_HIP(c, launch_kde_eval(dim, P, N, bel, bel_rows, bw, Q, queries, query_rows, leave_one_out, out, c->stream));
+  return ROME_OK;
+}
+int rome_kde_eval(rome_ctx* c, int32_t layout, int32_t dim, int32_t P, int32_t N, int32_t n_bel_blocks, const double* bel,
+                  const int32_t* bel_rows, const double* bw, int32_t Q, int32_t n_query_blocks, const double* queries,
+                  const int32_t* query_rows, int32_t leave_one_out, double* out) {
+  int rc = check_kde_eval(c, dim, P, N, bel, bw, Q, queries, leave_one_out, out); if (rc) return rc;
+  if (layout != ROME_LAYOUT_SOA && layout != ROME_LAYOUT_AOS && layout != ROME_LAYOUT_AOS_POINTS) return ROME_ERR_INVALID_ARG;
+  if (n_bel_blocks < 0 || n_query_blocks < 0 || !mmd_rows_ok(bel_rows, P, n_bel_blocks)) return ROME_ERR_INVALID_ARG;
+  if (queries && !mmd_rows_ok(query_rows, P, n_query_blocks)) return ROME_ERR_INVALID_ARG;
+  if (bw) for (size_t k = 0; k < (size_t)n_bel_blocks * dim; ++k) if (!std::isfinite(bw[k]) || !(bw[k] > 0.0)) return ROME_ERR_INVALID_ARG;
+  if (P == 0 || Q == 0) return ROME_OK;
+  ROME_HIP(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  void *d_b, *d_q = nullptr, *d_o, *d_h, *d_br = nullptr, *d_qr = nullptr;
+  const size_t np = (size_t)P, nh = 8ull * n_bel_blocks * dim, no = 8 * np * Q;
+  if ((rc = ensure(c, 0, 8ull * n_bel_blocks * dim * N, &d_b))) return rc;
+  if (queries && (rc = ensure(c, 1, 8ull * n_query_blocks * dim * Q, &d_q))) return rc;
+  if ((rc = ensure(c, 2, no, &d_o))) return rc;
+  if ((rc = ensure(c, 3, nh, &d_h))) return rc;
+  if ((rc = stage_blocks(c, layout, n_bel_blocks, dim, N, bel, (double*)d_b))) return rc;
+  if (queries && (rc = stage_blocks(c, layout, n_query_blocks, dim, Q, queries, (double*)d_q))) return rc;
+  ROME_HIP(c, hipMemcpyAsync(d_h, bw, nh, hipMemcpyHostToDevice, s));
+  if (bel_rows) {
+    if ((rc = ensure(c, 4, 4 * np, &d_br))) return rc;
+    ROME_HIP(c, hipMemcpyAsync(d_br, bel_rows, 4 * np, hipMemcpyHostToDevice, s));
+  }
+  if (queries && query_rows) {
+    if ((rc = ensure(c, 5, 4 * np, &d_qr))) return rc;
+    ROME_HIP(c, hipMemcpyAsync(d_qr, query_rows, 4 * np, hipMemcpyHostToDevice, s));
+  }
+  ROME_HIP(c, launch_kde_eval(dim, P, N, (const double*)d_b, (const int32_t*)d_br, (const double*)d_h, Q, (const double*)d_q,
+                              (const int32_t*)d_qr, leave_one_out, (double*)d_o, s));
+  ROME_HIP(c, hipMemcpyAsync(out, d_o, no, hipMemcpyDeviceToHost, s));
+  ROME_HIP(c, hipStreamSynchronize(s));
+  return ROME_OK;
+}
 
 static int check_kde(rome_ctx* c, int32_t dim, int32_t V, int32_t N, const double* bel, const double* bw) {
   if (!c || V < 0 || N < 2 || N > ROME_MAX_PARTICLES_REGISTER || dim < 1 || dim > 6 || (V > 0 && (!bel || !bw))) return ROME_ERR_INVALID_ARG;

@@ -106,6 +106,11 @@ hipError_t launch_belief_stats(int dim, int V, int N, const double* bel, double*
 // scale: HOST [dim] weights or null (ones), passed by value; out [P], sums [P][3] or null; Na, Nb <= 512
 hipError_t launch_mmd(int dim, int P, int Na, const double* a, const int32_t* a_rows, int Nb, const double* b, const int32_t* b_rows,
                       const double* scale, double sigma, double* out, double* sums, hipStream_t s);
+// log-density of P beliefs at Q query points each: pair p evaluates block bel_rows[p] of bel ([.][dim][N], bandwidths bw[bel_rows[p]][dim])
+// at block query_rows[p] of queries ([.][dim][Q]) (null tables: p; null queries: the belief's own points, Q == N); leave_one_out only
+// with null queries and N >= 2; out [P][Q]; N <= 512
+hipError_t launch_kde_eval(int dim, int P, int N, const double* bel, const int32_t* bel_rows, const double* bw, int Q, const double* queries,
+                           const int32_t* query_rows, int leave_one_out, double* out, hipStream_t s);
 // block_idx: optional [V] block of `bel` that belief v lives in (nullptr: v) -- the bandwidths of a scattered subset of a store
 hipError_t launch_kde_bandwidth(int dim, int V, int N, const double* bel, uint32_t circ_mask, double tol_e, double tol_c,
                                 double* bw, hipStream_t s, const int32_t* block_idx = nullptr);

@@ -8,10 +8,14 @@
 //    (unvendored multiscale Gibbs product): the definition is the one in
 //    oracle/rome_oracle.c (ro_product, ro_product_bw) and is only claimed statistically against the reference.
 //  * k_mmd<M>: maximum mean discrepancy between two particle sets (AMP `mmd`), one 256-thread block per pair of sets.
+//  * k_kde_eval<M>: log-density of a belief's kernel density estimate at query points (the belief called as a function, AMP
+//    `evaluateDualTree`), one 256-thread block per (belief, tile of 256 queries).
 // All are written once over a manifold policy M (Flat<2> Point2, Flat<3> Pose2, Se3M Pose3), which holds everything that
 // differs between the variable types.  Belief statistics: one wave (64-thread block) per variable.  Product: one 256-thread
 // block per variable (see k_product); weights are scanned in particle order so the resampling picks are the same as a
 // sequential CPU scan.
+#include <cmath>
+
 #include "rome_device_math.hpp"
 #include "rome_kernels.h"
 
@@ -261,6 +265,62 @@ __global__ void __launch_bounds__(kMmdThreads) k_mmd(const MmdArgs g) {
   }
 }
 
+// ---- kde_eval: log-density of a belief at query points -------------------------------------------------------------------------
+// out[p][i] = −½ q_min + log Σ_j exp(−½ (q_j − q_min)) − log N' − Σ_k log h_k − (D/2) log 2π,  q_j = M::dist2(x_i, y_j, 1/h) (saturated
+// at 1e300, so that the result is finite for every finite input), j in particle order, the running-minimum sum of k_product.  Block
+// b serves pair p = b / tiles and queries 256·(b mod tiles) ..: the N points of belief block bel_rows[p] are staged once in dynamic LDS
+// (M::load / M::put: one quat_exp per point), then each thread owns one query and walks the points at a wave-uniform LDS address.
+// The arithmetic of a query is that of its thread alone and does not involve tid: the bits of out[p][i] depend on the belief block, its
+// bandwidth row and the query, not on Q, P or the query's place.  Self-evaluation (queries == null, Q == N) loads the queries from the
+// belief block through the same M::load; leave-one-out skips j == i and counts N' = N − 1.
+constexpr int kKdeEvalThreads = 256;
+constexpr int kKdeEvalMaxN = 512;
+
+struct KdeEvalArgs {
+  int N, Q, tiles, loo;
+  const double* bel;           // [rows][D][N]
+  const int32_t* bel_rows;     // [P] block of `bel` (and row of `bw`) of pair p, or null: p
+  const double* bw;            // [rows][D]
+  const double* queries;       // [rows][D][Q], or null: the pair's own belief block (Q == N)
+  const int32_t* query_rows;
+  double c0;                   // log N' + (D/2) log 2π
+  double* out;                 // [P][Q]
+};
+
+template <class M>
+__global__ void __launch_bounds__(kKdeEvalThreads) k_kde_eval(const KdeEvalArgs g) {
+  constexpr int D = M::D;
+  extern __shared__ double kde_eval_pts[];
+  const int tid = threadIdx.x, N = g.N, Q = g.Q;
+  const int p = blockIdx.x / g.tiles, tile = blockIdx.x - p * g.tiles;
+  const int brow = g.bel_rows ? g.bel_rows[p] : p;
+  const double* B = g.bel + (size_t)brow * D * N;
+  const LdsLines Y{kde_eval_pts, N};
+  mmd_stage<M>(B, N, tid, Y);
+  __syncthreads();
+  const int i = tile * kKdeEvalThreads + tid;
+  if (i >= Q) return;
+  const double* X = g.queries ? g.queries + (size_t)(g.query_rows ? g.query_rows[p] : p) * D * Q : B;
+  typename M::Pt x;
+  M::load(X, Q, i, x);
+  double ih[D], lnh = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) { const double h = g.bw[(size_t)brow * D + k]; ih[k] = 1.0 / h; lnh += fast_log(h); }
+  const int skip = g.loo ? i : -1;
+  double qmin = __builtin_inf(), sacc = 0.0;
+  for (int j = 0; j < N; ++j) {
+    if (j == skip) continue;
+    typename M::Pt y;
+    M::get(Y, j, y);
+    const double q = fmin(M::dist2(x, y, ih), 1e300);
+    const double dq = q - qmin;
+    const double e = fast_exp_neg(-0.5 * fabs(dq));
+    sacc = dq < 0.0 ? fma(sacc, e, 1.0) : sacc + e;
+    qmin = fmin(qmin, q);
+  }
+  g.out[(size_t)p * Q + i] = ((-0.5 * qmin + fast_log(sacc)) - lnh) - g.c0;
+}
+
 struct ProductArgs {
   int V, N;
   const int32_t* prop_ptr;   // [V+1]
@@ -505,6 +565,28 @@ hipError_t launch_mmd(int dim, int P, int Na, const double* a, const int32_t* a_
   if (dim == 2) return launch_mmd_of<Flat<2>>(P, g, s);
   if (dim == 3) return launch_mmd_of<Flat<3>>(P, g, s);
   if (dim == 6) return launch_mmd_of<Se3M>(P, g, s);
+  return hipErrorInvalidValue;
+}
+
+template <class M>
+static hipError_t launch_kde_eval_of(int P, const KdeEvalArgs& g, hipStream_t s) {
+  const size_t lds = sizeof(double) * M::kLds * (size_t)g.N;   // <= 28 KiB at 512 Pose3 points
+  hipLaunchKernelGGL(k_kde_eval<M>, dim3((unsigned)(P * g.tiles)), dim3(kKdeEvalThreads), lds, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_kde_eval(int dim, int P, int N, const double* bel, const int32_t* bel_rows, const double* bw, int Q, const double* queries,
+                           const int32_t* query_rows, int leave_one_out, double* out, hipStream_t s) {
+  if (P <= 0 || Q <= 0) return hipSuccess;
+  if (N < 1 || N > kKdeEvalMaxN || (!queries && Q != N) || (leave_one_out && (queries || N < 2))) return hipErrorInvalidValue;
+  KdeEvalArgs g;
+  g.N = N; g.Q = Q; g.tiles = (Q - 1) / kKdeEvalThreads + 1; g.loo = leave_one_out ? 1 : 0;
+  if ((long long)P * g.tiles > 0x7fffffffLL) return hipErrorInvalidValue;   // blocks of a 1-D grid
+  g.bel = bel; g.bel_rows = bel_rows; g.bw = bw; g.queries = queries; g.query_rows = query_rows; g.out = out;
+  g.c0 = std::log((double)(leave_one_out ? N - 1 : N)) + 0.5 * dim * 1.8378770664093453;   // log 2π
+  if (dim == 2) return launch_kde_eval_of<Flat<2>>(P, g, s);
+  if (dim == 3) return launch_kde_eval_of<Flat<3>>(P, g, s);
+  if (dim == 6) return launch_kde_eval_of<Se3M>(P, g, s);
   return hipErrorInvalidValue;
 }
 

@@ -672,6 +672,36 @@ class DeviceGraph:
                                                     float(tol_euclid), float(tol_circular), bw.data_ptr()), self.ctx.handle)
         return bw
 
+    def logpdf(self, vartype, queries=None, bw=None, leave_one_out=False, out=None):
+        """[V, Q] log-densities (rome_kde_eval_dev; api.kde_logpdf on store-resident beliefs) of every belief of one variable type at
+        the Q points of the same block of `queries`, a device tensor [V][dim][Q]; None evaluates each belief at its own N particles, and
+        leave_one_out then leaves each particle out of its own density.  bw: [V][dim] device tensor of kernel bandwidths, default
+        self.kde_bandwidths(vartype).  No host round trip, capturable (pass `out` to keep the result outside the graph's memory pool)."""
+        torch = self.torch
+        b = self.bel[vartype]
+        V, d, N = b.shape
+
+        def ok(t, shape):
+            return tuple(t.shape) == shape and t.dtype == torch.float64 and t.device == b.device and t.is_contiguous()
+        if queries is not None and not (queries.dim() == 3 and ok(queries, (V, d, queries.shape[2]))):
+            raise ValueError("DeviceGraph.logpdf: `queries` must be a contiguous float64 tensor of shape (%d, %d, Q) on %s" % (V, d, b.device))
+        if leave_one_out and (queries is not None or N < 2):
+            raise ValueError("DeviceGraph.logpdf: leave_one_out applies to self-evaluation (queries=None) of at least 2 particles")
+        Q = N if queries is None else queries.shape[2]
+        if bw is None:
+            bw = self.kde_bandwidths(vartype)
+        elif not ok(bw, (V, d)):
+            raise ValueError("DeviceGraph.logpdf: `bw` must be a contiguous float64 tensor of shape %s on %s" % ((V, d), b.device))
+        if out is None:
+            out = torch.empty((V, Q), dtype=torch.float64, device=self.device)
+        elif not ok(out, (V, Q)):
+            raise ValueError("DeviceGraph.logpdf: `out` must be a contiguous float64 tensor of shape %s on %s" % ((V, Q), b.device))
+        self._bind_stream()
+        _lib.check(self._lib.rome_kde_eval_dev(self.ctx.handle, d, V, N, b.data_ptr(), None, bw.data_ptr(), Q,
+                                               None if queries is None else queries.data_ptr(), None, 1 if leave_one_out else 0,
+                                               out.data_ptr()), self.ctx.handle)
+        return out
+
     def download_beliefs(self, fg):
         for vt in (Pose2, Point2, Pose3):
             h = self.bel[vt].cpu().numpy()

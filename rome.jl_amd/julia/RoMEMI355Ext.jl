@@ -762,6 +762,27 @@ function approxDeconv(dfg::AbstractDFG, flabel::Symbol; solveKey::Symbol=:defaul
   deconv(dfg, f, getVal(dfg, vars[1]; solveKey), getVal(dfg, vars[2]; solveKey))
 end
 
+# ---- belief evaluation on the device (rome_kde_eval; the belief called as a function, `getBelief(fg, :x)(pts)`) ------------------
+# bel, pts: vectors of the reference's native points of ONE variable type, as in mmd (ROME_LAYOUT_AOS_POINTS); bw: the dim kernel
+# bandwidths (kde_bandwidths of the belief's coordinates).  pts === nothing evaluates the belief at its own points; leave_one_out then
+# leaves each point out of its own density.  -> the log-densities, one per query (tangent coordinates; see the header on what is not
+# checked against AMP).
+function kde_logpdf(bel::Vector{P}, bw::Vector{Float64}, pts::Union{Nothing,Vector{P}}=nothing; leave_one_out::Bool=false) where {P}
+  d = _mmd_dim(P)
+  length(bw) == d || error("kde_logpdf: bw must have $d entries for points of type $P")
+  pts === nothing || !leave_one_out || error("kde_logpdf: leave_one_out applies to self-evaluation (pts === nothing)")
+  nq = pts === nothing ? length(bel) : length(pts)
+  out = Vector{Float64}(undef, nq)
+  GC.@preserve bel pts bw out begin
+    check(ccall((:rome_kde_eval, LIB), Cint,
+      (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Int32, Int32, Ptr{Float64}, Ptr{Int32}, Int32,
+       Ptr{Float64}),
+      ctx().h, 2, d, 1, length(bel), 1, Ptr{Float64}(pointer(bel)), C_NULL, bw, nq, pts === nothing ? 0 : 1,
+      pts === nothing ? Ptr{Float64}(C_NULL) : Ptr{Float64}(pointer(pts)), C_NULL, leave_one_out ? 1 : 0, out))
+  end
+  out
+end
+
 # ---- stage 2 of the partial-aware product (rome_product_partial; include/rome_mi355.h, DESIGN.md §12d) -----------
 # prop: N x dim x rows, bel: N x dim x V (exactly the C side's SoA blocks [.][dim][N]); bel holds the product of the full proposals on
 # entry and is updated in place.  The task tables are 0-based, as the header defines them: task t rewrites coordinate task_coord[t] of
