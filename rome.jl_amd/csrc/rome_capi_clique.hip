@@ -1,87 +1,37 @@
 // rome_capi_clique.hip -- the clique batch, the device-resident belief store and the three plan kinds (up-solve, scatter, block operations)
-// behind the extern "C" boundary of librome_mi355.so.  Host-side plumbing only.
+// behind the extern "C" boundary of librome_mi355.so.  Host-side plumbing only, and of that only what calls HIP: the row families, the
+// validation and update index of an up-solve description and the layout of the three device arenas used here (clique proposals, plan,
+// temporary store of the one-shot up-solve) are host-only code in rome_upsolve_index.h.  An arena is never sized by hand: `carve` runs
+// its layout function with a measuring cursor, gets memory of exactly that size, runs it again to place, then uploads.
 #include "rome_capi_internal.h"
 
 using namespace rome;
 
 /* ---- clique-level batch from host beliefs ---- */
 namespace {
-// the five row families of a rome_clique_host.  kind: 0 Pose2Pose2 (+ PriorPose2 rows), 1 bearing-range, 2 Pose3Pose3 (+ PriorPose3 rows),
-// 3 PriorPoint2 sampler; variable types: 0 Pose2, 1 Point2, 2 Pose3; valt = type of the array an `alt` entry indexes (-1: no multihypo);
-// base = first row of the family in the proposal buffer of its target type (rome_clique_upsolve)
-struct Fam {
-  int n; const int32_t* rows4; int F; const double* mu; const double* spread; int dz, nL, dfx, dt; double* out; int vf, vt; int dir_all;
-  uint64_t off; int kind; int base;
-  const int32_t* alt; const double* hw; const double* nh; const int32_t* sid; int valt;
-  const int32_t* meas;   // per-row block of the measurement samples (Pose2Pose2 / bearing-range / Pose3Pose3 rows), or nullptr
-  int vmeas() const { return kind == 1 ? 1 : (kind == 2 ? 2 : 0); }   // variable type of the store array a `meas` entry indexes
-};
-constexpr int NF = 5;
-void make_fams(const rome_clique_host* q, Fam (&fam)[NF]) {
-  const Fam f[NF] = {
-    {q->n_p2p2, q->p2p2_rows4, q->f_p2p2, q->p2p2_mu, q->p2p2_cov, 3, 6, 3, 3, q->out_p2p2, 0, 0, 0, 0ull, 0, 0,
-     q->p2p2_alt, q->p2p2_hypo_w, q->p2p2_nullhypo, q->p2p2_stream, 0, q->p2p2_meas},
-    {q->n_br1, q->br1_rows4, q->f_br, q->br_mu, q->br_sigma, 2, 2, 2, 3, q->out_br1, 1, 0, 1, 1ull << 28, 1, q->n_p2p2,
-     q->br1_alt, q->br1_hypo_w, q->br1_nullhypo, q->br1_stream, 1, q->br1_meas},
-    {q->n_br0, q->br0_rows4, q->f_br, q->br_mu, q->br_sigma, 2, 2, 3, 2, q->out_br0, 0, 1, 0, 2ull << 28, 1, 0,
-     q->br0_alt, q->br0_hypo_w, q->br0_nullhypo, q->br0_stream, 1, q->br0_meas},
-    {q->n_p3p3, q->p3p3_rows4, q->f_p3p3, q->p3p3_mu, q->p3p3_cov, 6, 21, 6, 6, q->out_p3p3, 2, 2, 0, 5ull << 28, 2, 0,
-     nullptr, nullptr, q->p3p3_nullhypo, q->p3p3_stream, -1, q->p3p3_meas},
-    {q->n_prpt2, q->prpt2_rows4, q->f_prpt2, q->prpt2_mu, q->prpt2_cov, 2, 3, 2, 2, q->out_prpt2, 1, 1, 0, 7ull << 28, 3, q->n_br0,
-     nullptr, nullptr, nullptr, q->prpt2_stream, -1, nullptr}};
-  for (int k = 0; k < NF; ++k) fam[k] = f[k];
-}
-// table entries must address the arrays they index (nv = variables per type); hypothesis / stream columns in range
-int check_fam_rows(const Fam& f, const int (&nv)[3]) {
-  if (f.n < 0 || f.F < 0 || (f.n > 0 && (!f.rows4 || !f.mu || !f.spread || f.F == 0))) return ROME_ERR_INVALID_ARG;
-  if (f.alt && !f.hw) return ROME_ERR_INVALID_ARG;
-  for (int r = 0; r < f.n; ++r) {
-    const int32_t* e = f.rows4 + 4 * (size_t)r;
-    if (e[0] < 0 || e[0] >= f.F || e[2] < 0 || e[2] >= nv[f.vf] || e[3] < 0 || e[3] >= nv[f.vt] || e[1] < 0 || e[1] > 2) return ROME_ERR_INVALID_ARG;
-    if (f.alt && f.alt[r] >= 0) {
-      if (f.alt[r] >= nv[f.valt] || !(f.hw[r] >= 0.0 && f.hw[r] <= 1.0)) return ROME_ERR_INVALID_ARG;
-    } else if (f.alt && f.alt[r] < -1) return ROME_ERR_INVALID_ARG;
-    if (f.nh && !(f.nh[r] >= 0.0 && f.nh[r] <= 1.0)) return ROME_ERR_INVALID_ARG;
-    if (f.sid && (f.sid[r] < 0 || f.sid[r] >= (1 << 28))) return ROME_ERR_INVALID_ARG;
-    if (f.meas && (f.meas[r] < -1 || f.meas[r] >= nv[f.vmeas()] || (f.meas[r] >= 0 && e[1] == 2))) return ROME_ERR_INVALID_ARG;
-  }
-  return ROME_OK;
-}
-// bytes of a family's device tables (rows4, mu, L, the optional columns)
-size_t fam_table_bytes(const Fam& f) {
-  return al256((size_t)f.n * 16) + al256((size_t)f.F * f.dz * 8) + al256((size_t)f.F * f.nL * 8) + 256 +
-         (f.alt ? al256((size_t)f.n * 4) + al256((size_t)f.n * 8) : 0) + (f.nh ? al256((size_t)f.n * 8) : 0) + (f.sid ? al256((size_t)f.n * 4) : 0) +
-         (f.meas ? al256((size_t)f.n * 4) : 0);
-}
-struct FamDev { const int32_t* rows = nullptr; const double* mu = nullptr; const double* L = nullptr; const int32_t* alt = nullptr;
-                const double* hw = nullptr; const double* nh = nullptr; const int32_t* sid = nullptr; const int32_t* meas = nullptr; };
-// uploads a family's tables into `arena` (asynchronously: `Ls` must outlive the stream work); MvNormal factors get their packed Cholesky
-int upload_fam(rome_ctx* c, const Fam& f, unsigned char* arena, size_t* used, std::vector<double>& Ls, FamDev& d) {
-  d = FamDev{};
-  if (f.n == 0) return ROME_OK;
-  hipStream_t s = c->stream;
-  const double* Lsrc = f.spread;
+// An arena from its layout function `lay(cursor)`: measured, obtained from `memory(bytes, &p)` (-> ROME_OK or an error), placed, and
+// the copies it owes issued on the context's stream (asynchronous: their sources must outlive the stream work)
+template <class Memory, class Lay> int carve(rome_ctx* c, Memory&& memory, Lay&& lay) {
+  ArenaCursor measure;
+  (void)lay(measure);
+  void* arena = nullptr;
   int rc;
-  if (f.kind != 1) {   // MvNormal factors: packed lower Cholesky of every covariance
-    Ls.resize((size_t)f.F * f.nL);
-    if ((rc = rome_cholesky_lower(f.dz, f.F, f.spread, Ls.data()))) return rc;
-    Lsrc = Ls.data();
-  }
-  auto put = [&](const void* src, size_t bytes) -> void* {
-    void* dst = arena + *used;
-    if (hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) != hipSuccess) return nullptr;
-    *used += al256(bytes);
-    return dst;
-  };
-#define ROME_PUT(dst, T, src, bytes) do { void* _p = put((src), (bytes)); if (!_p) return hip_fail(c, hipGetLastError()); (dst) = (const T*)_p; } while (0)
-  ROME_PUT(d.rows, int32_t, f.rows4, (size_t)f.n * 16);
-  ROME_PUT(d.mu, double, f.mu, (size_t)f.F * f.dz * 8);
-  ROME_PUT(d.L, double, Lsrc, (size_t)f.F * f.nL * 8);
-  if (f.alt) { ROME_PUT(d.alt, int32_t, f.alt, (size_t)f.n * 4); ROME_PUT(d.hw, double, f.hw, (size_t)f.n * 8); }
-  if (f.nh) ROME_PUT(d.nh, double, f.nh, (size_t)f.n * 8);
-  if (f.sid) ROME_PUT(d.sid, int32_t, f.sid, (size_t)f.n * 4);
-  if (f.meas) ROME_PUT(d.meas, int32_t, f.meas, (size_t)f.n * 4);
-#undef ROME_PUT
+  if ((rc = memory(measure.used, &arena))) return rc;
+  ArenaCursor place(arena, measure.used);
+  if ((rc = lay(place))) return rc;
+  return place.commit([c](void* dst, const void* src, size_t bytes) {
+    const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream);
+    return e == hipSuccess ? ROME_OK : hip_fail(c, e);
+  });
+}
+// the same from workspace `idx` of the context
+template <class Lay> int carve_ctx(rome_ctx* c, int idx, Lay&& lay) {
+  return carve(c, [=](size_t bytes, void** p) { return ensure(c, idx, bytes, p); }, lay);
+}
+// the host beliefs of the three variable types (caller's layout) -> their blocks in an arena (lay_beliefs)
+int stage_beliefs(rome_ctx* c, int layout, const int (&nv)[3], int N, const double* const (&host)[3], double* const (&bel)[3]) {
+  for (int t = 0; t < 3; ++t)
+    if (int rc = stage_blocks(c, layout, nv[t], kVdim[t], N, host[t], bel[t])) return rc;
   return ROME_OK;
 }
 // rows [lo, hi) of a family: one convolution launch into `out` (the block of row `lo`)
@@ -111,43 +61,26 @@ int rome_clique_proposals(rome_ctx* c, const rome_opts* o, const rome_clique_hos
   const int N = o->n_particles;
   Fam fam[NF]; make_fams(q, fam);
   const int nv[3] = {q->n_pose2, q->n_point2, q->n_pose3};
-  const int vdim[3] = {3, 2, 6};
-  const double* vhost[3] = {q->bel_pose2, q->bel_point2, q->bel_pose3};
-  size_t need = 0;
-  for (int t = 0; t < 3; ++t) { if (nv[t] < 0 || (nv[t] > 0 && !vhost[t])) return ROME_ERR_INVALID_ARG; need += al256((size_t)nv[t] * vdim[t] * N * 8); }
+  const double* const vhost[3] = {q->bel_pose2, q->bel_point2, q->bel_pose3};
+  for (int t = 0; t < 3; ++t) if (nv[t] < 0 || (nv[t] > 0 && !vhost[t])) return ROME_ERR_INVALID_ARG;
   for (const Fam& f : fam) {
     if ((rc = check_fam_rows(f, nv))) return rc;
     if (f.n > 0 && !f.out) return ROME_ERR_INVALID_ARG;
     if (f.meas) return ROME_ERR_INVALID_ARG;   // measurement-sample rows address a store (rome_upsolve_plan)
-    need += al256((size_t)f.n * f.dt * N * 8) + fam_table_bytes(f);
   }
   ROME_BIND(c);
-  void* arena_v = nullptr;
-  if ((rc = ensure(c, 9, need + 4096, &arena_v))) return rc;
-  unsigned char* arena = (unsigned char*)arena_v;
-  size_t used = 0;
-  double* dbel[3];
-  for (int t = 0; t < 3; ++t) {
-    dbel[t] = (double*)(arena + used);
-    if ((rc = stage_blocks(c, o->layout, nv[t], vdim[t], N, vhost[t], dbel[t]))) return rc;
-    used += al256((size_t)nv[t] * vdim[t] * N * 8);
-  }
+  std::vector<double> Ls[NF];
+  ProposalsArena A;
   hipStream_t s = c->stream;
-  std::vector<std::vector<double>> Ls(NF);
   DrainOnExit drain{s};
-  double* dout[NF] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  for (int k = 0; k < NF; ++k) {
-    const Fam& f = fam[k];
-    if (f.n == 0) continue;
-    FamDev d;
-    if ((rc = upload_fam(c, f, arena, &used, Ls[k], d))) return rc;
-    dout[k] = (double*)(arena + used);
-    used += al256((size_t)f.n * f.dt * N * 8);
-    ROME_HIP(c, launch_fam(f, d, o, o->stream_offset, 0, f.n, dbel[f.vf], dbel[f.vt], dout[k], s));
-  }
+  if ((rc = carve_ctx(c, 9, [&](ArenaCursor& a) { return lay_proposals(a, fam, nv, N, Ls, A); }))) return rc;
+  if ((rc = stage_beliefs(c, o->layout, nv, N, vhost, A.bel))) return rc;
+  for (int k = 0; k < NF; ++k)
+    if (fam[k].n > 0)
+      ROME_HIP(c, launch_fam(fam[k], A.fd[k], o, o->stream_offset, 0, fam[k].n, A.bel[fam[k].vf], A.bel[fam[k].vt], A.out[k], s));
   // proposals back to the host in the caller's layout
   for (int k = 0; k < NF; ++k)
-    if ((rc = fetch_blocks(c, o->layout, fam[k].n, fam[k].dt, N, dout[k], fam[k].out))) return rc;
+    if ((rc = fetch_blocks(c, o->layout, fam[k].n, fam[k].dt, N, A.out[k], fam[k].out))) return rc;
   return ROME_OK;
 }
 
@@ -176,199 +109,74 @@ struct rome_blockop_plan {
 };
 struct rome_upsolve_plan {
   rome_ctx* ctx = nullptr; rome_store* st = nullptr;
-  int N = 0, layout = 0, gi = 3, pi = 1, n_up = 0;
-  Fam fam[NF]; FamDev fd[NF];
-  std::vector<int> fam_lo[NF];            // first row of family f that targets update position >= k (rows are grouped in update order)
-  std::vector<int> step_k;                // boundaries of the update steps (ranges of the update list updated together)
-  std::vector<int> up_cnt_before;         // [k][t]: updates of type t among the first k
-  int n_upt[3] = {0, 0, 0}, prop_rows_t[3] = {0, 0, 0}, max_k[3] = {1, 1, 1};
-  double* d_prop[3] = {nullptr, nullptr, nullptr}; double* d_pbw[3] = {nullptr, nullptr, nullptr};
-  int32_t* d_ptr[3] = {nullptr, nullptr, nullptr}; int32_t* d_rws[3] = {nullptr, nullptr, nullptr};
-  int32_t* d_upblock[3] = {nullptr, nullptr, nullptr}; int32_t* d_upstream[3] = {nullptr, nullptr, nullptr};
-  int32_t* d_upmirror[3] = {nullptr, nullptr, nullptr};
-  int32_t* d_gather[3] = {nullptr, nullptr, nullptr};   // (dim, var, position, type) per updated variable: store -> contiguous download buffer
-  double* d_newout[3] = {nullptr, nullptr, nullptr}; double* d_bwout[3] = {nullptr, nullptr, nullptr};
-  double* new_host[3] = {nullptr, nullptr, nullptr}; double* bw_host[3] = {nullptr, nullptr, nullptr};
-  bool has_mirror = false, has_upstream = false;
-  int n_smsg[3] = {0, 0, 0}, smsg_base[3] = {0, 0, 0};   // store-resident messages: rows [smsg_base, smsg_base + n_smsg) of the type's proposal buffer
-  int32_t* d_smsg_ent[3] = {nullptr, nullptr, nullptr};  // (dim, source block, proposal row, type) per message: gathered at the start of every run
+  int N = 0, layout = 0, gi = 3, pi = 1;
+  UpsolveSteps steps;   // (rome_upsolve_index.h; its family tables point nowhere after creation)
+  FamDev fd[NF];
+  struct Type : TypeDev, TypeCounts {   // one variable type: its pieces of the arena, its counts, the host outputs (or nullptr), its tree workspace
+    double* new_host = nullptr; double* bw_host = nullptr;
+    size_t tree_off = 0;
+  } type[3];
   DevBuf arena;   // the plan's device memory (empty when it is carved from the context's arena: the one-shot host entry)
-  size_t tree_need = 8;               // the tree workspaces of the three types side by side (their products may run concurrently)
-  size_t tree_off[3] = {0, 0, 0};
+  size_t tree_need = 8;   // the tree workspaces of the three types side by side (their products may run concurrently)
 };
 
 namespace {
-const int kVdim[3] = {3, 2, 6};
 const uint32_t kCircBw[3] = {0b100u, 0u, 0b111000u}, kCircProd[3] = {0b100u, 0u, 0u};
 const uint64_t kProdOff[3] = {3ull << 28, 4ull << 28, 6ull << 28};
 
-// builds a plan over `st`; ctx_arena: carve the plan's device memory from the context's arena (the one-shot host entry) instead of an
-// allocation the plan owns
+// builds a plan over `st`: the index (host only), then the arena -- measured, allocated, placed and uploaded by one layout function.
+// ctx_arena: carve the plan's device memory from the context's arena (the one-shot host entry) instead of an allocation the plan owns
 int plan_build(rome_ctx* c, rome_store* st, const rome_opts* o, const rome_clique_upsolve_host* u, rome_upsolve_plan* P, bool ctx_arena) {
-  const rome_clique_host* q = &u->clique;
   const int N = o->n_particles;
-  if (N > ROME_MAX_PARTICLES_GIBBS) return ROME_ERR_UNSUPPORTED_N;   // the multiscale Gibbs product: lane = output sample, two wavefronts per variable
+  if (N > ROME_MAX_PARTICLES_GIBBS) return ROME_ERR_UNSUPPORTED_N;
   if (N != st->N) return ROME_ERR_INVALID_ARG;
-  if (N < 2 || u->n_up < 0 || (u->n_up > 0 && (!u->up_type || !u->up_var))) return ROME_ERR_INVALID_ARG;
-  if (u->schedule != ROME_UPSOLVE_SEQUENTIAL && u->schedule != ROME_UPSOLVE_JACOBI) return ROME_ERR_INVALID_ARG;
-  P->ctx = c; P->st = st; P->N = N; P->layout = o->layout; P->n_up = u->n_up;
+  P->ctx = c; P->st = st; P->N = N; P->layout = o->layout;
   P->gi = u->gibbs_iters > 0 ? u->gibbs_iters : 3; P->pi = u->product_iters > 0 ? u->product_iters : 1;
-  const int nv[3] = {st->nv[0], st->nv[1], st->nv[2]};
-  if (q->n_pose2 > nv[0] || q->n_point2 > nv[1] || q->n_pose3 > nv[2]) return ROME_ERR_INVALID_ARG;
-  // ---- update list: (type, variable) -> global position k and position within the type's list
-  std::vector<int> kpos[3], uplist[3];
-  for (int t = 0; t < 3; ++t) kpos[t].assign((size_t)nv[t], -1);
-  P->up_cnt_before.assign((size_t)u->n_up * 3 + 3, 0);
-  for (int k = 0; k < u->n_up; ++k) {
-    const int t = u->up_type[k], v = u->up_var[k];
-    if (t < 0 || t > 2 || v < 0 || v >= nv[t] || kpos[t][v] >= 0) return ROME_ERR_INVALID_ARG;
-    if (u->up_stream && (u->up_stream[k] < 0 || u->up_stream[k] >= (1 << 28))) return ROME_ERR_INVALID_ARG;
-    if (u->up_mirror && u->up_mirror[k] < -1) return ROME_ERR_INVALID_ARG;
-    kpos[t][v] = k;
-    for (int tt = 0; tt < 3; ++tt) P->up_cnt_before[3 * (size_t)(k + 1) + tt] = P->up_cnt_before[3 * (size_t)k + tt] + (tt == t ? 1 : 0);
-    uplist[t].push_back(k);
-  }
-  make_fams(q, P->fam);
-  const int n_msg[3] = {u->n_msg_pose2, u->n_msg_point2, u->n_msg_pose3};
-  const double* msg_host[3] = {u->msg_pose2, u->msg_point2, u->msg_pose3};
-  const int32_t* msg_up[3] = {u->msg_pose2_up, u->msg_point2_up, u->msg_pose3_up};
-  double* new_host[3] = {u->new_pose2, u->new_point2, u->new_pose3};
-  double* bw_host[3] = {u->bw_pose2, u->bw_point2, u->bw_pose3};
-  const int n_smsg[3] = {u->n_smsg_pose2, u->n_smsg_point2, u->n_smsg_pose3};
-  const int32_t* smsg_src[3] = {u->smsg_pose2_src, u->smsg_point2_src, u->smsg_pose3_src};
-  const int32_t* smsg_up[3] = {u->smsg_pose2_up, u->smsg_point2_up, u->smsg_pose3_up};
-  int msg_base[3];
   int rc;
-  for (int t = 0; t < 3; ++t) P->prop_rows_t[t] = 0;
-  for (const Fam& f : P->fam) { if ((rc = check_fam_rows(f, nv))) return rc; P->prop_rows_t[f.vt] += f.n; }
-  for (int t = 0; t < 3; ++t) {
-    if (n_msg[t] < 0 || (n_msg[t] > 0 && (!msg_host[t] || !msg_up[t]))) return ROME_ERR_INVALID_ARG;
-    P->n_upt[t] = (int)uplist[t].size();
-    P->new_host[t] = P->n_upt[t] ? new_host[t] : nullptr; P->bw_host[t] = P->n_upt[t] ? bw_host[t] : nullptr;
-    msg_base[t] = P->prop_rows_t[t]; P->prop_rows_t[t] += n_msg[t];
-    if (n_smsg[t] < 0 || (n_smsg[t] > 0 && (!smsg_src[t] || !smsg_up[t]))) return ROME_ERR_INVALID_ARG;
-    P->n_smsg[t] = n_smsg[t]; P->smsg_base[t] = P->prop_rows_t[t]; P->prop_rows_t[t] += n_smsg[t];
-  }
-  P->has_mirror = u->up_mirror != nullptr; P->has_upstream = u->up_stream != nullptr;
-  // ---- rows: every row targets an updated variable, rows grouped in update order; the row range of every update position; CSR
-  std::vector<std::vector<int>> csr[3];    // per type: proposal rows (in the type's buffer) of every updated variable, in update order
-  for (int t = 0; t < 3; ++t) csr[t].resize(uplist[t].size());
-  for (int k4 = 0; k4 < NF; ++k4) {
-    const Fam& f = P->fam[k4];
-    P->fam_lo[k4].assign((size_t)u->n_up + 1, 0);
-    int prev = -1;
-    for (int r = 0; r < f.n; ++r) {
-      const int32_t* e = f.rows4 + 4 * (size_t)r;
-      const int k = kpos[f.vt][e[3]];
-      if (k < 0 || k < prev) return ROME_ERR_INVALID_ARG;
-      if (k != prev) { for (int kk = prev + 1; kk <= k; ++kk) P->fam_lo[k4][kk] = r; }
-      prev = k;
-      csr[f.vt][(size_t)(P->up_cnt_before[3 * (size_t)k + f.vt])].push_back(f.base + r);
-    }
-    for (int kk = prev + 1; kk <= u->n_up; ++kk) P->fam_lo[k4][kk] = f.n;
-  }
-  for (int t = 0; t < 3; ++t)
-    for (int m = 0; m < n_msg[t]; ++m) {
-      const int k = msg_up[t][m];
-      if (k < 0 || k >= u->n_up || u->up_type[k] != t) return ROME_ERR_INVALID_ARG;
-      csr[t][(size_t)P->up_cnt_before[3 * (size_t)k + t]].push_back(msg_base[t] + m);
-    }
-  std::vector<int32_t> sm_h[3];
-  for (int t = 0; t < 3; ++t)
-    for (int m = 0; m < n_smsg[t]; ++m) {   // store-resident messages: source = a block of the store that this plan does not write
-      const int k = smsg_up[t][m], src = smsg_src[t][m];
-      if (k < 0 || k >= u->n_up || u->up_type[k] != t || src < 0 || src >= nv[t] || kpos[t][src] >= 0) return ROME_ERR_INVALID_ARG;
-      csr[t][(size_t)P->up_cnt_before[3 * (size_t)k + t]].push_back(P->smsg_base[t] + m);
-      sm_h[t].push_back(kVdim[t]); sm_h[t].push_back(src); sm_h[t].push_back(P->smsg_base[t] + m); sm_h[t].push_back(t);
-    }
-  std::vector<int32_t> ptr_h[3], rws_h[3], blk_h[3], sid_h[3], mir_h[3], gat_h[3];
-  for (int t = 0; t < 3; ++t) {
-    P->max_k[t] = 1;
-    ptr_h[t].push_back(0);
-    for (const auto& l : csr[t]) { for (int r : l) rws_h[t].push_back(r); ptr_h[t].push_back((int32_t)rws_h[t].size()); if ((int)l.size() > P->max_k[t]) P->max_k[t] = (int)l.size(); }
-    if (rws_h[t].empty()) rws_h[t].push_back(0);
-    int pos = 0;
-    for (int k : uplist[t]) {
-      blk_h[t].push_back(u->up_var[k]);
-      sid_h[t].push_back(u->up_stream ? u->up_stream[k] : pos);
-      mir_h[t].push_back(u->up_mirror ? u->up_mirror[k] : -1);
-      gat_h[t].push_back(kVdim[t]); gat_h[t].push_back(u->up_var[k]); gat_h[t].push_back(pos); gat_h[t].push_back(t);
-      ++pos;
-    }
-  }
-  // ---- steps: ranges [k0, k1) of the update list that are updated together
-  P->step_k.clear(); P->step_k.push_back(0);
-  if (u->up_group) {
-    for (int k = 1; k < u->n_up; ++k) {
-      if (u->up_group[k] < u->up_group[k - 1]) return ROME_ERR_INVALID_ARG;
-      if (u->up_group[k] != u->up_group[k - 1]) P->step_k.push_back(k);
-    }
-  } else if (u->schedule == ROME_UPSOLVE_SEQUENTIAL) {
-    for (int k = 1; k < u->n_up; ++k) P->step_k.push_back(k);
-  }
-  P->step_k.push_back(u->n_up);
-  // ---- device memory
-  size_t need = 4096;
-  for (int t = 0; t < 3; ++t) {
-    const size_t blk = (size_t)kVdim[t] * N * 8, nu = uplist[t].size();
-    need += al256((size_t)P->prop_rows_t[t] * blk) + al256((size_t)P->prop_rows_t[t] * kVdim[t] * 8) + al256(ptr_h[t].size() * 4) + al256(rws_h[t].size() * 4)
-          + 3 * al256(nu * 4 + 4) + al256(nu * 16 + 16) + al256(nu * blk) + al256(nu * kVdim[t] * 8) + al256((size_t)n_smsg[t] * 16 + 16);
-  }
-  for (const Fam& f : P->fam) need += fam_table_bytes(f);
+  UpsolveIndex X;   // (its tables feed the uploads: declared before the guard that drains the stream)
+  if ((rc = index_upsolve(u, st->nv, N, X))) return rc;
   ROME_BIND(c);
-  void* arena_v = nullptr;
-  if (ctx_arena) { if ((rc = ensure(c, 12, need, &arena_v))) return rc; }
-  else { ROME_HIP(c, P->arena.alloc(need)); arena_v = P->arena.p; }
-  unsigned char* arena = (unsigned char*)arena_v;
-  size_t used = 0;
+  std::vector<double> Ls[NF];
   hipStream_t s = c->stream;
-  std::vector<std::vector<double>> Ls(NF);
-  DrainOnExit drain{s};
-  auto put = [&](const void* src, size_t bytes, void** dst) -> int {
-    *dst = arena + used;
-    if (bytes) ROME_HIP(c, hipMemcpyAsync(*dst, src, bytes, hipMemcpyHostToDevice, s));
-    used += al256(bytes);
+  DrainOnExit drain{s};   // (the uploads have completed before Ls and the caller's tables go away)
+  auto memory = [&](size_t bytes, void** p) -> int {
+    if (ctx_arena) return ensure(c, 12, bytes, p);
+    ROME_HIP(c, P->arena.alloc(bytes));
+    *p = P->arena.p;
     return ROME_OK;
   };
-  auto take = [&](size_t bytes) -> void* { void* p = arena + used; used += al256(bytes); return p; };
+  if ((rc = carve(c, memory, [&](ArenaCursor& a) { return lay_plan(a, X, N, Ls, P->type, P->fd); }))) return rc;
+  const double* msg_host[3] = {u->msg_pose2, u->msg_point2, u->msg_pose3};
+  double* new_host[3] = {u->new_pose2, u->new_point2, u->new_pose3};
+  double* bw_host[3] = {u->bw_pose2, u->bw_point2, u->bw_pose3};
+  P->tree_need = 0;
   for (int t = 0; t < 3; ++t) {
-    const size_t blk = (size_t)kVdim[t] * N * 8, nu = uplist[t].size();
-    P->d_prop[t] = (double*)take((size_t)P->prop_rows_t[t] * blk);
-    P->d_pbw[t] = (double*)take((size_t)P->prop_rows_t[t] * kVdim[t] * 8);
-    P->d_newout[t] = (double*)take(nu * blk);
-    P->d_bwout[t] = (double*)take(nu * kVdim[t] * 8);
-    void* p;
-    if ((rc = put(ptr_h[t].data(), ptr_h[t].size() * 4, &p))) return rc; P->d_ptr[t] = (int32_t*)p;
-    if ((rc = put(rws_h[t].data(), rws_h[t].size() * 4, &p))) return rc; P->d_rws[t] = (int32_t*)p;
-    if ((rc = put(blk_h[t].data(), nu * 4, &p))) return rc; P->d_upblock[t] = (int32_t*)p;
-    if ((rc = put(sid_h[t].data(), nu * 4, &p))) return rc; P->d_upstream[t] = (int32_t*)p;
-    if ((rc = put(mir_h[t].data(), nu * 4, &p))) return rc; P->d_upmirror[t] = (int32_t*)p;
-    if ((rc = put(gat_h[t].data(), nu * 16, &p))) return rc; P->d_gather[t] = (int32_t*)p;
-    if ((rc = put(sm_h[t].data(), (size_t)n_smsg[t] * 16, &p))) return rc; P->d_smsg_ent[t] = (int32_t*)p;
-    if (n_msg[t] > 0) {   // upward messages: appended to the type's proposal buffer, bandwidths once
-      double* mb = P->d_prop[t] + (size_t)msg_base[t] * kVdim[t] * N;
-      if ((rc = stage_blocks(c, o->layout, n_msg[t], kVdim[t], N, msg_host[t], mb))) return rc;
-      ROME_HIP(c, launch_kde_bandwidth(kVdim[t], n_msg[t], N, mb, kCircBw[t], 1e-2, 1e-6,
-                                             P->d_pbw[t] + (size_t)msg_base[t] * kVdim[t], s));
+    const TypeCounts& x = X.type[t];
+    rome_upsolve_plan::Type& y = P->type[t];
+    static_cast<TypeCounts&>(y) = x;
+    if (x.n_up) { y.new_host = new_host[t]; y.bw_host = bw_host[t]; }
+    if (x.n_msg > 0) {   // upward messages: appended to the type's proposal buffer, bandwidths once
+      double* mb = y.prop + (size_t)x.msg_base * kVdim[t] * N;
+      if ((rc = stage_blocks(c, o->layout, x.n_msg, kVdim[t], N, msg_host[t], mb))) return rc;
+      ROME_HIP(c, launch_kde_bandwidth(kVdim[t], x.n_msg, N, mb, kCircBw[t], 1e-2, 1e-6, y.pbw + (size_t)x.msg_base * kVdim[t], s));
     }
-    P->tree_off[t] = t == 0 ? 0 : P->tree_need;
-    if (t == 0) P->tree_need = 0;
-    P->tree_need += al256(gibbs_workspace_bytes(kVdim[t], P->prop_rows_t[t], (int)nu, N)) + 256;
+    y.tree_off = P->tree_need;
+    P->tree_need += al256(gibbs_workspace_bytes(kVdim[t], x.prop_rows, x.n_up, N)) + 256;
   }
-  for (int k4 = 0; k4 < NF; ++k4) if ((rc = upload_fam(c, P->fam[k4], arena, &used, Ls[k4], P->fd[k4]))) return rc;
-  if (used > need) return ROME_ERR_ALLOC;
-  // the host tables must not be referenced after creation (the caller's arrays may go away)
-  for (Fam& f : P->fam) { f.rows4 = nullptr; f.mu = f.spread = nullptr; f.alt = nullptr; f.hw = f.nh = nullptr; f.sid = nullptr; f.out = nullptr; f.meas = nullptr; }
-  return ROME_OK;   // (~DrainOnExit: the uploads have completed before Ls goes away)
+  // what a run reads stays with the plan; the host tables must not be referenced after creation (the caller's arrays may go away)
+  P->steps = std::move(static_cast<UpsolveSteps&>(X));
+  for (Fam& f : P->steps.fam) { f.rows4 = nullptr; f.mu = f.spread = nullptr; f.alt = nullptr; f.hw = f.nh = nullptr; f.sid = nullptr; f.out = nullptr; f.meas = nullptr; }
+  return ROME_OK;
 }
 
 int plan_run(rome_upsolve_plan* P, const rome_opts* o, double* mirror_out, int64_t mirror_stride) {
   rome_ctx* c = P->ctx; rome_store* st = P->st;
+  const UpsolveSteps& X = P->steps;
   const int N = P->N;
   int rc;
-  if (P->has_mirror && !mirror_out) return ROME_ERR_INVALID_ARG;
+  if (X.has_mirror && !mirror_out) return ROME_ERR_INVALID_ARG;
   if (mirror_stride == 0) mirror_stride = 6 * (int64_t)N;
-  if (P->has_mirror)
+  if (X.has_mirror)
     if (mirror_stride < (int64_t)N) return ROME_ERR_INVALID_ARG;   // (a block spans dim * N doubles from its slot: PACKED layouts use stride N)
   ROME_BIND(c);
   void* trees = nullptr;
@@ -407,47 +215,50 @@ int plan_run(rome_upsolve_plan* P, const rome_opts* o, double* mirror_out, int64
     return ROME_OK;
   };
   // store-resident messages: the source blocks as they are NOW -> their proposal rows, and their manikde! bandwidths (once per run)
-  for (int t = 0; t < 3; ++t)
-    if (P->n_smsg[t] > 0 && P->gi > 0) {
-      ROME_HIP(c, launch_scatter_blocks(P->n_smsg[t], N, P->d_smsg_ent[t], P->d_prop[t], (int64_t)kVdim[t] * N, st->bel[0], st->bel[1], st->bel[2], s, /*to_store=*/0));
-      ROME_HIP(c, launch_kde_bandwidth(kVdim[t], P->n_smsg[t], N, P->d_prop[t] + (size_t)P->smsg_base[t] * kVdim[t] * N, kCircBw[t], 1e-2, 1e-6,
-                                             P->d_pbw[t] + (size_t)P->smsg_base[t] * kVdim[t], s));
+  for (int t = 0; t < 3; ++t) {
+    const rome_upsolve_plan::Type& y = P->type[t];
+    if (y.n_smsg > 0 && P->gi > 0) {
+      ROME_HIP(c, launch_scatter_blocks(y.n_smsg, N, y.smsg, y.prop, (int64_t)kVdim[t] * N, st->bel[0], st->bel[1], st->bel[2], s, /*to_store=*/0));
+      ROME_HIP(c, launch_kde_bandwidth(kVdim[t], y.n_smsg, N, y.prop + (size_t)y.smsg_base * kVdim[t] * N, kCircBw[t], 1e-2, 1e-6,
+                                             y.pbw + (size_t)y.smsg_base * kVdim[t], s));
     }
+  }
   for (int it = 0; it < P->gi; ++it) {
     const uint64_t base = o->stream_offset + ((uint64_t)it << 32);
-    const int nsteps = P->n_up > 0 ? (int)P->step_k.size() - 1 : 0;
+    const int nsteps = X.n_up > 0 ? (int)X.step_k.size() - 1 : 0;
     for (int stp = 0; stp < nsteps; ++stp) {
-      const int k0 = P->step_k[stp], k1 = P->step_k[stp + 1];
+      const int k0 = X.step_k[stp], k1 = X.step_k[stp + 1];
       int fam_a[NF], lo_a[NF], hi_a[NF], naf = 0;
       for (int k4 = 0; k4 < NF; ++k4) {
-        const Fam& f = P->fam[k4];
-        const int lo = P->fam_lo[k4][k0], hi = f.n == 0 ? 0 : (k1 < P->n_up ? P->fam_lo[k4][k1] : f.n);
+        const Fam& f = X.fam[k4];
+        const int lo = X.fam_lo[k4][k0], hi = f.n == 0 ? 0 : (k1 < X.n_up ? X.fam_lo[k4][k1] : f.n);
         if (hi > lo) { fam_a[naf] = k4; lo_a[naf] = lo; hi_a[naf] = hi; ++naf; }
       }
       int typ_a[3], nat = 0;
       for (int t = 0; t < 3; ++t) {
-        const int pa = P->up_cnt_before[3 * (size_t)k0 + t], pb = P->up_cnt_before[3 * (size_t)k1 + t];
-        if (pb > pa && P->prop_rows_t[t] > 0) typ_a[nat++] = t;
+        const int pa = X.up_cnt_before[3 * (size_t)k0 + t], pb = X.up_cnt_before[3 * (size_t)k1 + t];
+        if (pb > pa && P->type[t].prop_rows > 0) typ_a[nat++] = t;
       }
       rc = phase(naf, [&](int i, hipStream_t sx) -> int {
         const int k4 = fam_a[i], lo = lo_a[i], hi = hi_a[i];
-        const Fam& f = P->fam[k4];
-        double* out = P->d_prop[f.vt] + (size_t)(f.base + lo) * f.dt * N;
+        const Fam& f = X.fam[k4];
+        double* out = P->type[f.vt].prop + (size_t)(f.base + lo) * f.dt * N;
         ROME_HIP(c, launch_fam(f, P->fd[k4], o, base, lo, hi, st->bel[f.vf], st->bel[f.vt], out, sx, st->bel[f.vmeas()]));
-        if (P->max_k[f.vt] > 1)   // (a plan whose destinations take ONE proposal each -- sampling a graph's measurements, transporting a belief -- multiplies nothing: no manikde!)
-          ROME_HIP(c, launch_kde_bandwidth(f.dt, hi - lo, N, out, kCircBw[f.vt], 1e-2, 1e-6, P->d_pbw[f.vt] + (size_t)(f.base + lo) * f.dt, sx));
+        if (P->type[f.vt].max_k > 1)   // (a plan whose destinations take ONE proposal each -- sampling a graph's measurements, transporting a belief -- multiplies nothing: no manikde!)
+          ROME_HIP(c, launch_kde_bandwidth(f.dt, hi - lo, N, out, kCircBw[f.vt], 1e-2, 1e-6, P->type[f.vt].pbw + (size_t)(f.base + lo) * f.dt, sx));
         return ROME_OK;
       });
       if (rc) return rc;
       rc = phase(nat, [&](int i, hipStream_t sx) -> int {
         const int t = typ_a[i];
-        const int pa = P->up_cnt_before[3 * (size_t)k0 + t], pb = P->up_cnt_before[3 * (size_t)k1 + t];
+        const rome_upsolve_plan::Type& y = P->type[t];
+        const int pa = X.up_cnt_before[3 * (size_t)k0 + t], pb = X.up_cnt_before[3 * (size_t)k1 + t];
         // the product writes the new beliefs IN PLACE into the store (a product reads only proposals and its own variable's block)
-        GibbsPlace place{P->d_upblock[t] + pa, P->has_upstream ? P->d_upstream[t] + pa : nullptr,
-                               (P->has_mirror && mirror_out) ? P->d_upmirror[t] + pa : nullptr, mirror_out, mirror_stride};
-        ROME_HIP(c, launch_product_gibbs(kVdim[t], pb - pa, N, P->prop_rows_t[t], P->d_ptr[t] + pa, P->d_rws[t], P->d_prop[t], P->d_pbw[t],
-                                               st->bel[t], st->bel[t], (unsigned char*)trees + P->tree_off[t], kCircProd[t], P->pi, P->max_k[t],
-                                               o->seed, base + kProdOff[t] + (P->has_upstream ? 0ull : (uint64_t)pa), sx, &place));
+        GibbsPlace place{y.block + pa, X.has_upstream ? y.stream + pa : nullptr, (X.has_mirror && mirror_out) ? y.mirror + pa : nullptr,
+                               mirror_out, mirror_stride};
+        ROME_HIP(c, launch_product_gibbs(kVdim[t], pb - pa, N, y.prop_rows, y.ptr + pa, y.rows, y.prop, y.pbw,
+                                               st->bel[t], st->bel[t], (unsigned char*)trees + y.tree_off, kCircProd[t], P->pi, y.max_k,
+                                               o->seed, base + kProdOff[t] + (X.has_upstream ? 0ull : (uint64_t)pa), sx, &place));
         return ROME_OK;
       });
       if (rc) return rc;
@@ -457,29 +268,32 @@ int plan_run(rome_upsolve_plan* P, const rome_opts* o, double* mirror_out, int64
     for (int e = 0; e < n_cur; ++e) ROME_HIP(c, hipStreamWaitEvent(s, ev_cur[e], 0));
     on_main = true;
   }
-  if (P->has_mirror && P->gi > 0) {
+  if (X.has_mirror && P->gi > 0) {
     // updated variables whose product never ran (no proposals at all) still owe their block to the mirror: the product kernel handles
     // K = 0 (copy), so nothing to do here as long as the type has proposal rows; a type without any row keeps its beliefs
-    for (int t = 0; t < 3; ++t)
-      if (P->n_upt[t] && P->prop_rows_t[t] == 0) {
-        GibbsPlace place{P->d_upblock[t], nullptr, P->d_upmirror[t], mirror_out, mirror_stride};
-        ROME_HIP(c, launch_product_gibbs(kVdim[t], P->n_upt[t], N, 0, P->d_ptr[t], P->d_rws[t], P->d_prop[t], P->d_pbw[t], st->bel[t], st->bel[t],
-                                               (unsigned char*)trees + P->tree_off[t], kCircProd[t], 1, 1, o->seed, 0, s, &place));
+    for (int t = 0; t < 3; ++t) {
+      const rome_upsolve_plan::Type& y = P->type[t];
+      if (y.n_up && y.prop_rows == 0) {
+        GibbsPlace place{y.block, nullptr, y.mirror, mirror_out, mirror_stride};
+        ROME_HIP(c, launch_product_gibbs(kVdim[t], y.n_up, N, 0, y.ptr, y.rows, y.prop, y.pbw, st->bel[t], st->bel[t],
+                                               (unsigned char*)trees + y.tree_off, kCircProd[t], 1, 1, o->seed, 0, s, &place));
       }
+    }
   }
   // ---- results (only when the plan was created with host outputs): the updated beliefs and their manikde! bandwidths
   bool sync = false;
   for (int t = 0; t < 3; ++t) {
-    const int nu = P->n_upt[t];
+    const rome_upsolve_plan::Type& y = P->type[t];
+    const int nu = y.n_up;
     if (nu == 0) continue;
-    if (P->bw_host[t]) {
-      ROME_HIP(c, launch_kde_bandwidth(kVdim[t], nu, N, st->bel[t], kCircBw[t], 1e-2, 1e-6, P->d_bwout[t], s, P->d_upblock[t]));
-      ROME_HIP(c, hipMemcpyAsync(P->bw_host[t], P->d_bwout[t], (size_t)nu * kVdim[t] * 8, hipMemcpyDeviceToHost, s));
+    if (y.bw_host) {
+      ROME_HIP(c, launch_kde_bandwidth(kVdim[t], nu, N, st->bel[t], kCircBw[t], 1e-2, 1e-6, y.bwout, s, y.block));
+      ROME_HIP(c, hipMemcpyAsync(y.bw_host, y.bwout, (size_t)nu * kVdim[t] * 8, hipMemcpyDeviceToHost, s));
       sync = true;
     }
-    if (P->new_host[t]) {
-      ROME_HIP(c, launch_scatter_blocks(nu, N, P->d_gather[t], P->d_newout[t], (int64_t)kVdim[t] * N, st->bel[0], st->bel[1], st->bel[2], s, /*to_store=*/0));
-      if ((rc = fetch_blocks(c, P->layout, nu, kVdim[t], N, P->d_newout[t], P->new_host[t]))) return rc;
+    if (y.new_host) {
+      ROME_HIP(c, launch_scatter_blocks(nu, N, y.gather, y.newout, (int64_t)kVdim[t] * N, st->bel[0], st->bel[1], st->bel[2], s, /*to_store=*/0));
+      if ((rc = fetch_blocks(c, P->layout, nu, kVdim[t], N, y.newout, y.new_host))) return rc;
     }
   }
   if (sync) ROME_HIP(c, hipStreamSynchronize(s));
@@ -665,9 +479,8 @@ int rome_clique_upsolve(rome_ctx* c, const rome_opts* o, const rome_clique_upsol
   const int N = o->n_particles;
   if (N > ROME_MAX_PARTICLES_GIBBS) return ROME_ERR_UNSUPPORTED_N;
   const int nv[3] = {q->n_pose2, q->n_point2, q->n_pose3};
-  const double* vhost[3] = {q->bel_pose2, q->bel_point2, q->bel_pose3};
-  size_t need = 4096;
-  for (int t = 0; t < 3; ++t) { if (nv[t] < 0 || (nv[t] > 0 && !vhost[t])) return ROME_ERR_INVALID_ARG; need += al256((size_t)nv[t] * kVdim[t] * N * 8); }
+  const double* const vhost[3] = {q->bel_pose2, q->bel_point2, q->bel_pose3};
+  for (int t = 0; t < 3; ++t) if (nv[t] < 0 || (nv[t] > 0 && !vhost[t])) return ROME_ERR_INVALID_ARG;
   if (u->up_mirror) return ROME_ERR_INVALID_ARG;   // (mirrors belong to plans: there is no device buffer to mirror into here)
   for (int k = 0; k < u->n_up; ++k) {               // the results are read back: every updated type needs its host outputs
     const int t = u->up_type ? u->up_type[k] : -1;
@@ -676,19 +489,13 @@ int rome_clique_upsolve(rome_ctx* c, const rome_opts* o, const rome_clique_upsol
     if (!nh[t] || !bh[t]) return ROME_ERR_INVALID_ARG;
   }
   ROME_BIND(c);
-  void* arena_v = nullptr;
-  if ((rc = ensure(c, 11, need, &arena_v))) return rc;
-  unsigned char* arena = (unsigned char*)arena_v;
-  size_t used = 0;
   rome_store st;
   st.ctx = c; st.N = N;
+  for (int t = 0; t < 3; ++t) st.nv[t] = nv[t];
   {
     DrainOnExit drain{c->stream};
-    for (int t = 0; t < 3; ++t) {
-      st.nv[t] = nv[t]; st.bel[t] = (double*)(arena + used);
-      if ((rc = stage_blocks(c, o->layout, nv[t], kVdim[t], N, vhost[t], st.bel[t]))) return rc;
-      used += al256((size_t)nv[t] * kVdim[t] * N * 8);
-    }
+    if ((rc = carve_ctx(c, 11, [&](ArenaCursor& a) { lay_beliefs(a, nv, N, st.bel); return (int)ROME_OK; }))) return rc;
+    if ((rc = stage_beliefs(c, o->layout, nv, N, vhost, st.bel))) return rc;
   }
   rome_upsolve_plan P;
   if ((rc = plan_build(c, &st, o, u, &P, true))) return rc;

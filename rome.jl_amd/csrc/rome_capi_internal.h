@@ -4,6 +4,7 @@
 #include "../../include/rome_mi355.h"
 #include "rome_kernels.h"
 #include "rome_layout.h"
+#include "rome_upsolve_index.h"   // (al256, the arena cursor)
 
 #include <cmath>
 #include <cstdlib>
@@ -66,8 +67,6 @@ struct DevBuf {
 // host vectors feed / receive asynchronous copies: whatever way an entry returns (an error in the middle included), the stream is
 // drained before those vectors are destroyed (declare the guard AFTER them)
 struct DrainOnExit { hipStream_t s; ~DrainOnExit() { (void)hipStreamSynchronize(s); } };
-
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the context's workspaces (grown on demand, kept), side streams, pinned staging
 int ensure(rome_ctx* c, int idx, size_t bytes, void** out);
