@@ -11,7 +11,8 @@ namespace rome {
 // translation t only; a Pose2 target's heading passes through unchanged (neither the solve nor the entropy touches it).
 //   CLOSED_FORM / NEWTON: the radial projection  t ← a + ρ (t − a)/‖t − a‖  (also the exact minimum-norm Gauss-Newton step);
 //                         t == a leaves along +x, ρ ≤ 0 returns a (the minimiser of (ρ − n)² over n ≥ 0 is n = 0).
-//   GAUSS_NEWTON:         that step iterated, the functor evaluated at every iterate until |r| ≤ tol.
+//   GAUSS_NEWTON:         that step iterated, the functor evaluated at every iterate until |r| ≤ tol; status 1 for ρ ≤ 0, as NEWTON
+//                         reports it (at ρ = 0 the anchor zeroes the functor, but it is the degenerate ring, not a root).
 //   NELDER_MEAD:          nelder_mead<2> on r² over (x, y) (at fixed θ on a Pose2 target).
 // The measurement ρ = μ + σξ (σ < 0: Uniform(μ − |σ|, μ + |σ|) through the normal CDF of ξ, as BR::measurement); one standard normal
 // per particle from the particle's own Philox call (rng_normals<1>).
@@ -100,7 +101,7 @@ struct RangeBase {
       return 0;
     } else if constexpr (SOLVER == kSolverGaussNewton) {
       for (int it = 0; it < max_iters; ++it) {
-        if (fabs(functor(z, fx, t)) <= tol) return 0;
+        if (fabs(functor(z, fx, t)) <= tol) return z[0] > 0.0 ? 0 : 1;   // (ρ <= 0: the anchor is no root, as verify reports it)
         range_project(z[0], fx[0], fx[1], t[0], t[1]);
       }
       return 1;

@@ -11,7 +11,10 @@ Two ways into the library for the same rows, same streams (stream_offset + row),
 Every output buffer has a guard block before and after the table, pre-filled with NaN (status: -7), checked after the launch.
 
 Hypothesis tables (tests/hypo_ref.py) carry `alt_var`, `hypo_w` and `nullhypo` columns: Dev uploads them where the table has them and
-launch(hypo=...) attaches the named ones; noise=... hands the launch its normals (or, with presampled=1, its measurement samples)."""
+launch(hypo=...) attaches the named ones; noise=... hands the launch its normals (or, with presampled=1, its measurement samples).
+
+Ring tables (tests/ring_ref.py: "br1", "p2r", "ppr0", "ppr1", "pb0", "pb1") go through the range, bearing and bearing-range entries; their
+dimensions and direction come from ring_ref.DIMS / DIR_ALL, and the landmark and pose kinds keep their targets in a store of their own."""
 import ctypes as C
 import functools
 import hashlib
@@ -19,8 +22,11 @@ import hashlib
 import numpy as np
 
 import conv_ref as CR
+import ring_ref as RR
 
-ENTRY = {CR.P2P2: "rome_conv_pose2pose2_dev", CR.BR0: "rome_conv_pose2point2br_dev", CR.P3P3: "rome_conv_pose3pose3_dev"}
+ENTRY = {CR.P2P2: "rome_conv_pose2pose2_dev", CR.BR0: "rome_conv_pose2point2br_dev", CR.P3P3: "rome_conv_pose3pose3_dev",
+         "br1": "rome_conv_pose2point2br_dev", "p2r": "rome_conv_point2point2range_dev", "ppr0": "rome_conv_pose2point2range_dev",
+         "ppr1": "rome_conv_pose2point2range_dev", "pb0": "rome_conv_pose2point2bearing_dev", "pb1": "rome_conv_pose2point2bearing_dev"}
 ST_GUARD = -7
 HYPO_COLUMNS = {"alt_var": 4, "hypo_w": 8, "nullhypo": 8}                                # column -> bytes per row
 CF, NEWTON, GN = 0, 1, 3
@@ -51,7 +57,8 @@ class Dev:
         self.keep = []
         self.mu, self.L = self._up(t["mu"]), self._up(t["L"])
         self.bel_fixed = self._up(t["bel_fixed"], int(shift))
-        self.bel_target = self._up(t["bel_target"], int(shift)) if self.kind == CR.BR0 else self.bel_fixed
+        own = self.kind == CR.BR0 or (self.kind in RR.DIMS and "bel_target" in t)     # (a p2r table has one Point2 store)
+        self.bel_target = self._up(t["bel_target"], int(shift)) if own else self.bel_fixed
         rows = np.ascontiguousarray(t["rows4"], dtype=np.int32)
         self.rows4 = self._up(rows)
         self.cols = [self._up(np.ascontiguousarray(rows[:, k])) for k in range(4)]       # factor, dir, fixed_var, target_var
@@ -74,7 +81,11 @@ def launch(env, d, n_conv, solver, how="packed", status=False, row0=0, shift=Fal
     noise: (n_conv, dz, N) host array for the `noise` field.  dir_all: the direction of a bearing-range table.
     refused=True: the entry point must return an error and store nothing -> its error code."""
     torch, _lib, lib, ctx = env
-    dt, N = (3 if d.kind == CR.BR0 and dir_all == 1 else CR.DIMS[d.kind][2]), d.N     # bearing-range towards the pose: the target is a Pose2
+    ring = d.kind in RR.DIMS
+    if ring:
+        dir_all = RR.DIR_ALL[d.kind]
+    dz = RR.DIMS[d.kind][0] if ring else CR.DIMS[d.kind][0]
+    dt, N = (RR.DIMS[d.kind][2] if ring else 3 if d.kind == CR.BR0 and dir_all == 1 else CR.DIMS[d.kind][2]), d.N     # bearing-range towards the pose: the target is a Pose2
     blk = dt * N
     assert 0 <= row0 and row0 + n_conv <= len(d.t["rows4"]), "rows beyond the table"
     o = _lib.default_opts(solver, n_particles=N, seed=d.t["seed"], stream_offset=d.t["stream_offset"] + row0, **opts)
@@ -88,13 +99,13 @@ def launch(env, d, n_conv, solver, how="packed", status=False, row0=0, shift=Fal
         T.rows4 = d.rows4.data_ptr() + 16 * row0
     else:
         T.factor, T.dir, T.fixed_var, T.target_var = [c.data_ptr() + 4 * row0 for c in d.cols]
-        if d.kind == CR.BR0:
+        if d.kind == CR.BR0 or (ring and d.kind != "p2r"):
             T.dir = None                                                              # the direction of a bearing-range table is dir_all
     T.out = out.data_ptr() + 8 * (blk + off)
     for name in hypo:
         setattr(T, name, d.hypo[name].data_ptr() + HYPO_COLUMNS[name] * row0)
     if noise is not None:
-        assert noise.shape == (n_conv, CR.DIMS[d.kind][0], N)
+        assert noise.shape == (n_conv, dz, N)
         hold = torch.from_numpy(np.ascontiguousarray(noise, dtype=np.float64)).cuda()
         T.noise = hold.data_ptr()
     if status:
@@ -119,6 +130,7 @@ def launch(env, d, n_conv, solver, how="packed", status=False, row0=0, shift=Fal
         ctx.synchronize()
         assert rc != 0, "the entry point accepted the table"
         assert np.isnan(out.cpu().numpy()).all() and (st is None or (st.cpu().numpy() == ST_GUARD).all()), "a refused launch stored something"
+        assert mout is None or np.isnan(mout.cpu().numpy()).all(), "a refused launch stored a mirror block"
         return rc
     _lib.check(rc, ctx.handle)
     ctx.synchronize()
