@@ -61,7 +61,6 @@ class _PlanStub:
     def __init__(self, fn, opts, kw):
         self.fn, self.kw = fn, kw
         self.opts = _lib.Opts.from_buffer_copy(opts)
-        self._keep = (None, self.opts)
 
     def __call__(self):
         raise RuntimeError("plan-only DeviceGraph (bench.py --dry-run): there is no device to launch on")
@@ -311,7 +310,8 @@ class DeviceGraph:
     def _plan(self, fn, opts, _ctx=None, **kw):
         """Pre-builds the rome_conv_dev descriptor once; the returned callable only binds the current
         torch stream and issues the launch (what a captured / replayed step calls).  `_ctx`: a Context whose stream the
-        caller has fixed (one per pipeline slot) -- the launch then is a single C call with no stream lookup."""
+        caller has fixed (one per pipeline slot) -- the launch then is a single C call with no stream lookup.  The callable's `.opts`
+        is the options copy it launches with (a cached launch's stream offset is updated there)."""
         if self.plan_only:
             return _PlanStub(fn, opts, kw)
         keep = []
@@ -328,7 +328,7 @@ class DeviceGraph:
                 rc = fn(hf, po, pc)
                 if rc:
                     check(rc, hf)
-            launch_fixed._keep = (keep, o, cd, _ctx)
+            launch_fixed._keep, launch_fixed.opts = (keep, o, cd, _ctx), o
             return launch_fixed
 
         def launch():
@@ -336,7 +336,7 @@ class DeviceGraph:
             rc = fn(h, po, pc)
             if rc:
                 check(rc, h)
-        launch._keep = (keep, o, cd)
+        launch._keep, launch.opts = (keep, o, cd), o
         return launch
 
     def _conv_kw(self, rec, out, noise=None, status=None, rows=None):

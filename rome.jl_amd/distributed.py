@@ -6,24 +6,26 @@ variables and runs the convolutions that TARGET its variables -- no collective o
 sweep.  The one real exchange step is the separator message of the Bayes tree (IIF `LikelihoodMessage`
 holding a `TreeBelief` of N points per separator variable; SURVEY.md §5 "distributed communication
 backend"): after a sweep every rank publishes the beliefs of its boundary variables and receives the
-ones its cut factors read (`SeparatorExchange`).  Messages are N x dim doubles (2.4 kB per Pose2), i.e.
-latency-bound: the collective is posted asynchronously right after a sweep and completed just before the
-next one, so it overlaps with the next sweep's launch instead of serialising with it (the cut factors then
-read separator beliefs that are one sweep old -- the same asynchrony IIF's clique tasks have).
+ones its cut factors read (`SeparatorPipeline`).  Messages are N x dim doubles (2.4 kB per Pose2), i.e.
+latency-bound: the collective is posted asynchronously right after a sweep and completed `depth` sweeps
+later, so it overlaps with the next sweeps' launches instead of serialising with them (the cut factors then
+read separator beliefs that are `depth` sweeps old -- the same asynchrony IIF's clique tasks have).
+
+Every driver exchanges through ONE all-gather (`_AllGather`: transport and aliasing rule) and hands a family
+record to `rome_conv_dev` through ONE keyword builder (`_family_kw`).
 """
 import numpy as np
 
+# factor classes that no multi-rank driver serves: (class name, PackedGraph table)
+_UNSERVED = (("Point2Point2Range", "p2rng"), ("Pose2Point2Range", "pprng"), ("Pose2Point2Bearing", "pbear"),
+             ("Pose3Pose3XYYaw", "p3xyy"), ("PriorPose3ZRP", "zrp3"), ("Pose3Pose3Rotation", "p3rot"))
 
-def _refuse_range_tables(dg, where):
-    """the multi-rank drivers plan the DeviceGraph.families() tables only: a graph with range-only factors is refused (asked of the
+
+def _refuse_unserved(dg, where):
+    """the multi-rank drivers plan the DeviceGraph.families() tables only: a graph with any other factor is refused (asked of the
     packed graph, which a stand-in for DeviceGraph holds too)"""
-    if dg.packed.has_range():
-        names = [n for n, k in (("Point2Point2Range", "p2rng"), ("Pose2Point2Range", "pprng")) if k in dg.tab]
-        raise TypeError("%s: %s factors are not supported by the multi-rank drivers" % (where, " / ".join(names)))
-    if dg.packed.has_bearing():
-        raise TypeError("%s: Pose2Point2Bearing factors are not supported by the multi-rank drivers" % where)
-    if dg.packed.has_partial3():
-        names = [n for n, k in (("Pose3Pose3XYYaw", "p3xyy"), ("PriorPose3ZRP", "zrp3"), ("Pose3Pose3Rotation", "p3rot")) if k in dg.tab]
+    names = [n for n, k in _UNSERVED if getattr(dg.packed, k)["F"]]
+    if names:
         raise TypeError("%s: %s factors are not supported by the multi-rank drivers" % (where, " / ".join(names)))
 
 
@@ -49,61 +51,45 @@ def shard_convolutions_by_target(target_var, n_vars, world, rank):
     return np.nonzero((t >= lo) & (t < hi))[0]
 
 
-class SeparatorExchange:
-    """All-gather of separator beliefs between graph segments.
+class _AllGather:
+    """THE exchange of this module: every rank's `send` region (n doubles) lands in [rank * n, (rank + 1) * n) of every rank's `recv`
+    region.  It owns the choice of transport --
+      * `comm` (a direct communicator of rome_jl_amd.rccl): `all_gather_f64` enqueued on the stream given to the call, pointers and count
+        computed once;
+      * else, `collective` (world > 1, or the forced one-rank measurement form): `torch.distributed.all_gather_into_tensor` on torch's
+        current stream; work=True posts it asynchronously and returns the work handle;
+      * else the one-rank local copy into the rank's own slice --
+    and the aliasing rule: a `send` that IS the rank's slice of `recv` (the in-place layouts) goes to the direct communicator as it is,
+    to torch.distributed as a copy (it refuses aliasing arguments), and needs no local copy."""
 
-    Every rank publishes `n_sep` belief blocks (rows `publish_rows` of a source tensor [rows, dim, N]);
-    `ghosts` lists, for each ghost block this rank keeps, which (source rank, source slot) feeds it.
-    One fixed-size `all_gather_into_tensor` per exchange (the payload is tiny, so one collective beats
-    per-edge send/recv).  `post()` launches it asynchronously, `complete()` waits and scatters.
-    """
+    def __init__(self, dist, rank, send, recv, collective, comm=None):
+        self.dist, self.comm, self.collective = dist, comm, collective
+        self.send, self.recv = send.view(-1), recv.view(-1)
+        n = self.send.numel()
+        self.own = self.recv[rank * n:(rank + 1) * n]
+        self.in_place = self.send.data_ptr() == self.own.data_ptr()
+        self.args = (self.send.data_ptr(), self.recv.data_ptr(), n)
 
-    def __init__(self, torch, dist, world, rank, publish_rows, ghosts, dim, N, device, dtype=None, always_collective=False):
-        self.torch, self.dist = torch, dist
-        self.world, self.rank = world, rank
-        self.always_collective = always_collective  # issue the collective even for world == 1 (smoke tests)
-        dtype = dtype or torch.float64
-        n_sep = len(publish_rows)
-        self.publish_rows = torch.as_tensor(np.asarray(publish_rows, dtype=np.int64), device=device)
-        self.send = torch.zeros((n_sep, dim, N), dtype=dtype, device=device)
-        self.recv = torch.zeros((world * n_sep, dim, N), dtype=dtype, device=device)
-        self.ghost_blocks = torch.as_tensor(np.asarray([g[0] for g in ghosts], dtype=np.int64), device=device)
-        self.ghost_src = torch.as_tensor(np.asarray([(g[1] % world) * n_sep + g[2] for g in ghosts], dtype=np.int64), device=device)
-        self.pending = None
-        self.have_data = False
-
-    def post(self, source):
-        """Gather this rank's separator rows from `source` and launch the collective (asynchronously)."""
-        self.torch.index_select(source, 0, self.publish_rows, out=self.send)
-        if self.world > 1 or self.always_collective:
-            self.pending = self.dist.all_gather_into_tensor(self.recv.view(-1), self.send.view(-1), async_op=True)
-        else:
-            self.recv.copy_(self.send)
-        self.have_data = True
-
-    def complete(self, beliefs):
-        """Wait for the posted collective (if any) and overwrite the ghost blocks of `beliefs` [V, dim, N]."""
-        if not self.have_data:
-            return
-        if self.pending is not None:
-            self.pending.wait()
-            self.pending = None
-        beliefs.index_copy_(0, self.ghost_blocks, self.recv.index_select(0, self.ghost_src))
-        self.have_data = False
-
-    def exchange(self, source, beliefs):
-        """Synchronous form: post + complete."""
-        self.post(source)
-        self.complete(beliefs)
+    def __call__(self, stream=0, work=False):
+        if self.comm is not None:
+            self.comm.all_gather_f64(*self.args, stream)
+        elif self.collective:
+            return self.dist.all_gather_into_tensor(self.recv, self.send.clone() if self.in_place else self.send, async_op=work)
+        elif not self.in_place:
+            self.own.copy_(self.send)
 
 
-def chain_segment_exchange(torch, dist, world, rank, N, device, publish_rows, ghost_prev, ghost_next, always_collective=False):
-    """The exchange used by bench.py / the weak-scaling layout: segments in a ring; every rank publishes two
-    rows of its proposal table (slot 0: its first pose, slot 1: its last pose);
-    ghost_prev <- previous rank's slot 1, ghost_next <- next rank's slot 0."""
-    return SeparatorExchange(torch, dist, world, rank, publish_rows,
-                             [(ghost_prev, rank - 1, 1), (ghost_next, rank + 1, 0)], 3, N, device,
-                             always_collective=always_collective)
+def _family_kw(rec, rows4, bel_fixed, bel_target, out, rows=None, mirror=None):
+    """The rome_conv_dev keywords of one family record (DeviceGraph.family_table) over the caller's index table `rows4` and buffers.
+    rows = (lo, hi): that slice of the table and of `out`'s rows; mirror = (row -> slot map, send region).  alt_var / hypo_w / nullhypo
+    are present exactly when the record has them: the library picks its kernel from which pointers are null."""
+    cut = (lambda x: x) if rows is None else (lambda x: x[rows[0]:rows[1]])
+    kw = dict(n_conv=rec["n"] if rows is None else rows[1] - rows[0], dir_all=rec["dir_all"], rows4=cut(rows4), mu=rec["mu"], L=rec["L"],
+              bel_fixed=bel_fixed, bel_target=bel_target, out=cut(out))
+    kw.update({k: cut(rec[c]) for k, c in (("alt_var", "alt"), ("hypo_w", "w"), ("nullhypo", "nh")) if rec.get(c) is not None})
+    if mirror is not None:
+        kw.update(mirror_map=mirror[0], mirror_out=mirror[1])
+    return kw
 
 
 class SeparatorPipeline:
@@ -127,7 +113,7 @@ class SeparatorPipeline:
     """
 
     def __init__(self, dg, opts, dist, world, rank, publish, ghosts, always_collective=False, depth=2, rccl_comms=None):
-        _refuse_range_tables(dg, type(self).__name__)
+        _refuse_unserved(dg, type(self).__name__)
         torch = dg.torch
         self.dg, self.dist, self.world, self.rank = dg, dist, world, rank
         self.collective = world > 1 or always_collective
@@ -210,45 +196,39 @@ class SeparatorPipeline:
 
         self.plans = []
         for b in range(D):
-            remap = {vt: {} for vt in vts}
+            # ghost remap of slot b: per variable type a lookup table variable -> block of its store (identity but for the ghosts, which
+            # are blocks of receive buffer b); every index column is ONE gather of the original column through it
+            lut = {vt: torch.arange(self.V[vt], dtype=torch.int32) for vt in vts}
             for vt, gi, src, slot in ghosts:
                 if slot >= npub[vt]:
-                    raise ValueError("ghost refers to slot %d of %s but only %d are published" % (slot, vt.__name__, npub[vt]))
+                    raise ValueError("ghost refers to slot %d of %s but only %d are published" % (slot, vt.name, npub[vt]))
                 g = ghost_block(vt, b, src, slot)
-                remap[vt][int(gi)] = g
+                lut[vt][int(gi)] = g
                 self.store[vt][g].copy_(dg.bel[vt][int(gi)])   # until the first message arrives: the local initial belief
+            lut = {vt: t.to(dev) for vt, t in lut.items()}
+            through = lambda col, vt: torch.where(col >= 0, lut[vt][col.clamp(min=0).long()], col)   # noqa: E731  (-1 = no alternative)
             plans_b = []
             for f in fams:
                 tb = ftab[f]
                 rows = tb["rows4"].clone()
-                for col, vt in ((2, tb["vt_fixed"]), (3, tb["vt_target"])):
-                    for gi, g in remap[vt].items():
-                        rows[:, col][tb["rows4"][:, col] == gi] = g
-                alt = tb["alt"]
-                if alt is not None:
-                    vl = tb["vt_fixed"] if f == "br1" else tb["vt_target"]   # the landmark slot
-                    alt = alt.clone()
-                    for gi, g in remap[vl].items():
-                        alt[tb["alt"] == gi] = g
-                vt_t = tb["vt_target"]
-                kw = dict(n_conv=tb["n"], dir_all=tb["dir_all"], rows4=rows, mu=tb["mu"], L=tb["L"],
-                          bel_fixed=self.store[tb["vt_fixed"]], bel_target=self.store[vt_t], out=self.out[b][f])
-                if alt is not None:
-                    kw.update(alt_var=alt, hypo_w=tb["w"])
-                if tb.get("nh") is not None:     # nullhypo= factors: one probability per row
-                    kw.update(nullhypo=tb["nh"])
+                rows[:, 2], rows[:, 3] = through(rows[:, 2], tb["vt_fixed"]), through(rows[:, 3], tb["vt_target"])
+                if tb["alt"] is not None:
+                    tb = dict(tb, alt=through(tb["alt"], tb["vt_fixed"] if f == "br1" else tb["vt_target"]))   # the landmark slot
+                vt_t, mirror = tb["vt_target"], None
                 if pub_by_f[f]:
                     lo = sec_off[vt_t] + slot0[f] * dim[vt_t] * N
                     # any number of separator rows per family: row -> slot map (rome_conv_dev.mirror_map), -1 = not published
                     mm = torch.full((tb["n"],), -1, dtype=torch.int32)
                     mm[torch.as_tensor(pub_by_f[f], dtype=torch.long)] = torch.arange(len(pub_by_f[f]), dtype=torch.int32)
-                    kw.update(mirror_map=mm.to(dev), mirror_out=self.send[b][lo: lo + len(pub_by_f[f]) * dim[vt_t] * N])
+                    mirror = (mm.to(dev), self.send[b][lo: lo + len(pub_by_f[f]) * dim[vt_t] * N])
+                kw = _family_kw(tb, rows, self.store[tb["vt_fixed"]], self.store[vt_t], self.out[b][f], mirror=mirror)
                 if slot_ctx[b] is not None:
                     kw["_ctx"] = slot_ctx[b]
                 plans_b.append(dg._plan(tb["fn"], opts, **kw))
             self.plans.append(plans_b)
-        self._ag_args = [(self.send[b].data_ptr(), self.recv[b].data_ptr(), self.send[b].numel(),
-                          self.streams[b].cuda_stream if self.streams is not None else 0) for b in range(D)]
+        self.gather = [_AllGather(dist, rank, self.send[b], self.recv[b], self.collective, self.comms[b] if self.comms is not None else None)
+                       for b in range(D)]
+        self._stream = [self.streams[b].cuda_stream if self.streams is not None else 0 for b in range(D)]
         self.k = 0
         # Steps k, k+1, .. run round-robin on `depth` streams.  In the torch.distributed form the join "sweep k+depth waits for
         # collective k" is a wait-for-event packet at the head of stream k % depth (≈ 8 µs of queue latency on this stack, measured);
@@ -259,19 +239,12 @@ class SeparatorPipeline:
         if w is not None:
             w.wait()   # stream-level join (the host runs several steps ahead of the GPU: a host-side query cannot replace it)
         for pl in self.plans[b]:
-            pl()
-        if self.collective:
-            self.works[b] = self.dist.all_gather_into_tensor(self.recv[b], self.send[b], async_op=True)
-        else:
-            self.recv[b][:self.payload].copy_(self.send[b])
+            pl()       # sweeps of step k (direct form: on stream b, which their rome_ctx is bound to) ...
+        self.works[b] = self.gather[b](self._stream[b], work=True)   # ... followed by the separator exchange (direct form: same stream)
 
     def step(self):
         b = self.k % self.depth
-        if self.comms is not None:
-            for pl in self.plans[b]:
-                pl()                                         # sweeps of step k on stream b (their rome_ctx is bound to it)
-            self.comms[b].all_gather_f64(*self._ag_args[b])  # ... followed on the same stream by the separator exchange
-        elif self.streams is not None:
+        if self.comms is None and self.streams is not None:
             with self.dg.torch.cuda.stream(self.streams[b]):
                 self._step_on_current_stream(b)
         else:
@@ -324,7 +297,7 @@ class TargetShardedSweep:
     (V/world x dim x N doubles per rank; Manhattan: 8.4 MB in total) restores the replicated store."""
 
     def __init__(self, dg, opts, dist, world, rank, family="p2p2", always_collective=False, rccl_comm=None):
-        _refuse_range_tables(dg, type(self).__name__)
+        _refuse_unserved(dg, type(self).__name__)
         torch = dg.torch
         self.dg, self.dist, self.world, self.rank = dg, dist, world, rank
         self.collective = world > 1 or always_collective
@@ -348,86 +321,76 @@ class TargetShardedSweep:
         self.store[:V].copy_(any_bel)
         self.rows4 = torch.as_tensor(np.ascontiguousarray(sorted_rows), dtype=torch.int32, device=any_bel.device)
         self.prop = torch.zeros((tb["n"], d, N), dtype=any_bel.dtype, device=any_bel.device)   # sorted-table order
-        o = type(opts).from_buffer_copy(opts) if hasattr(type(opts), "from_buffer_copy") else opts
-        if hasattr(o, "stream_offset"):
-            o.stream_offset = opts.stream_offset + self.row_lo
-        n = self.row_hi - self.row_lo
-        self.n_rows = n
-        mh = {}
-        if tb["alt"] is not None:   # multihypo rows travel with their rows through the sort
-            idx = torch.as_tensor(order, device=tb["alt"].device)
-            self.alt, self.w = tb["alt"][idx].contiguous(), torch.as_tensor(tb["w"])[idx.to(torch.as_tensor(tb["w"]).device)].contiguous()
-            mh = dict(alt_var=self.alt[self.row_lo:self.row_hi], hypo_w=self.w[self.row_lo:self.row_hi])
-        if tb.get("nh") is not None:   # nullhypo rows likewise
-            self.nh = tb["nh"][torch.as_tensor(order, device=tb["nh"].device)].contiguous()
-            mh["nullhypo"] = self.nh[self.row_lo:self.row_hi]
-        self._mh = mh
-        self.plan = dg._plan(tb["fn"], o, n_conv=n, dir_all=tb["dir_all"], rows4=self.rows4[self.row_lo:self.row_hi], mu=tb["mu"], L=tb["L"],
-                             bel_fixed=self.store, bel_target=self.store, out=self.prop[self.row_lo:self.row_hi], **mh) if n else (lambda: None)
+        self.n_rows = self.row_hi - self.row_lo
+        # the family record in sorted-table order: multihypo / nullhypo columns travel with their rows through the sort
+        by_order = lambda col: None if col is None else torch.as_tensor(col)[torch.as_tensor(order, device=torch.as_tensor(col).device)].contiguous()   # noqa: E731
+        self.alt, self.w, self.nh = by_order(tb["alt"]), by_order(tb["w"]), by_order(tb.get("nh"))
+        # ONE launch of the owned rows, built once with step()'s Philox streams (row position in the sorted table); step() and solve_step()
+        # only move the stream offset of its options copy (plan.opts), and only when it is not there already (_offset: where it is)
+        o = type(opts).from_buffer_copy(opts)
+        o.stream_offset = opts.stream_offset + self.row_lo
+        self.plan = dg._plan(tb["fn"], o, **_family_kw(dict(tb, alt=self.alt, w=self.w, nh=self.nh), self.rows4, self.store, self.store, self.prop,
+                                                       rows=(self.row_lo, self.row_hi)))
+        self._step_offset = self._offset = int(o.stream_offset)
         self.mine = self.store[rank * q:(rank + 1) * q]
         self.comm = rccl_comm if (rccl_comm is not None and self.collective and any_bel.is_cuda) else None
+        self._gather = _AllGather(dist, rank, self.mine, self.store, self.collective, self.comm)   # in place: `mine` is a slice of the store
         self.work = None
+        self._solve = None   # the workspace of solve_step, made by its first call
+
+    def _sweep(self, stream_offset):
+        """the launch of the owned rows (none: nothing) with Philox stream `stream_offset` for the first of them"""
+        if self.n_rows:
+            if stream_offset != self._offset:
+                self.plan.opts.stream_offset = self._offset = stream_offset
+            self.plan()
 
     def step(self):
         """sweep of the owned rows, then the all-gather of the owned belief blocks (asynchronous; `wait()` completes it)."""
         self.wait()
-        self.plan()
+        self._sweep(self._step_offset)
         self.exchange()
+
+    def _solve_workspace(self):
+        torch, dev = self.dg.torch, self.store.device
+        n, d = self.prop.shape[0], self.store.shape[1]
+        lo_v = self.rank * self.q
+        return dict(bw=torch.zeros((max(n, 1), d), dtype=self.store.dtype, device=dev),
+                    # CSR of the OWNED variables over the OWNED rows only (rebased to row_lo): the tree build and the
+                    # bandwidths then touch this rank's rows and nothing else
+                    ptr=torch.as_tensor((self.ptr[lo_v:lo_v + self.q + 1] - self.row_lo).astype(np.int32), device=dev),
+                    rows=torch.arange(max(self.n_rows, 1), dtype=torch.int32, device=dev),
+                    out=torch.zeros_like(self.mine),
+                    max_k=int(max(1, np.diff(self.ptr).max())))
 
     def solve_step(self, opts, sweep=0, gibbs_iters=1):
         """One strong-scaled SOLVE iteration with the reference's operations: sweep of the owned rows, `manikde!` bandwidths of
         those proposals, multiscale Gibbs product (manifoldProduct) of the owned variables -- whose proposals are a contiguous
         row range of the target-sorted table -- then the all-gather of the owned beliefs.  Everything but the final exchange is
-        rank-local; bandwidths and product (5.7 of the 5.9 ms of a Manhattan iteration) shard perfectly."""
-        dg, torch = self.dg, self.dg.torch
+        rank-local; bandwidths and product (5.7 of the 5.9 ms of a Manhattan iteration) shard perfectly.
+        The sweep is the constructor's launch at this iteration's stream offset; `opts` gives that offset and the product's options."""
+        dg = self.dg
         self.wait()
-        if not hasattr(self, "_solve"):
-            dev = self.store.device
-            n, d = self.prop.shape[0], self.store.shape[1]
-            lo_v0 = self.rank * self.q
-            self._solve = dict(bw=torch.zeros((max(n, 1), d), dtype=self.store.dtype, device=dev),
-                               # CSR of the OWNED variables over the OWNED rows only (rebased to row_lo): the tree build and the
-                               # bandwidths then touch this rank's rows and nothing else
-                               ptr=torch.as_tensor((self.ptr[lo_v0:lo_v0 + self.q + 1] - self.row_lo).astype(np.int32), device=dev),
-                               rows=torch.arange(max(self.n_rows, 1), dtype=torch.int32, device=dev),
-                               out=torch.zeros_like(self.mine),
-                               max_k=int(max(1, np.diff(self.ptr).max())))
+        if self._solve is None:
+            self._solve = self._solve_workspace()
         S = self._solve
-        d, N = self.store.shape[1], self.store.shape[2]
+        d = self.store.shape[1]
         circ = 0b100 if d == 3 else 0
-        o = type(opts).from_buffer_copy(opts)
-        o.stream_offset = opts.stream_offset + (sweep << 32) + self.row_lo
-        lo_v, q = self.rank * self.q, self.q
         if self.n_rows:
             # the sweep of the owned rows with this iteration's Philox streams, then the manikde! bandwidths of those proposals
-            self._sweep_plan(o)()
+            self._sweep(opts.stream_offset + (sweep << 32) + self.row_lo)
             dg.kde_bandwidth_rows(d, self.n_rows, self.prop[self.row_lo:self.row_hi], circ, S["bw"][self.row_lo:self.row_hi])
         op = type(opts).from_buffer_copy(opts)
-        op.stream_offset = opts.stream_offset + (sweep << 32) + dg.STREAM_PROD2 + lo_v      # product stream = global variable id
-        dg.product_gibbs_rows(op, d, q, S["ptr"], S["rows"], self.prop[self.row_lo:], S["bw"][self.row_lo:], self.n_rows,
+        op.stream_offset = opts.stream_offset + (sweep << 32) + dg.STREAM_PROD2 + self.rank * self.q      # product stream = global variable id
+        dg.product_gibbs_rows(op, d, self.q, S["ptr"], S["rows"], self.prop[self.row_lo:], S["bw"][self.row_lo:], self.n_rows,
                               self.mine, S["out"], circ, int(gibbs_iters), S["max_k"])
         self.mine.copy_(S["out"])
         self.exchange()
 
-    def _sweep_plan(self, o):
-        """The launch of the owned rows (multihypo columns included) with the Philox streams of `o`: built once, afterwards only
-        the stream offset of the cached descriptor's options changes."""
-        if getattr(self, "_solve_plan", None) is None:
-            tb = self.dg.family_table(self.family)
-            self._solve_plan = self.dg._plan(tb["fn"], o, n_conv=self.n_rows, dir_all=tb["dir_all"], rows4=self.rows4[self.row_lo:self.row_hi],
-                                             mu=tb["mu"], L=tb["L"], bel_fixed=self.store, bel_target=self.store,
-                                             out=self.prop[self.row_lo:self.row_hi], **self._mh)
-        self._solve_plan._keep[1].stream_offset = o.stream_offset
-        return self._solve_plan
-
     def exchange(self):
-        if not self.collective:
-            return
-        if self.comm is not None:   # in place: the send block is this rank's slice of the receive buffer
-            st = self.dg.torch.cuda.current_stream(self.store.device).cuda_stream
-            self.comm.all_gather_f64(self.mine.data_ptr(), self.store.data_ptr(), self.mine.numel(), st)
-        else:
-            self.work = self.dist.all_gather_into_tensor(self.store.view(-1), self.mine.reshape(-1).clone(), async_op=True)
+        """the all-gather of the owned belief blocks (torch.distributed: asynchronous, `wait()` completes it)"""
+        st = self.dg.torch.cuda.current_stream(self.store.device).cuda_stream if self.comm is not None else 0
+        self.work = self._gather(st, work=True)
 
     def wait(self):
         if self.work is not None:
@@ -497,7 +460,9 @@ class FrontierShard:
         # (always_collective: the one-rank measurement form -- the own blocks go through the exchange buffer and the scatter too)
         others = [(l, b) for r in range(self.world) if r != self.rank or self.always_collective for l, b in slots[r].items()]
         sc = self.scatter_cls(self.store, [l for l, _ in others], [b for _, b in others], stride=N) if others else None
-        return dict(up=up, scatter=sc, recv=recv, send=send, width=width, U=N, labels=labels)
+        # (`gather`: the exchange of this plan's buffers, what step() calls)
+        gather = _AllGather(self.dist, self.rank, send, recv, self.world > 1 or self.always_collective, self.comm)
+        return dict(up=up, scatter=sc, recv=recv, send=send, width=width, U=N, labels=labels, gather=gather)
 
     def plan(self, cliques, gibbsIters=3, Niter=1, usable=None):
         cliques = [list(c) for c in cliques]
@@ -535,11 +500,7 @@ class FrontierShard:
         st = self.bind_stream()
         if plan["up"] is not None:
             plan["up"].run(opts, mirror_out=plan["send"], mirror_stride=plan["U"])
-        if self.world > 1 or self.always_collective:
-            if self.comm is not None:
-                self.comm.all_gather_f64(plan["send"].data_ptr(), plan["recv"].data_ptr(), plan["send"].numel(), st)
-            else:
-                self.dist.all_gather_into_tensor(plan["recv"], plan["send"].clone())
+        plan["gather"](st)
         if plan["scatter"] is not None:
             plan["scatter"].run(plan["recv"])
 
@@ -579,18 +540,32 @@ class LinearizeShard:
         """as linearize(), the coordinates given as index arrays into the X of begin()"""
         return self.linearize(kind, mu, W, X[ia], None if ib is None else X[ib], ctx)
 
+    def _layout(self, kind, F):
+        """The wire layout of one kind's F rows, the same on the device and the host path: rank k's slice of the receive buffer is the three
+        planes [r (q·dr) | Ja (q·dr·da) | Jb (q·dr·db)], each padded to q = ceil(F / world) rows.
+        -> (dz, dr, da, db, q, doubles per row, rows of every rank)"""
+        from . import api
+        dz, dr, da, db = api._LIN_DIMS[kind]
+        spans = [shard_range(F, self.world, k) for k in range(self.world)]
+        return dz, dr, da, db, -(-F // self.world), dr * (1 + da + db), [hi - lo for lo, hi in spans]
+
+    @staticmethod
+    def _unpack(out, dr, da, db, q, cnt):
+        """the gathered buffer [world, q * per] (host array) -> (r [F, dr], Ja [F, dr, da], Jb [F, dr, db] or None)"""
+        def plane(lo, *shape):   # every rank's rows of the plane that starts at `lo` of its slice, padding dropped
+            hi = lo + q * int(np.prod(shape))
+            return np.concatenate([out[k, lo:hi].reshape(q, *shape)[:n] for k, n in enumerate(cnt)])
+        return plane(0, dr), plane(q * dr, dr, da), plane(q * dr * (1 + da), dr, db) if db else None
+
     def _linearize_dev(self, kind, mu, W, xa, xb, ctx):
         import ctypes as C
         import time
         from . import _lib, api
         torch = self.torch
         ctx = ctx or api.default_context()
-        dz, dr, da, db = api._LIN_DIMS[kind]
-        F = len(mu)
+        dz, dr, da, db, q, per, cnt = self._layout(kind, len(mu))
+        F, n = len(mu), cnt[self.rank]
         lo, hi = shard_range(F, self.world, self.rank)
-        n = hi - lo
-        q = -(-F // self.world)                                  # rows per rank, padded
-        per = dr * (1 + da + db)
         key = int(kind)
         ent = self.cache.get(key)
         # the factor tables of this rank's rows: device-resident across the iterations of ONE solve.  The entry HOLDS the host arrays it
@@ -598,8 +573,10 @@ class LinearizeShard:
         # with the same kind and row count replaces it -- one entry per kind, so repeated / incremental solves do not accumulate tensors.
         if ent is None or ent["mu_host"] is not mu or ent["W_host"] is not W or ent["F"] != F:
             t = lambda a: torch.as_tensor(np.ascontiguousarray(a[lo:hi], dtype=np.float64), device=self.device)   # noqa: E731
+            recv = torch.zeros(self.world * q * per, dtype=torch.float64, device=self.device)
+            send = recv[self.rank * q * per:(self.rank + 1) * q * per]
             self.cache[key] = dict(mu_host=mu, W_host=W, F=F, pin=None, mu=t(np.asarray(mu).reshape(F, dz)), W=t(np.asarray(W).reshape(F, dr * dr)),
-                                   recv=torch.zeros(self.world * q * per, dtype=torch.float64, device=self.device),
+                                   recv=recv, send=send, gather=_AllGather(self.dist, self.rank, send, recv, self.world > 1, self.comm),
                                    xa=torch.empty((max(n, 1), da), dtype=torch.float64, device=self.device),
                                    xb=torch.empty((max(n, 1), max(db, 1)), dtype=torch.float64, device=self.device))
         c = self.cache[key]
@@ -612,8 +589,7 @@ class LinearizeShard:
             if db:
                 c["xb"][:n].copy_(torch.as_tensor(np.ascontiguousarray(xb[lo:hi], dtype=np.float64)), non_blocking=False)
         st.synchronize(); t1 = tick()
-        send = c["recv"][self.rank * q * per:(self.rank + 1) * q * per]
-        base = send.data_ptr()
+        base = c["send"].data_ptr()
         if n:
             P = lambda x: C.c_void_p(x)                           # noqa: E731
             _lib.check(_lib.load().rome_linearize_dev(ctx.handle, int(kind), n, P(c["mu"].data_ptr()), P(c["W"].data_ptr()), P(c["xa"].data_ptr()),
@@ -621,10 +597,7 @@ class LinearizeShard:
                                                       P(base + 8 * q * dr * (1 + da)) if db else None), ctx.handle)
         st.synchronize(); t2 = tick()
         if self.world > 1:
-            if self.comm is not None:
-                self.comm.all_gather_f64(send.data_ptr(), c["recv"].data_ptr(), send.numel(), st.cuda_stream)
-            else:
-                self.dist.all_gather_into_tensor(c["recv"], send.clone())
+            c["gather"](st.cuda_stream)
             st.synchronize()
         t3 = tick()
         if c["pin"] is None:
@@ -634,39 +607,21 @@ class LinearizeShard:
         t4 = tick()
         S = self.stats
         S["calls"] += 1; S["upload_ms"] += 1e3 * (t1 - t0); S["kernel_ms"] += 1e3 * (t2 - t1); S["exchange_ms"] += 1e3 * (t3 - t2); S["download_ms"] += 1e3 * (t4 - t3)
-        cnt = [shard_range(F, self.world, k)[1] - shard_range(F, self.world, k)[0] for k in range(self.world)]
-        r = np.concatenate([out[k, :q * dr].reshape(q, dr)[:cnt[k]] for k in range(self.world)])
-        Ja = np.concatenate([out[k, q * dr:q * dr * (1 + da)].reshape(q, dr, da)[:cnt[k]] for k in range(self.world)])
-        Jb = np.concatenate([out[k, q * dr * (1 + da):].reshape(q, dr, db)[:cnt[k]] for k in range(self.world)]) if db else None
-        return r, Ja, Jb
+        return self._unpack(out, dr, da, db, q, cnt)
 
     def linearize(self, kind, mu, W, xa, xb, ctx=None):
         if self.on_device:
             return self._linearize_dev(kind, mu, W, xa, xb, ctx)
         torch = self.torch
-        F = len(mu)
-        lo, hi = shard_range(F, self.world, self.rank)
-        if hi > lo:
+        dz, dr, da, db, q, per, cnt = self._layout(kind, len(mu))
+        lo, hi = shard_range(len(mu), self.world, self.rank)
+        n = hi - lo
+        recv = torch.zeros(self.world * q * per, dtype=torch.float64, device=self.device)
+        send = recv[self.rank * q * per:(self.rank + 1) * q * per]
+        if n:   # (more ranks than rows: nothing to contribute)
             rk, Ja, Jb = self.kernel(kind, mu[lo:hi], W[lo:hi], xa[lo:hi], None if xb is None else xb[lo:hi], ctx=ctx)
-            dr, da = Ja.shape[1], Ja.shape[2]
-            db = 0 if Jb is None else Jb.shape[2]
-        else:   # more ranks than rows: shapes from a one-row probe are not needed, nothing to contribute
-            rk = Ja = Jb = None
-        # block widths are the same on every rank with rows; agree on them (ranks without rows learn them here)
-        dims = torch.tensor([0, 0, 0] if rk is None else [dr, da, db], dtype=torch.int64, device=self.device)
-        self.dist.all_reduce(dims, op=self.dist.ReduceOp.MAX)
-        dr, da, db = (int(v) for v in dims.tolist())
-        per = dr * (1 + da + db)
-        q = -(-F // self.world)                                  # rows per rank, padded
-        send = torch.zeros(q * per, dtype=torch.float64, device=self.device)
-        if rk is not None:
-            flat = np.concatenate([rk.reshape(hi - lo, -1), Ja.reshape(hi - lo, -1)] + ([Jb.reshape(hi - lo, -1)] if db else []), axis=1)
-            send[:(hi - lo) * per] = torch.as_tensor(flat.ravel(), device=self.device)
-        recv = torch.empty(self.world * q * per, dtype=torch.float64, device=self.device)
-        self.dist.all_gather_into_tensor(recv, send)
-        out = recv.cpu().numpy().reshape(self.world, q, per)
-        rows = np.concatenate([out[k, :shard_range(F, self.world, k)[1] - shard_range(F, self.world, k)[0]] for k in range(self.world)])
-        r = rows[:, :dr]
-        Ja_ = rows[:, dr:dr + dr * da].reshape(F, dr, da)
-        Jb_ = rows[:, dr + dr * da:].reshape(F, dr, db) if db else None
-        return r, Ja_, Jb_
+            assert np.size(rk) == n * dr and np.shape(Ja) == (n, dr, da) and (not db or np.shape(Jb) == (n, dr, db)), "block widths differ from api._LIN_DIMS"
+            for at, plane in ((0, rk), (q * dr, Ja)) + (((q * dr * (1 + da), Jb),) if db else ()):
+                send[at:at + np.size(plane)] = torch.as_tensor(np.ascontiguousarray(plane, dtype=np.float64).ravel(), device=self.device)
+        _AllGather(self.dist, self.rank, send, recv, self.world > 1)()   # (torch.distributed: the planes are host arrays)
+        return self._unpack(recv.cpu().numpy().reshape(self.world, q * per), dr, da, db, q, cnt)

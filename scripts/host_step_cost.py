@@ -1,12 +1,13 @@
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 os.environ.setdefault("MASTER_ADDR","127.0.0.1"); os.environ.setdefault("MASTER_PORT","29533")
 import numpy as np, torch, torch.distributed as dist
 import rome_jl_amd as R
-from rome_jl_amd.distributed import PipelinedSegmentSweep
+from rome_jl_amd.distributed import PipelinedSegmentSweep, TargetShardedSweep
 dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda",0))
 N=100
-fg=R.loadG2o("/root/repo/tests/golden/manhattan.g2o", N=N)
+fg=R.loadG2o(os.path.join(ROOT,"tests","golden","manhattan.g2o"), N=N)
 cov=np.diag([1/44.6,1/399.0,1/9591.0])
 fg.addVariable("ghost_prev",R.Pose2); fg.addVariable("ghost_next",R.Pose2)
 fg.addFactor(["ghost_prev","x0"],R.Pose2Pose2(R.MvNormal([1.0,0,0],cov)))
@@ -33,7 +34,7 @@ for _ in range(2000):
 print("stream ctx %.1f us"%((time.perf_counter()-t)/2000*1e6))
 torch.cuda.synchronize()
 t=time.perf_counter()
-for _ in range(500): pipe.plans[0]()
+for _ in range(500): pipe.plans[0][0]()
 th=(time.perf_counter()-t)/500*1e6; torch.cuda.synchronize()
 print("plan launch host %.1f us"%th)
 t=time.perf_counter()
@@ -50,4 +51,14 @@ t=time.perf_counter()
 for _ in range(500): w=pg._allgather_base(o,i)
 th=(time.perf_counter()-t)/500*1e6; torch.cuda.synchronize()
 print("pg._allgather_base host %.1f us"%th)
+# the strong-scaling driver over the same graph, one rank with the collective forced (as bench.py runs it at world 1)
+sh=TargetShardedSweep(dg,opts,dist,1,0,always_collective=True)
+for _ in range(2000): sh.step()
+sh.wait(); torch.cuda.synchronize()
+t=time.perf_counter()
+for _ in range(2000): sh.step()
+th=time.perf_counter()-t
+sh.wait(); torch.cuda.synchronize()
+tt=time.perf_counter()-t
+print("TargetShardedSweep.step host %.1f us, total per step %.1f us"%(th/2000*1e6, tt/2000*1e6))
 dist.destroy_process_group()

@@ -75,7 +75,7 @@ class OracleDG:
             for m, r in enumerate(mirror_rows):
                 blk = out[r].reshape(-1)
                 mirror_out[m * blk.numel():(m + 1) * blk.numel()].copy_(blk)
-        launch._keep = (None, o_keep)
+        launch.opts = o_keep
         return launch
 
     # ---- the row-range stages of TargetShardedSweep.solve_step, computed by the oracle ----

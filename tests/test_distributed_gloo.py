@@ -1,5 +1,5 @@
-"""N>1 path on CPU: 2 ranks over gloo.  Covers the sharding helpers and the separator-belief
-all-gather (`rome_jl_amd.distributed`), with the oracle standing in -- as test infrastructure only --
+"""N>1 path on CPU: ranks over gloo.  Covers the sharding helpers and the multi-rank drivers
+(`rome_jl_amd.distributed`), with the oracle standing in -- as test infrastructure only --
 for the per-rank sweep compute, so that the sharded result can be checked against the unsharded one."""
 import os
 import socket
@@ -24,25 +24,9 @@ def _worker(rank, world, port, ret):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
         import rome_jl_amd as R
-        from rome_jl_amd.distributed import (chain_segment_exchange, shard_range, owner_of, shard_convolutions_by_target)
+        from rome_jl_amd.distributed import shard_range, owner_of, shard_convolutions_by_target
         import oracle as ro
         N = 32
-        # ---- (a) separator exchange between chained segments ----
-        V = 6  # 4 owned poses + ghost_prev (4) + ghost_next (5)
-        bel = torch.full((V, 3, N), float(rank), dtype=torch.float64)
-        prop = torch.zeros((7, 3, N), dtype=torch.float64)       # proposal table: row 2 = first pose, row 5 = last pose
-        prop[2] = 100.0 + rank; prop[5] = 200.0 + rank
-        ex = chain_segment_exchange(torch, dist, world, rank, N, "cpu", [2, 5], ghost_prev=4, ghost_next=5)
-        ex.complete(bel)                                           # nothing posted yet: no-op
-        ok_a = bool((bel == float(rank)).all())
-        ex.post(prop)                                              # asynchronous collective ...
-        prop[2] = -1.0                                             # ... is not affected by later writes to the source
-        ex.complete(bel)
-        ok_a = ok_a and bool((bel[4] == 200.0 + (rank - 1) % world).all() and (bel[5] == 100.0 + (rank + 1) % world).all()
-                             and (bel[:4] == float(rank)).all())
-        prop[2] = 300.0 + rank
-        ex.exchange(prop, bel)                                     # synchronous form
-        ok_a = ok_a and bool((bel[5] == 300.0 + (rank + 1) % world).all())
         # ---- (b) strong-scaling shard of one graph by target ownership == unsharded sweep ----
         fg = R.synth_manhattan(P=60, loops=25, seed=5, N=N)
         R.dead_reckon_init(fg, seed=2)
@@ -64,7 +48,7 @@ def _worker(rank, world, port, ret):
         ok_c = all(owner_of(i, 60, world) == rank for i in range(lo, hi)) and (hi - lo) == 30
         cover = torch.zeros(len(target)); cover[torch.from_numpy(rows)] = 1; dist.all_reduce(cover)
         ok_d = bool((cover == 1).all())
-        ret[rank] = (ok_a, ok_b, ok_c, ok_d)
+        ret[rank] = (ok_b, ok_c, ok_d)
     finally:
         dist.destroy_process_group()
 
@@ -74,7 +58,7 @@ def test_two_rank_gloo_sharding_and_separator_exchange():
     world = 2
     mgr = mp.Manager(); ret = mgr.dict()
     mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
-    assert dict(ret) == {0: (True, True, True, True), 1: (True, True, True, True)}, dict(ret)
+    assert dict(ret) == {0: (True, True, True), 1: (True, True, True)}, dict(ret)
 
 
 def test_shard_helpers_cover_and_balance():
@@ -556,6 +540,29 @@ def test_target_sharded_solve_step_any_world_equals_one_rank(world, P):
         assert any(lo == hi for lo, hi in spans)                # the empty share really occurred
     for r in range(world):
         assert np.array_equal(ret[r][0], ref), r
+
+
+def test_target_sharded_step_after_solve_step_draws_what_the_first_step_drew():
+    """ONE launch serves step() and solve_step(): both set its stream offset, so a step() after a solve_step() over the same beliefs
+    repeats the first step's proposal table bit for bit (world 1, no process group)."""
+    sys.path.insert(0, ROOT)
+    import rome_jl_amd as R
+    import oracle as ro
+    from rome_jl_amd.distributed import TargetShardedSweep
+    N = 16
+    fg = R.synth_manhattan(P=40, loops=15, seed=9, N=N)
+    R.dead_reckon_init(fg, seed=2)
+    dg = _OracleDG(R, fg, 5)
+    o = ro.make_opts(N=N, seed=5, stream_offset=11)
+    sh = TargetShardedSweep(dg, o, None, 1, 0)
+    initial = sh.store.clone()
+    sh.step(); sh.wait()
+    first = sh.prop.clone()
+    sh.solve_step(o, sweep=2); sh.wait()
+    assert not np.array_equal(sh.prop.numpy(), first.numpy()) and not np.array_equal(sh.store.numpy(), initial.numpy())
+    sh.store.copy_(initial)
+    sh.step(); sh.wait()
+    assert np.array_equal(sh.prop.numpy(), first.numpy())
 
 
 # ---------------------------------------------------------------------------------------------------------
